@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: corner residual+Jacobian evals/s (mode E) on synthetic calib frames.
 
-    python bench.py --gpus N --steps K --warmup W [--frames F | --frames-total F] [--model eucm]
+    python bench.py --gpus N --steps K --warmup W [--frames F | --frames-total F] [--model eucm] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: set-up, warm-up, the K timed steps and the line (`ms_per_step` = wall time of one
+timed step).  `--dump-outputs DIR` also writes what the last timed step computed (r and J, see _dump_outputs).  `--full` adds
+everything else this file measures after the timed region: the `extra` block (mode N, solvers, other models, sizes and rigs,
+sharded solves), the in-run PMC traffic passes, the CPU baseline and the parity check against the oracle.
 
 One process per GPU.  Under torch.distributed.run the launcher sets RANK/LOCAL_RANK/WORLD_SIZE; started plainly with
 `--gpus N` (N > 1, WORLD_SIZE unset) this file is its own launcher: the parent - which never touches the GPU - starts N fresh
@@ -201,6 +206,33 @@ def _pmc_traffic_now(args):
                      "command on the same workload; KiB units, FETCH_SIZE x 2 (gfx950), mean over the k_eval dispatches")
 
 
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def _dump_outputs(out_dir, r_out, J_out, n_corners, D):
+    """--dump-outputs: what the timed path hands its caller after the last step - r [n][2] and J [n][2][D] (one camera: the
+    per-frame [n_i][2][D] blocks concatenate to one [n][2][D] array) - as float64 .npy files.  When both do not fit
+    DUMP_BUDGET_BYTES, the same corners of both are written: a sorted sample drawn by a fixed-seed generator (identical from
+    run to run for the same arguments), with its corner indices in corner_index.npy."""
+    import numpy as np
+    import torch
+    assert J_out.numel() == n_corners * 2 * D, "--dump-outputs expects one camera (J = [n][2][D])"
+    os.makedirs(out_dir, exist_ok=True)
+    r = r_out.view(n_corners, 2)
+    J = J_out.view(n_corners, 2, D)
+    per_corner = (2 + 2 * D) * 8
+    if n_corners * per_corner <= DUMP_BUDGET_BYTES:
+        np.save(os.path.join(out_dir, "residuals.npy"), r.cpu().numpy())
+        np.save(os.path.join(out_dir, "jacobian.npy"), J.cpu().numpy())
+        return
+    m = DUMP_BUDGET_BYTES // (per_corner + 8)
+    idx = np.sort(np.random.default_rng(0).choice(n_corners, size=m, replace=False))
+    sel = torch.from_numpy(idx).to(r_out.device)
+    np.save(os.path.join(out_dir, "corner_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "residuals.npy"), r.index_select(0, sel).cpu().numpy())
+    np.save(os.path.join(out_dir, "jacobian.npy"), J.index_select(0, sel).cpu().numpy())
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -369,7 +401,17 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary (mode N / solver) measurements")
     ap.add_argument("--no-rig", action="store_true", help="skip the two-camera leg of the secondary measurements")
     ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 --pmc passes behind roofline.traffic (two short child runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the secondary measurements (mode N, solvers, other models, sizes and rigs, "
+                         "sharded solves), the in-run rocprofv3 --pmc traffic passes, the CPU baseline and the parity check against "
+                         "the oracle; the --no-* switches above leave parts of it out.  Without it a run does the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's r and J) as DIR/<name>.npy, float64, "
+                         "<= 60 MB in all: whole arrays when they fit, else the same seeded sample of corners on every run")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only: set up, warm up, time the K steps, (dump), print the line
+        args.no_extra = args.no_cpu_baseline = args.no_traffic = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around this process: be one (N fresh workers; this parent never touches the GPU)
@@ -463,6 +505,9 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
     kernel_ms = float(ev0.elapsed_time(ev1)) / args.steps
+    if rank == 0 and args.dump_outputs:
+        # before anything else reuses r_out (the --full legs of other models evaluate into it)
+        _dump_outputs(args.dump_outputs, r_out, J_out, n_corners, D)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -709,7 +754,7 @@ def main():
                 p2.close()
             # BASELINE configs[2]: the other models of the hot path at the headline size - mode E roofline (HIP events on the
             # launch stream, same recipe as the headline), the mode-N build and a Gauss-Newton solve - so that KB4 and
-            # OPENCV5 are measured by the driver's default command too (`--model kb4|opencv5` gives their full lines)
+            # OPENCV5 are measured by a --full run of the default workload too (`--model kb4|opencv5` gives their full lines)
             if args.model == "eucm" and not strong:
                 cfg2 = {}
                 for m2 in ("kb4", "opencv5"):

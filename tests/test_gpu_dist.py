@@ -351,7 +351,7 @@ def test_bench_launches_its_own_ranks_on_the_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--frames", "1000",
-                        "--no-cpu-baseline", "--no-rig", "--no-traffic"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-rig", "--no-traffic"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1

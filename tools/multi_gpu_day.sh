@@ -31,9 +31,9 @@ echo "pytest tests/test_gpu_multi.py tests/test_gpu_dist.py: rc $? : $(tail -1 "
 # ---- 2. bench.py, weak and strong --------------------------------------------------------------------------------------------
 for N in 1 2 4 8; do
     if [ "$N" -gt "$NMAX" ]; then echo "bench --gpus $N: skipped ($NMAX GPU(s) in use)" | tee -a "$O/summary.txt"; continue; fi
-    timeout 1500 python3 bench.py --gpus "$N" --no-cpu-baseline --no-traffic > "$O/bench_weak_n$N.json" 2> "$O/bench_weak_n$N.err"
+    timeout 1500 python3 bench.py --gpus "$N" --full --no-cpu-baseline --no-traffic > "$O/bench_weak_n$N.json" 2> "$O/bench_weak_n$N.err"
     echo "bench --gpus $N (weak, 10 000 frames per GPU): rc $?" | tee -a "$O/summary.txt"
-    timeout 1500 python3 bench.py --gpus "$N" --frames-total 50000 --steps 300 --warmup 50 --no-cpu-baseline --no-traffic > "$O/bench_strong50k_n$N.json" 2> "$O/bench_strong50k_n$N.err"
+    timeout 1500 python3 bench.py --gpus "$N" --frames-total 50000 --steps 300 --warmup 50 --full --no-cpu-baseline --no-traffic > "$O/bench_strong50k_n$N.json" 2> "$O/bench_strong50k_n$N.err"
     echo "bench --gpus $N --frames-total 50000 (strong, configs[3]): rc $?" | tee -a "$O/summary.txt"
 done
 # the refusal path, once: one more GPU than there is
