@@ -453,8 +453,14 @@ int ccal_eval(ccal_problem* p, const double* intr, const double* poses, const do
     ccal_ctx* ctx = p->ctx;
     int rc = ccal_upload_params(p, intr, poses, extr);
     if (rc != CCAL_OK) return rc;
-    if (!p->d_r) HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_r, sizeof(double) * std::max<int64_t>(2 * p->n_corners, 2)));
-    if (!p->d_J) HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_J, sizeof(double) * std::max<int64_t>(p->j_len, 2)));
+    if (!p->d_r) {
+        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_r, sizeof(double) * std::max<int64_t>(2 * p->n_corners, 2)));
+        HIP_TRY(ctx, test_poison_f64(ctx, p->d_r, sizeof(double) * std::max<int64_t>(2 * p->n_corners, 2), false, ctx->stream));
+    }
+    if (!p->d_J) {
+        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_J, sizeof(double) * std::max<int64_t>(p->j_len, 2)));
+        HIP_TRY(ctx, test_poison_f64(ctx, p->d_J, sizeof(double) * std::max<int64_t>(p->j_len, 2), false, ctx->stream));
+    }
     rc = ccal_eval_dev(p, apply_loss, p->d_r, p->d_J);
     if (rc != CCAL_OK) return rc;
     if (p->n_corners) {
@@ -471,7 +477,10 @@ int reprojection_errors_dev(ccal_problem* p, const double* intr, const double* p
     ccal_ctx* ctx = p->ctx;
     int rc = ccal_upload_params(p, intr, poses, extr);
     if (rc != CCAL_OK) return rc;
-    if (!p->d_err) HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1)));
+    if (!p->d_err) {
+        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1)));
+        HIP_TRY(ctx, test_poison_f64(ctx, p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1), false, ctx->stream));
+    }
     for (int c = 0; c < p->n_cams; ++c) {
         KArgs a = make_args(p, c);
         a.err_out = p->d_err;
@@ -506,6 +515,7 @@ int ccal_init_poses(ccal_problem* p, const double* intr, int min_points, double*
         const size_t want = std::max(b_po + b_va, problem_scratch_hint(p));       // (room for validation()'s temporaries too: growing the block later costs a free)
         HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_scratch, want));
         p->scratch_bytes = want;
+        HIP_TRY(ctx, test_poison_f64(ctx, p->d_scratch, b_po, false, ctx->stream));      // (the poses slice; not the counts behind it)
     }
     double* d_po = reinterpret_cast<double*>(p->d_scratch);
     int32_t* d_va = reinterpret_cast<int32_t*>(p->d_scratch + b_po);
@@ -529,7 +539,10 @@ int ccal_validation(ccal_problem* p, int cam, const double* intr, const double* 
     if (p->cams[cam].obs.empty()) return fail(ctx, CCAL_ERR_INVALID_ARG, "camera has no observations");
     int rc = ccal_upload_params(p, intr, poses, extr);
     if (rc != CCAL_OK) return rc;
-    if (!p->d_err) HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1)));
+    if (!p->d_err) {
+        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1)));
+        HIP_TRY(ctx, test_poison_f64(ctx, p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1), false, ctx->stream));
+    }
     KArgs a = make_args(p, cam);
     a.err_out = p->d_err;
     HIP_TRY(ctx, launch_reproj_err(p, cam, a, ctx->stream));

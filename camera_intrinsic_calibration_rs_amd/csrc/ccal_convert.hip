@@ -245,6 +245,7 @@ extern "C" int ccal_convert_model(ccal_ctx* ctx, int src_model, const double* sr
     double* d_buf = nullptr;                    // [src 10 | tgt 10 | out 64 | rays]
     HIP_TRY(ctx, hipMalloc((void**)&d_buf, sizeof(double) * (size_t)(20 + 64 + (size_t)n_grid * CONV_REC)));
     struct Free { double* p; ~Free() { (void)hipFree(p); } } guard{ d_buf };
+    HIP_TRY(ctx, test_poison_f64(ctx, d_buf, sizeof(double) * (size_t)(20 + 64 + (size_t)n_grid * CONV_REC), false, st));
     // The fit runs in the kernels' canonical OPENCV5 order (k1, k2, p1, p2, k3): both parameter vectors are permuted HERE, at the
     // boundary (ccal_model_conventions.ocv5_order), the kernels get the identity
     ModelRt rt = model_rt(ctx);

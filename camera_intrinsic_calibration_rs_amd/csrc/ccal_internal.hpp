@@ -134,6 +134,11 @@ inline void ctx_stream_put(ccal_ctx* ctx, hipStream_t s) {
     if (ctx && !ctx->destroy_requested && ctx->cache_streams.size() < 4) { try { ctx->cache_streams.push_back(s); return; } catch (...) { } }
     (void)hipStreamDestroy(s);
 }
+// Test hook of the second library (-DCCAL_TEST_HOOKS): with CCAL_TEST_POISON_ALLOC=1 fill a freshly allocated (or cache-reused) block
+// of DOUBLES with 0xFF bytes - a quiet NaN - before the library's own clears and uploads, so that a result depending on memory nobody
+// wrote turns into NaN (tests/test_gpu_poison.py).  Never called on indices, offsets, counters, flags or DevState.  Defined out of
+// line in ccal_solver.hip, which each library compiles itself; hidden, so that each library calls its own.  The product's is empty.
+__attribute__((visibility("hidden"))) hipError_t test_poison_f64(ccal_ctx* ctx, void* p, size_t bytes, bool host, hipStream_t s);
 inline void ctx_cache_clear(ccal_ctx* ctx) {
     for (auto& b : ctx->cache_dev) (void)hipFree(b.p);
     for (auto& b : ctx->cache_host) (void)hipHostFree(b.p);

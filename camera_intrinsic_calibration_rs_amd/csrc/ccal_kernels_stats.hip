@@ -272,12 +272,14 @@ hipError_t order_stats_device(const double* d_vals, int64_t n, char* work, doubl
     return hipSuccess;
 }
 
-static hipError_t ensure_scratch(ccal_problem* p, size_t total) {
+// (f64_off, f64_bytes: the slice of doubles the caller puts there - the test hook's poison on a new block)
+static hipError_t ensure_scratch(ccal_problem* p, size_t total, size_t f64_off, size_t f64_bytes) {
     if (p->scratch_bytes >= total) return hipSuccess;
     if (p->d_scratch) { (void)hipStreamSynchronize(p->ctx->stream); ctx_release(p->ctx, p->d_scratch, false); p->d_scratch = nullptr; p->scratch_bytes = 0; }
     const size_t want = std::max(total, problem_scratch_hint(p));
     const hipError_t e = ctx_dev_alloc(p->ctx, (void**)&p->d_scratch, want);
     if (e == hipSuccess) p->scratch_bytes = want;
+    if (e == hipSuccess) return test_poison_f64(p->ctx, p->d_scratch + f64_off, f64_bytes, false, p->ctx->stream);
     return e;
 }
 static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -295,7 +297,7 @@ static hipError_t gather_camera_errors(ccal_problem* p, int cam, const double* d
     const int64_t n = dst[n_list];
     if (n <= 0) return hipSuccess;
     const size_t b_off = up256((size_t)(n_list + 1) * sizeof(int64_t)), b_val = up256((size_t)n * sizeof(double));
-    hipError_t e = ensure_scratch(p, b_off + b_val + order_stats_work_bytes());
+    hipError_t e = ensure_scratch(p, b_off + b_val + order_stats_work_bytes(), b_off, b_val);
     if (e != hipSuccess) return e;
     int64_t* d_dst = reinterpret_cast<int64_t*>(p->d_scratch);
     double* d_a = reinterpret_cast<double*>(p->d_scratch + b_off);

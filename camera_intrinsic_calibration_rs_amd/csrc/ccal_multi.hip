@@ -513,6 +513,8 @@ int ccal_multi_validation(ccal_multi_problem* mp, int cam, const double* intr, c
         const size_t want = std::max(need, order_stats_block_bytes(std::max<int64_t>(mp->n_corners, 1), c0->stream));     // every camera of the problem fits
         if (hipMalloc((void**)&mp->d_gather, want) != hipSuccess) { (void)hipGetLastError(); return mfail(m, CCAL_ERR_NO_MEMORY, "ccal_multi_validation: out of device memory"); }
         mp->gather_bytes = want;
+        if (test_poison_f64(c0, mp->d_gather, (size_t)total * sizeof(double), false, c0->stream) != hipSuccess)      // (the values, not the work area)
+            return mfail(m, CCAL_ERR_HIP, "ccal_multi_validation: test hook failed");
     }
     double* d_all = reinterpret_cast<double*>(mp->d_gather);
     int64_t at = 0;

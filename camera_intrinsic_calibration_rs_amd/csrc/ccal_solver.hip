@@ -45,6 +45,19 @@ using namespace ccal;
 
 namespace ccal {
 
+hipError_t test_poison_f64(ccal_ctx* ctx, void* p, size_t bytes, bool host, hipStream_t s) {
+#ifdef CCAL_TEST_HOOKS
+    // read on every call (not cached in a static): tests switch it per case in-process
+    const char* e = std::getenv("CCAL_TEST_POISON_ALLOC");
+    if (!e || e[0] != '1' || !p || !bytes) return hipSuccess;
+    if (host) { std::memset(p, 0xFF, bytes); return hipSuccess; }
+    return hipMemsetAsync(p, 0xFF, bytes, s ? s : ctx->stream);
+#else
+    (void)ctx; (void)p; (void)bytes; (void)host; (void)s;
+    return hipSuccess;
+#endif
+}
+
 void normal_ws_destroy(ccal_problem* p) {
     NormalWs* w = p->nws;
     if (!w) return;
@@ -133,6 +146,10 @@ static int fused_ws_ensure(ccal_problem* p) {
                                                                                   // the in-process transport alternates between them)
     const size_t d_total = zeroed + 2 * b_no + b_state + b_stage;
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&f->d_block, d_total));
+    // (test hook: the double slices - pf, praw, partial, red | mc_f, cost_f | d_stage; not done_cnt, d_state)
+    HIP_TRY(ctx, test_poison_f64(ctx, f->d_block, zeroed - b_cnt, false, ctx->stream));
+    HIP_TRY(ctx, test_poison_f64(ctx, f->d_block + zeroed, 2 * b_no, false, ctx->stream));
+    HIP_TRY(ctx, test_poison_f64(ctx, f->d_block + zeroed + 2 * b_no + b_state, b_stage, false, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(f->d_block, 0, zeroed, ctx->stream));             // (stream-ordered in front of everything that uses the workspace)
     {
         char* q = f->d_block;
@@ -154,6 +171,7 @@ static int fused_ws_ensure(ccal_problem* p) {
         const bool zc = ns * 6 * sizeof(double) <= kSpreadBytes;         // (beyond kZeroCopyBytes: single-launch groups only, FusedJob::begin)
         const size_t b_hs = up(sizeof(HostStatus)), b_res = zc ? up((ns * 6 + CCAL_PMAX) * sizeof(double)) : 0;
         HIP_TRY(ctx, ctx_host_alloc(ctx, (void**)&f->h_block, b_hs + b_res + b_stage));
+        HIP_TRY(ctx, test_poison_f64(ctx, f->h_block + b_hs, b_res + b_stage, true, nullptr));      // h_result, h_stage (not h_status)
         char* q = f->h_block;
         f->h_status = reinterpret_cast<HostStatus*>(q); q += b_hs;
         f->h_result = zc ? reinterpret_cast<double*>(q) : nullptr; q += b_res;
@@ -183,6 +201,7 @@ int normal_ws_ensure(ccal_problem* p) {
     p->nws = w;
     w->K = p->K; w->RB = red_size(p->K); w->PF = pf_size(p->K);
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->dc, CCAL_KMAX * sizeof(double)));
+    HIP_TRY(ctx, test_poison_f64(ctx, w->dc, CCAL_KMAX * sizeof(double), false, ctx->stream));
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->cols, CCAL_KMAX * sizeof(ColInfo)));
     return CCAL_OK;
 }
@@ -320,11 +339,14 @@ int normal_ws_ensure_general(ccal_problem* p) {
     const size_t gbytes = std::max<int64_t>(gl, 1) * sizeof(double);
     for (int i = 0; i < 2; ++i) {
         HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->G[i], gbytes));
+        HIP_TRY(ctx, test_poison_f64(ctx, w->G[i], gbytes, false, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(w->G[i], 0, gbytes, ctx->stream));     // tile (1,0) of two-tile blocks is never written
         HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->cost_o[i], std::max(p->n_obs, 1) * sizeof(double)));
+        HIP_TRY(ctx, test_poison_f64(ctx, w->cost_o[i], std::max(p->n_obs, 1) * sizeof(double), false, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(w->cost_o[i], 0, std::max(p->n_obs, 1) * sizeof(double), ctx->stream));
     }
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->partial, (size_t)w->RB * std::max(n_pw, w->n_rows) * sizeof(double)));
+    HIP_TRY(ctx, test_poison_f64(ctx, w->partial, (size_t)w->RB * std::max(n_pw, w->n_rows) * sizeof(double), false, ctx->stream));
     // (every clear of this function is ordered on the context's stream: it does not synchronise with the null stream, and the
     // kernels rely on what is never written staying zero - holes in the record buffers, upper-triangle rows of `partial`)
     // k_schurq writes the lower triangle and the extras only: the rows of the upper triangle stay zero.  On the context's
@@ -332,10 +354,14 @@ int normal_ws_ensure_general(ccal_problem* p) {
     // elimination writes the buffer
     HIP_TRY(ctx, hipMemsetAsync(w->partial, 0, (size_t)w->RB * std::max(n_pw, w->n_rows) * sizeof(double), ctx->stream));
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->red, 2 * (size_t)(w->RB + 8) * sizeof(double)));      // two buffers: the in-process transport alternates
+    HIP_TRY(ctx, test_poison_f64(ctx, w->red, 2 * (size_t)(w->RB + 8) * sizeof(double), false, ctx->stream));
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->pf, (size_t)std::max(p->n_slots, 1) * w->PF * sizeof(double)));
+    HIP_TRY(ctx, test_poison_f64(ctx, w->pf, (size_t)std::max(p->n_slots, 1) * w->PF * sizeof(double), false, ctx->stream));
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->mc_slot, (size_t)std::max(p->n_slots, 1) * sizeof(double)));
+    HIP_TRY(ctx, test_poison_f64(ctx, w->mc_slot, (size_t)std::max(p->n_slots, 1) * sizeof(double), false, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(w->mc_slot, 0, (size_t)std::max(p->n_slots, 1) * sizeof(double), ctx->stream));
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->scal, 8 * sizeof(double)));
+    HIP_TRY(ctx, test_poison_f64(ctx, w->scal, 8 * sizeof(double), false, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(w->scal, 0, 8 * sizeof(double), ctx->stream));
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->flags, 4 * sizeof(int32_t)));
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->d_gstate, sizeof(DevState)));
@@ -345,6 +371,7 @@ int normal_ws_ensure_general(ccal_problem* p) {
     std::memset((void*)w->h_gstatus, 0, sizeof(HostStatus));
     HIP_TRY(ctx, hipMemsetAsync(w->flags, 0, 4 * sizeof(int32_t), ctx->stream));
     HIP_TRY(ctx, hipHostMalloc((void**)&w->h_pinned, (size_t)(w->RB + 16) * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(ctx, test_poison_f64(ctx, w->h_pinned, (size_t)(w->RB + 16) * sizeof(double), true, nullptr));
     w->general_ready = true;
     return normal_upload_cols(p);
 }

@@ -43,11 +43,13 @@ def test_library_exports_nothing_beyond_the_header():
 
 
 def test_no_test_hooks_in_the_product_library():
-    """Fault injection (CCAL_TEST_FAIL_SHARD) is compiled only into the second library the tests load (-DCCAL_TEST_HOOKS);
-    the product .so does not even contain the string."""
+    """Fault injection (CCAL_TEST_FAIL_SHARD) and the allocation poison (CCAL_TEST_POISON_ALLOC, tests/test_gpu_poison.py) are
+    compiled only into the second library the tests load (-DCCAL_TEST_HOOKS); the product .so does not even contain the strings."""
     blob = open(_ffi.LIB_PATH, "rb").read()
     assert b"CCAL_TEST_" not in blob
-    assert b"CCAL_TEST_FAIL_SHARD" in open(_ffi.LEGACY_LIB_PATH, "rb").read()
+    legacy = open(_ffi.LEGACY_LIB_PATH, "rb").read()
+    assert b"CCAL_TEST_FAIL_SHARD" in legacy
+    assert b"CCAL_TEST_POISON_ALLOC" in legacy
 
 
 def test_host_only_entry_points():
