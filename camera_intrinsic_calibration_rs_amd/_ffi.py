@@ -11,9 +11,9 @@ PMAX = 10
 MAX_CAMS = 8
 KMAX = 128
 
-OK, ERR_INVALID_ARG, ERR_HIP, ERR_NONFINITE, ERR_NOT_PD, ERR_NO_CONVERGENCE, ERR_UNSUPPORTED, ERR_NO_MEMORY = range(8)
+OK, ERR_INVALID_ARG, ERR_HIP, ERR_NONFINITE, ERR_NOT_PD, ERR_NO_CONVERGENCE, ERR_UNSUPPORTED, ERR_NO_MEMORY, NO_RESULT = range(9)
 STATUS_NAMES = ["CCAL_OK", "CCAL_ERR_INVALID_ARG", "CCAL_ERR_HIP", "CCAL_ERR_NONFINITE", "CCAL_ERR_NOT_PD",
-                "CCAL_ERR_NO_CONVERGENCE", "CCAL_ERR_UNSUPPORTED", "CCAL_ERR_NO_MEMORY"]
+                "CCAL_ERR_NO_CONVERGENCE", "CCAL_ERR_UNSUPPORTED", "CCAL_ERR_NO_MEMORY", "CCAL_NO_RESULT"]
 METHOD_GN, METHOD_LM = 0, 1
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1, 2
 MULTI_MAX_DEVICES = 16
@@ -108,6 +108,10 @@ SYMBOLS = [
     ("ccal_solve_batch", C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(SolverOpts), C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp),
                                    C.POINTER(Report)]),
     ("ccal_init_poses", C.c_int, [_vp, _dp, C.c_int, _dp, _ip]),
+    ("ccal_rdh_batch", C.c_int, [_vp, C.c_int, _lp, _dp, C.POINTER(C.c_uint64), C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp]),
+    ("ccal_radial_distortion_homography", C.c_int, [_vp, _dp, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _dp, _ip, _ip]),
+    ("ccal_homography_to_focal", C.c_int, [_dp, _dp]),
+    ("ccal_init_poses_division", C.c_int, [_vp, C.c_double, C.c_int, _dp, _ip]),
     ("ccal_pin_buffer", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("ccal_unpin_buffer", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ccal_init_camera_extrinsic", C.c_int, [_dp, _dp, C.c_int, _dp, C.c_int, C.POINTER(Report)]),

@@ -12,6 +12,13 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   util::calib_all_camera_with_extrinsics (src/util.rs:567-715)  calib_all_camera_with_extrinsics
   util::validation                  (src/util.rs:721-795)       validation
   io::write_report / object_to_json (src/io.rs)                 write_report / model_to_json / poses_to_json / ...
+  types::CalibParams                (src/types.rs:6-10)         CalibParams
+  util::find_best_two_frames_idx    (src/util.rs:168-219)       find_best_two_frames_idx
+  optimization::homography::radial_distortion_homography        radial_distortion_homography (+ rdh_sample_indices)
+  optimization::homography::homography_to_focal                 homography_to_focal
+  optimization::linear::init_pose   (linear.rs:5-21)            init_pose
+  (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
+   not here yet - see README, "From detections alone")
 
 Differences, on purpose: (1) `calib_camera` takes the per-frame initial poses as an argument (the
 reference computes them inside with sqpnp, src/util.rs:418-436, which is outside the hot path); frames
@@ -32,7 +39,7 @@ import numpy as np
 
 from . import _ffi
 from .engine import CcalError, Context, MultiContext, MultiProblem, Problem, default_opts, make_desc
-from .synth import MODEL_NAMES, MODEL_NPARAMS, PMAX, rodrigues, rotmat_to_rvec
+from .synth import MODEL_NAMES, MODEL_NPARAMS, PMAX, rodrigues, rotmat_to_rvec, splitmix64
 
 _MODEL_KEYS = {
     "ucm": ["fx", "fy", "cx", "cy", "alpha"],
@@ -116,6 +123,9 @@ class GenericModel:
 
     def height(self) -> float:
         return self._h
+
+    def set_w_h(self, w: int, h: int) -> None:
+        self._w, self._h = float(w), float(h)
 
     def copy(self) -> "GenericModel":
         return GenericModel(self.kind, self._params, self._w, self._h)
@@ -565,3 +575,109 @@ def frames_from_synth(sp, cam: int = 0) -> List[Optional[FrameFeature]]:
         feats = {k: FeaturePoint(tuple(sp.p2d[a + k]), tuple(sp.p3d[a + k])) for k in range(b - a)}
         out[int(sp.obs_slot[o])] = FrameFeature(0, (int(sp.width[cam]), int(sp.height[cam])), feats)
     return out
+
+
+# ----------------------------------------------------------------------------- calibration from detections alone
+@dataclasses.dataclass
+class CalibParams:                       # src/types.rs:6-10
+    fixed_focal: Optional[float] = None
+    disabled_distortion_num: int = 0
+    one_focal: bool = False
+
+    def to_json_obj(self) -> dict:
+        return {"fixed_focal": self.fixed_focal, "disabled_distortion_num": int(self.disabled_distortion_num),
+                "one_focal": bool(self.one_focal)}
+
+    @staticmethod
+    def from_json_obj(d: dict) -> "CalibParams":
+        ff = d.get("fixed_focal")
+        return CalibParams(None if ff is None else float(ff), int(d.get("disabled_distortion_num", 0)), bool(d.get("one_focal", False)))
+
+
+def find_best_two_frames_idx(detected_feature_frames: Sequence[Optional[FrameFeature]], random_pick: bool,
+                             seed: Optional[int] = None) -> Tuple[int, int]:
+    """util::find_best_two_frames_idx (src/util.rs:168-219).  Among the frames with the maximal corner count: the one whose
+    detections cover the largest bounding box, and the one whose centroid lies farthest from the mean centroid (ties: the
+    later frame, as a stable ascending sort's last element).  `random_pick`: two of them at random - reproducible under `seed`
+    (the reference's generator is unseeded)."""
+    best, idxs = 0, []
+    for i, f in enumerate(detected_feature_frames):
+        if f is None:
+            continue
+        n = len(f.features)
+        if n > best:
+            best, idxs = n, [i]
+        elif n == best:
+            idxs.append(i)
+    if random_pick:
+        pick = np.random.default_rng(seed).permutation(len(idxs))
+        return idxs[int(pick[0])], idxs[int(pick[1])]                  # IndexError with one candidate: the reference panics
+    pts = {i: np.array([fp.p2d for fp in detected_feature_frames[i].features.values()], dtype=np.float32) for i in idxs}
+    centre = {i: pts[i].mean(axis=0) for i in idxs}
+    mean_centre = np.mean([centre[i] for i in idxs], axis=0)
+    by_distance = sorted(idxs, key=lambda i: float(((centre[i] - mean_centre) ** 2).sum()))
+    by_area = sorted(idxs, key=lambda i: float(np.prod(pts[i].max(axis=0) - pts[i].min(axis=0))))
+    return by_area[-1], by_distance[-1]
+
+
+def rdh_sample_indices(seed: int, n_pairs: int, n_hyp: int) -> np.ndarray:
+    """Host twin of the RANSAC kernel's sampler: [n_hyp, 6] distinct pair indices - hypothesis h runs a partial Fisher-Yates
+    shuffle of 0 .. n_pairs-1 on splitmix64(seed, 6, stream=h): draw k swaps position k with k + z_k mod (n_pairs - k)."""
+    if n_pairs < 6:
+        raise ValueError("six distinct indices need at least six pairs")
+    out = np.empty((n_hyp, 6), dtype=np.int32)
+    for h in range(n_hyp):
+        z = splitmix64(int(seed), 6, stream=h)
+        a = np.arange(n_pairs)
+        for k in range(6):
+            j = k + int(z[k] % np.uint64(n_pairs - k))
+            a[k], a[j] = a[j], a[k]
+        out[h] = a[:6]
+    return out
+
+
+def _normalised_pairs(frame_feature0: FrameFeature, frame_feature1: FrameFeature) -> np.ndarray:
+    """Corners whose ids both frames hold (ids ascending), (p - (w/2, h/2)) / max(w/2, h/2) with the FIRST frame's size
+    (src/optimization/homography.rs:223-238)."""
+    w, h = frame_feature0.img_w_h
+    c = np.array([w / 2.0, h / 2.0]); half = max(w / 2.0, h / 2.0)
+    ids = sorted(set(frame_feature0.features) & set(frame_feature1.features))
+    p0 = np.array([frame_feature0.features[i].p2d for i in ids], dtype=np.float64).reshape(-1, 2)
+    p1 = np.array([frame_feature1.features[i].p2d for i in ids], dtype=np.float64).reshape(-1, 2)
+    return np.concatenate([(p0 - c) / half, (p1 - c) / half], axis=1)
+
+
+def radial_distortion_homography(frame_feature0: FrameFeature, frame_feature1: FrameFeature, seed: int = 0, n_hyp: int = 1000,
+                                 ctx: Optional[Context] = None) -> Tuple[float, np.ndarray]:
+    """optimization::homography::radial_distortion_homography (homography.rs:218-271) on the GPU: (lambda, H [3, 3]).
+    Without one valid hypothesis the reference returns its initial (0, zeros): so does this."""
+    r = _ctx(ctx).rdh_batch([_normalised_pairs(frame_feature0, frame_feature1)], [seed], n_hyp)
+    return float(r["lambda"][0]), r["H"][0].copy()
+
+
+def homography_to_focal(h_mat) -> Optional[float]:
+    """optimization::homography::homography_to_focal (homography.rs:274-325); None where the reference returns None."""
+    H = np.ascontiguousarray(h_mat, dtype=np.float64).reshape(9)
+    f = C.c_double()
+    rc = _ffi.load().ccal_homography_to_focal(H.ctypes.data_as(C.POINTER(C.c_double)), C.byref(f))
+    if rc == _ffi.NO_RESULT:
+        return None
+    if rc != _ffi.OK:
+        raise CcalError(rc, "ccal_homography_to_focal")
+    return float(f.value)
+
+
+def init_pose(frame_feature: FrameFeature, lam: float, ctx: Optional[Context] = None
+              ) -> Tuple[Tuple[float, float, float], Tuple[float, float, float]]:
+    """optimization::linear::init_pose (linear.rs:5-21): division-model undistortion, planar PnP -> (rvec, tvec)."""
+    slots, obs_cam, obs_slot, offs, X, U = _flatten([[frame_feature]], [[0]])
+    w, h = frame_feature.img_w_h
+    d, keep = make_desc(1, [MODEL_NAMES["ucm"]], [w], [h], False, 1, obs_cam, obs_slot, offs, X[:, 0], X[:, 1], X[:, 2], U[:, 0], U[:, 1], 1.0)
+    prob = Problem(_ctx(ctx), d, keep)
+    try:
+        poses, used = prob.init_poses_division(lam, 4)
+    finally:
+        prob.close()
+    if used[0] == 0:
+        raise RuntimeError("init_pose: no pose from these detections")            # sqpnp_solve_glam(..).unwrap()
+    return tuple(float(v) for v in poses[0, :3]), tuple(float(v) for v in poses[0, 3:])

@@ -75,7 +75,7 @@ int ccal_set_model_conventions(ccal_ctx* ctx, const ccal_model_conventions* in) 
     return CCAL_OK;
 }
 
-const char* ccal_version(void) { return "ccal-mi355x 0.2.0 (gfx950)"; }
+const char* ccal_version(void) { return "ccal-mi355x 0.3.0 (gfx950)"; }
 int ccal_model_num_params(int model) { return (model >= 0 && model < kNumModels) ? model_np(model) : model == CCAL_MODEL_EUCMT ? 8 : -1; }
 
 int ccal_ctx_create(int device_id, void* hip_stream, ccal_ctx** out) {

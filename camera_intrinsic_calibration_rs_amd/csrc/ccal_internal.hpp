@@ -265,6 +265,8 @@ int reprojection_errors_dev(ccal_problem* p, const double* intr, const double* p
 // ccal_kernels_init.hip
 hipError_t launch_pose_init(const ccal_problem* p, int cam, const double* d_intr, double* d_poses_obs, int32_t* d_valid,
                             int min_points, hipStream_t s);
+hipError_t launch_pose_init_division(const ccal_problem* p, int cam, double lambda, double* d_poses_obs, int32_t* d_valid,
+                                     int min_points, hipStream_t s);
 // Dynamic LDS above 48 KiB has to be enabled per kernel AND per device: remember the largest size enabled on each
 // device of this process (contexts on several GPUs may share the process).  Launchers run on any host thread
 // (ccal_solve_batch / ccal_solve_sharded drive one thread per context): the fast path is one atomic load, the

@@ -11,6 +11,11 @@
 
 namespace ccal {
 
+// Not a camera model of the engine: the one-parameter division model of the two-frame initialisation (init_pose,
+// src/optimization/linear.rs:5-21) as an unprojection variant of k_pose_init.  th = [half, half, w/2, h/2, lambda]:
+// bearing = ((p2d - c) / half) / (1 + lambda r^2).
+constexpr int kUnprojDivision = 100;
+
 // unproject + divide by z: the model inverse as published (UCM/EUCM closed form, Usenko et al. 2018;
 // KB4 Newton on theta; OPENCV5 fixed-point undistortion).  Returns false where the reference's
 // `unproject` yields None (outside the model's domain) or the ray is not in front of the camera.
@@ -18,7 +23,12 @@ template <int MODEL>
 __device__ __forceinline__ bool unproject_normalized(const double* th, double small_radius, double u, double v, double& xn, double& yn) {
     const double mx = (u - th[2]) / th[0], my = (v - th[3]) / th[1];
     const double r2 = mx * mx + my * my;
-    if constexpr (MODEL == kUCM || MODEL == kEUCM) {
+    if constexpr (MODEL == kUnprojDivision) {
+        const double sc = 1.0 + th[4] * r2;
+        if (!(sc > 1e-9)) return false;                         // beyond the division model's domain: no ray
+        xn = mx / sc; yn = my / sc;
+        return true;
+    } else if constexpr (MODEL == kUCM || MODEL == kEUCM) {
         const double alpha = th[4], beta = (MODEL == kEUCM) ? th[5] : 1.0;
         if (alpha > 0.5 && r2 > 1.0 / (beta * (2.0 * alpha - 1.0))) return false;
         const double t1 = 1.0 - (2.0 * alpha - 1.0) * beta * r2;
@@ -69,6 +79,7 @@ struct InitArgs {
     int32_t* valid_obs;     // [n_obs]     number of corners used, 0 = no pose
     int32_t min_points;
     ModelRt rt;             // the context's run-time conventions
+    double division[5];     // kUnprojDivision only: th as above
 };
 
 template <int MODEL>
@@ -80,7 +91,12 @@ __global__ __launch_bounds__(256) void k_pose_init(const InitArgs a) {
     const int64_t start = a.obs_off[o];
     const int n = (int)(a.obs_off[o + 1] - start);
     double th[th_len<MODEL>()];
-    load_theta<MODEL, false>(a.intr + a.cam * CCAL_PMAX, a.rt, th);
+    if constexpr (MODEL == kUnprojDivision) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) th[i] = a.division[i];
+    } else {
+        load_theta<MODEL, false>(a.intr + a.cam * CCAL_PMAX, a.rt, th);
+    }
 
     double M[36], rhs[8];            // upper triangle of A^T A (row-major packed) and A^T b
 #pragma unroll
@@ -179,10 +195,27 @@ __global__ __launch_bounds__(256) void k_pose_init(const InitArgs a) {
     a.valid_obs[o] = ok ? cnt : 0;
 }
 
-hipError_t launch_pose_init(const ccal_problem* p, int cam, const double* d_intr, double* d_poses_obs, int32_t* d_valid, int min_points, hipStream_t s) {
+static InitArgs pose_init_args(const ccal_problem* p, int cam) {
     InitArgs a = {};
     a.x = p->d_x; a.y = p->d_y; a.z = p->d_z; a.u = p->d_u; a.v = p->d_v;
     a.obs_off = p->d_obs_off; a.list = p->cams[cam].d_obs; a.n_list = (int32_t)p->cams[cam].obs.size(); a.cam = cam;
+    return a;
+}
+
+// init_pose of the two-frame initialisation: centre and scale from the camera's image size, as linear.rs:6-9
+hipError_t launch_pose_init_division(const ccal_problem* p, int cam, double lambda, double* d_poses_obs, int32_t* d_valid, int min_points, hipStream_t s) {
+    InitArgs a = pose_init_args(p, cam);
+    const double hw = 0.5 * p->cams[cam].width, hh = 0.5 * p->cams[cam].height, half = hw > hh ? hw : hh;
+    a.division[0] = half; a.division[1] = half; a.division[2] = hw; a.division[3] = hh; a.division[4] = lambda;
+    a.poses_obs = d_poses_obs; a.valid_obs = d_valid; a.min_points = min_points; a.rt = model_rt(p->ctx);
+    const int blocks = (a.n_list + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pose_init<kUnprojDivision>, dim3(blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_pose_init(const ccal_problem* p, int cam, const double* d_intr, double* d_poses_obs, int32_t* d_valid, int min_points, hipStream_t s) {
+    InitArgs a = pose_init_args(p, cam);
     a.intr = d_intr; a.poses_obs = d_poses_obs; a.valid_obs = d_valid; a.min_points = min_points; a.rt = model_rt(p->ctx);
     const int blocks = (a.n_list + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (blocks == 0) return hipSuccess;

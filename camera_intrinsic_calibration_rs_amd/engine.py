@@ -92,6 +92,41 @@ class Context:
             raise CcalError(rc, "ccal_rccl_comm_create", self.last_error())
         return h.value
 
+    # -- RANSAC radial-distortion homography (ccal_rdh_batch) -------------------------------------------------
+    def rdh_batch(self, pairs_list, seeds, n_hyp: int = 1000, per_hypothesis: bool = False):
+        """n independent problems in one launch.  pairs_list: arrays [n_i, 4] of normalised (x, y, x', y'); seeds: one uint64
+        each.  Returns a dict of per-problem arrays `lambda` [n], `H` [n, 3, 3], `score` [n], `best` [n] (-1: none), `n_valid` [n]
+        and, with per_hypothesis, `hyp_sample` [n, n_hyp, 6], `hyp_lambda`, `hyp_H` [n, n_hyp, 9], `hyp_score` (+inf: none)."""
+        n = len(pairs_list)
+        arrs = [_f64(a).reshape(-1, 4) for a in pairs_list]
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(a) for a in arrs], out=offs[1:])
+        allp = np.ascontiguousarray(np.concatenate(arrs)) if n else np.zeros((0, 4))
+        if allp.size == 0:
+            allp = np.zeros((1, 4))
+        sd = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+        if len(sd) != n:
+            raise ValueError("one seed per problem")
+        m = max(n, 1)
+        nan = np.nan
+        out = {"lambda": np.full(m, nan), "H": np.full((m, 3, 3), nan), "score": np.full(m, nan),
+               "best": np.full(m, -2, dtype=np.int32), "n_valid": np.full(m, -2, dtype=np.int32)}
+        hyp = {"hyp_sample": None, "hyp_lambda": None, "hyp_H": None, "hyp_score": None}
+        if per_hypothesis:
+            hyp = {"hyp_sample": np.full((m, n_hyp, 6), -2, dtype=np.int32), "hyp_lambda": np.full((m, n_hyp), nan),
+                   "hyp_H": np.full((m, n_hyp, 9), nan), "hyp_score": np.full((m, n_hyp), nan)}
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.lib.ccal_rdh_batch(self.handle, n, offs.ctypes.data_as(C.POINTER(C.c_int64)), _dp(allp),
+                                     sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_hyp), _dp(out["lambda"]), _dp(out["H"]),
+                                     _dp(out["score"]), ip(out["best"]), ip(out["n_valid"]), ip(hyp["hyp_sample"]),
+                                     _dp(hyp["hyp_lambda"]), _dp(hyp["hyp_H"]), _dp(hyp["hyp_score"]))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_rdh_batch", self.last_error())
+        out = {k: v[:n] for k, v in out.items()}
+        if per_hypothesis:
+            out.update({k: v[:n] for k, v in hyp.items()})
+        return out
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first
@@ -541,6 +576,14 @@ class Problem:
         poses = np.zeros((max(n_obs, 1), 6)); used = np.zeros(max(n_obs, 1), dtype=np.int32)
         self._check(self.lib.ccal_init_poses(self.handle, _dp(intr), int(min_points), _dp(poses),
                                              used.ctypes.data_as(C.POINTER(C.c_int32))), "ccal_init_poses")
+        return poses[:n_obs], used[:n_obs]
+
+    def init_poses_division(self, lam: float, min_points: int = 10):
+        """init_pose (src/optimization/linear.rs:5-21) of every observation frame: division-model bearings + planar PnP."""
+        n_obs = self.n_obs
+        poses = np.zeros((max(n_obs, 1), 6)); used = np.zeros(max(n_obs, 1), dtype=np.int32)
+        self._check(self.lib.ccal_init_poses_division(self.handle, float(lam), int(min_points), _dp(poses),
+                                                      used.ctypes.data_as(C.POINTER(C.c_int32))), "ccal_init_poses_division")
         return poses[:n_obs], used[:n_obs]
 
     # -- validation ---------------------------------------------------------------------------------

@@ -27,6 +27,10 @@
  *   ccal_init_poses          the unproject + sqpnp pose initialisation inside calib_camera  src/util.rs:418-436
  *   ccal_reprojection_errors / ccal_validation
  *                            validation()                                 src/util.rs:721-795
+ *   ccal_rdh_batch / ccal_radial_distortion_homography
+ *                            radial_distortion_homography                 src/optimization/homography.rs:218-271
+ *   ccal_homography_to_focal homography_to_focal                          src/optimization/homography.rs:274-325
+ *   ccal_init_poses_division init_pose                                    src/optimization/linear.rs:5-21
  *
  * Parameter layout.
  *   intr   [n_cams][CCAL_PMAX]  FULL model parameters [fx,fy,cx,cy,dist...] per camera, like
@@ -74,7 +78,9 @@ typedef enum {
     CCAL_ERR_NOT_PD = 4,          /* Cholesky of the normal equations failed: None */
     CCAL_ERR_NO_CONVERGENCE = 5,  /* informational: max_iterations reached (reference still returns Some) */
     CCAL_ERR_UNSUPPORTED = 6,
-    CCAL_ERR_NO_MEMORY = 7        /* host allocation failed inside the library (never thrown across the ABI) */
+    CCAL_ERR_NO_MEMORY = 7,       /* host allocation failed inside the library (never thrown across the ABI) */
+    CCAL_NO_RESULT = 8            /* the reference's `None` of an estimator that found nothing (homography_to_focal, an RANSAC
+                                     without one admissible hypothesis): not a failure of the call, the caller tries again */
 } ccal_status;
 
 typedef enum {                    /* camera-intrinsic-model GenericModel variants on the hot path */
@@ -367,6 +373,36 @@ int ccal_multi_solve(ccal_multi_problem* mp, const ccal_solver_opts* opts,
  * observation frame; n_used [n_obs] = corners that entered the estimate, 0 = no pose (the reference skips
  * frames with fewer than 10 valid unprojections: pass min_points = 10). */
 int ccal_init_poses(ccal_problem* p, const double* intr, int min_points, double* poses_obs, int32_t* n_used);
+
+/* ---- initialisation from detections alone (try_init_camera, src/util.rs:107-159) --------------
+ * radial_distortion_homography (src/optimization/homography.rs:218-271): RANSAC over a six-point minimal solver for a
+ * homography H with one-parameter division distortion lambda between two views of the board, n_hyp (reference: 1 000) random
+ * samples scored on ALL pairs (mean distance of evaluate_homography_lambda, :169-216), for n_prob independent problems in one
+ * launch.  Problem i holds the pairs [pair_offsets[i], pair_offsets[i + 1]) of `pairs` [.][4] = (x, y, x', y'), NORMALISED
+ * (p - (w/2, h/2)) / max(w/2, h/2) (:223-238); pair_offsets[0] == 0; fewer than 6 pairs in any problem: CCAL_ERR_INVALID_ARG,
+ * nothing is launched.  Hypothesis h of problem i samples 6 distinct pairs by a partial Fisher-Yates shuffle driven by the
+ * counter-based splitmix64 stream (seeds[i] + h * 0xD1B54A32D192ED03; outputs 1..6; draw k: j = k + z_k mod (n - k)) - the
+ * reference shuffles with an unseeded generator.  All arithmetic is f64 (the reference: f32).  The winner is the lowest score,
+ * ties to the lowest hypothesis index: the outputs are a pure function of (pairs, seed, n_hyp), and hypothesis h does not
+ * depend on n_hyp or on what else is in the batch.
+ * Per problem: lambda_out [n_prob], H_out [n_prob][9] row-major (scale as the solver leaves it), score_out [n_prob],
+ * best_idx_out [n_prob] (winning hypothesis), n_valid_out [n_prob] (hypotheses with an admissible root and a finite score).
+ * A problem without one: n_valid 0, best_idx -1, lambda 0, H 0, score +inf (the call still returns CCAL_OK).
+ * Optional per-hypothesis outputs (NULL: not wanted): hyp_sample [n_prob][n_hyp][6], hyp_lambda [n_prob][n_hyp],
+ * hyp_H [n_prob][n_hyp][9], hyp_score [n_prob][n_hyp] (+inf, lambda 0, H 0 where the solver returned none). */
+int ccal_rdh_batch(ccal_ctx* ctx, int n_prob, const int64_t* pair_offsets, const double* pairs, const uint64_t* seeds, int n_hyp,
+                   double* lambda_out, double* H_out, double* score_out, int32_t* best_idx_out, int32_t* n_valid_out,
+                   int32_t* hyp_sample, double* hyp_lambda, double* hyp_H, double* hyp_score);
+/* one problem; CCAL_NO_RESULT when no hypothesis was valid (outputs as above) */
+int ccal_radial_distortion_homography(ccal_ctx* ctx, const double* pairs, int n_pairs, uint64_t seed, int n_hyp,
+                                      double* lambda_out, double* H_out, double* score_out, int32_t* best_idx_out, int32_t* n_valid_out);
+/* homography_to_focal (src/optimization/homography.rs:274-325): focal length in units of the normalisation from H (row-major),
+ * CCAL_NO_RESULT (and *f = 0) where the reference returns None.  Host code, no context. */
+int ccal_homography_to_focal(const double* H, double* f);
+/* init_pose (src/optimization/linear.rs:5-21) for every observation frame of the problem: bearings
+ * ((p2d - c) / half) / (1 + lambda r^2) with c = (w/2, h/2), half = max(w/2, h/2) of the frame's camera, then the planar PnP of
+ * ccal_init_poses (the same kernel body; corners with 1 + lambda r^2 <= 0 are left out).  Outputs as ccal_init_poses. */
+int ccal_init_poses_division(ccal_problem* p, double lambda, int min_points, double* poses_obs, int32_t* n_used);
 
 /* ---- init_camera_extrinsic (src/util.rs:511-561) ------------------------------------------
  * T_i_0 of camera i from the board poses camera 0 and camera i estimated for the same n_common frames:
