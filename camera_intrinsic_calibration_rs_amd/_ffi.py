@@ -17,11 +17,13 @@ STATUS_NAMES = ["CCAL_OK", "CCAL_ERR_INVALID_ARG", "CCAL_ERR_HIP", "CCAL_ERR_NON
 METHOD_GN, METHOD_LM = 0, 1
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1, 2
 MULTI_MAX_DEVICES = 16
+PIX_U8, PIX_U16 = 0, 1                          # ccal_pixel_type
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
+_bp = C.POINTER(C.c_uint8)
 
 
 class ProblemDesc(C.Structure):
@@ -150,6 +152,16 @@ SYMBOLS = [
     ("ccal_multi_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp, _lp]),
     ("ccal_convert_model", C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int,
                                      C.POINTER(SolverOpts), C.POINTER(Report)]),
+    # applying a calibration: points, undistortion maps, remap
+    ("ccal_project_points", C.c_int, [_vp, C.c_int, _dp, C.c_int64, _dp, _dp, _bp]),
+    ("ccal_unproject_points", C.c_int, [_vp, C.c_int, _dp, C.c_int64, _dp, _dp, _bp]),
+    ("ccal_estimate_new_camera_matrix", C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _dp]),
+    ("ccal_undistort_map_create", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    ("ccal_undistort_map_from_host", C.c_int, [_vp, _fp, _fp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    ("ccal_undistort_map_download", C.c_int, [_vp, _fp, _fp]),
+    ("ccal_undistort_map_destroy", None, [_vp]),
+    ("ccal_remap", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    ("ccal_remap_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

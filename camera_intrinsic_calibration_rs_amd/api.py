@@ -17,6 +17,9 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   optimization::homography::radial_distortion_homography        radial_distortion_homography (+ rdh_sample_indices)
   optimization::homography::homography_to_focal                 homography_to_focal
   optimization::linear::init_pose   (linear.rs:5-21)            init_pose
+  GenericModel::project / unproject, estimate_new_camera_matrix_for_undistort, init_undistort_map
+                                    (examples/convert_model.rs:27-29)   GenericModel methods of the same names
+  remap                             (examples/test_pnp.rs:80)           remap (+ engine.UndistortMap for batches)
   (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
    not here yet - see README, "From detections alone")
 
@@ -38,7 +41,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from .engine import CcalError, Context, MultiContext, MultiProblem, Problem, default_opts, make_desc
+from .engine import (CcalError, Context, MultiContext, MultiProblem, Problem, UndistortMap, check_images, check_maps, default_opts,
+                     make_desc)
 from .synth import MODEL_NAMES, MODEL_NPARAMS, PMAX, rodrigues, rotmat_to_rvec, splitmix64
 
 _MODEL_KEYS = {
@@ -130,6 +134,58 @@ class GenericModel:
     def copy(self) -> "GenericModel":
         return GenericModel(self.kind, self._params, self._w, self._h)
 
+    # -- applying the model (the tail of examples/convert_model.rs and examples/test_pnp.rs) --------------------------------------
+    def _usable(self, what: str) -> None:
+        if self.kind in _CONTAINER_KINDS:
+            raise CcalError(_ffi.ERR_UNSUPPORTED, what, f"{self.kind} is a parameter container: its projection lives only in the absent crate")
+
+    def project(self, p3ds, ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """GenericModel::project: camera-frame points [n, 3] -> (uv [n, 2], valid [n]); rows where it is undefined are NaN."""
+        self._usable("project")
+        p3ds = np.asarray(p3ds, dtype=np.float64)
+        if p3ds.ndim != 2 or p3ds.shape[1] != 3:
+            raise ValueError("project: an [n, 3] array of points")
+        return _ctx(ctx).project_points(self.model_id, self._params, p3ds)
+
+    def unproject(self, p2ds, ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """GenericModel::unproject: pixels [n, 2] -> (rays [n, 3], valid [n]); a unit ray, NaN where there is none."""
+        self._usable("unproject")
+        p2ds = np.asarray(p2ds, dtype=np.float64)
+        if p2ds.ndim != 2 or p2ds.shape[1] != 2:
+            raise ValueError("unproject: an [n, 2] array of pixels")
+        return _ctx(ctx).unproject_points(self.model_id, self._params, p2ds)
+
+    def estimate_new_camera_matrix_for_undistort(self, balance: float, new_w_h: Optional[Tuple[int, int]] = None,
+                                                 ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+        """The pinhole matrix [3, 3] whose image holds the four edge midpoints' rays; balance 0 keeps every output pixel inside
+        the source image along the tighter axis, 1 keeps the whole source along the wider one.  None where an edge midpoint has
+        no ray in front of the camera."""
+        self._usable("estimate_new_camera_matrix_for_undistort")
+        if not (0.0 <= float(balance) <= 1.0):                      # also refuses NaN
+            raise ValueError("balance must lie in [0, 1]")
+        if new_w_h is not None and (len(new_w_h) != 2 or int(new_w_h[0]) <= 0 or int(new_w_h[1]) <= 0):
+            raise ValueError("new_w_h: a positive (width, height)")
+        return _ctx(ctx).estimate_new_camera_matrix(self.model_id, self._params, int(round(self._w)), int(round(self._h)),
+                                                    float(balance), new_w_h)
+
+    def init_undistort_map(self, projection_mat, new_w_h: Tuple[int, int], rotation=None,
+                           ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(xmap, ymap), f32 [h, w]: for every pixel of the new pinhole image `projection_mat` (3 x 3; `rotation` 3 x 3 from the
+        camera frame to the new one, None = identity) the source pixel it is sampled from, NaN where the model has none."""
+        self._usable("init_undistort_map")
+        K = np.asarray(projection_mat, dtype=np.float64)
+        if K.shape != (3, 3):
+            raise ValueError("projection_mat: a 3 x 3 matrix")
+        if rotation is not None and np.asarray(rotation).shape != (3, 3):
+            raise ValueError("rotation: a 3 x 3 matrix")
+        if len(new_w_h) != 2 or int(new_w_h[0]) <= 0 or int(new_w_h[1]) <= 0:
+            raise ValueError("new_w_h: a positive (width, height)")
+        m = _ctx(ctx).undistort_map(self.model_id, self._params, K, new_w_h, rotation)
+        try:
+            return m.download()
+        finally:
+            m.close()
+
     # cam{i}.json: {"EUCM": {"fx":..,"fy":..,"cx":..,"cy":..,"alpha":..,"beta":..,"width":..,"height":..}} (data/eucm.json)
     def to_json_obj(self) -> dict:
         if self.kind in _CONTAINER_KINDS:
@@ -196,6 +252,18 @@ def _ctx(ctx: Optional[Context]) -> Context:
     if _default_ctx is None:
         _default_ctx = Context(0)
     return _default_ctx
+
+
+def remap(img, xmap, ymap, ctx: Optional[Context] = None) -> np.ndarray:
+    """remap: one image [H][W] (uint8 / uint16) or [H][W][3] (uint8) resampled bilinearly through the maps -> the maps' shape, same
+    dtype; 0 where the map points outside the image or is NaN.  For many frames through one map keep an engine.UndistortMap."""
+    xmap, ymap = check_maps(xmap, ymap)
+    img, _, _ = check_images(img, False)
+    m = _ctx(ctx).undistort_map_from_arrays(xmap, ymap)
+    try:
+        return m.remap(img[None])[0]
+    finally:
+        m.close()
 
 
 class _Opened:

@@ -116,6 +116,13 @@ static void ctx_free(ccal_ctx* ctx) {
     if (ctx->own_stream && ctx->stream) { (void)hipSetDevice(ctx->device); (void)hipStreamDestroy(ctx->stream); }
     delete ctx;
 }
+}  // extern "C"
+namespace ccal {
+void ctx_unref(ccal_ctx* ctx) {
+    if (--ctx->n_problems == 0 && ctx->destroy_requested) ctx_free(ctx);
+}
+}  // namespace ccal
+extern "C" {
 void ccal_ctx_destroy(ccal_ctx* ctx) {
     if (!ctx) return;
     if (ctx->n_problems > 0) { ctx->destroy_requested = true; return; }     // freed by its last problem

@@ -163,6 +163,8 @@ inline void* pinned_device_ptr(const void* host, size_t bytes) {
 }  // namespace ccal
 namespace ccal {
 void ctx_worker_destroy(ccal_ctx* ctx);
+// ccal_api.hip: an object other than a problem that was counted in ctx->n_problems (an undistortion map) lets go of its context
+void ctx_unref(ccal_ctx* ctx);
 // the context's conventions as the kernels take them
 inline ModelRt model_rt(const ccal_ctx* ctx) {
     ModelRt rt = {};

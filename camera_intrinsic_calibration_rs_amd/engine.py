@@ -1,4 +1,4 @@
-"""Thin object wrappers over the C ABI (include/ccal.h): Context and Problem.
+"""Thin object wrappers over the C ABI (include/ccal.h): Context, Problem and UndistortMap.
 
 Nothing here computes; every method forwards to the HIP library through ctypes.
 """
@@ -127,11 +127,140 @@ class Context:
             out.update({k: v[:n] for k, v in hyp.items()})
         return out
 
+    # -- applying a calibration: points, the new camera matrix, undistortion maps (ccal_kernels_undistort.hip) ---------------
+    def _points(self, fn, where, model: int, params, pts, in_w: int, out_w: int):
+        pts = _f64(pts)
+        if pts.ndim != 2 or pts.shape[1] != in_w:
+            raise ValueError(f"{where}: an [n, {in_w}] array")
+        n = pts.shape[0]
+        params = _f64(params)
+        out = np.full((max(n, 1), out_w), np.nan)
+        valid = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = fn(self.handle, int(model), _dp(params), n, _dp(pts), _dp(out), valid.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        return out[:n], valid[:n].astype(bool)
+
+    def project_points(self, model: int, params, xyz):
+        """GenericModel::project over xyz [n, 3]: (uv [n, 2], valid [n]); invalid rows are NaN."""
+        return self._points(self.lib.ccal_project_points, "ccal_project_points", model, params, xyz, 3, 2)
+
+    def unproject_points(self, model: int, params, uv):
+        """GenericModel::unproject over uv [n, 2]: (rays [n, 3], valid [n]); invalid rows are NaN."""
+        return self._points(self.lib.ccal_unproject_points, "ccal_unproject_points", model, params, uv, 2, 3)
+
+    def estimate_new_camera_matrix(self, model: int, params, width: int, height: int, balance: float, new_w_h=None):
+        """estimate_new_camera_matrix_for_undistort: K [3, 3], or None where an edge midpoint has no ray (CCAL_NO_RESULT)."""
+        nw, nh = (0, 0) if new_w_h is None else (int(new_w_h[0]), int(new_w_h[1]))
+        K = np.full(9, np.nan)
+        rc = self.lib.ccal_estimate_new_camera_matrix(self.handle, int(model), _dp(_f64(params)), int(width), int(height),
+                                                      float(balance), nw, nh, _dp(K))
+        if rc == _ffi.NO_RESULT:
+            return None
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_estimate_new_camera_matrix", self.last_error())
+        return K.reshape(3, 3)
+
+    def undistort_map(self, model: int, params, K, new_w_h, rotation=None) -> "UndistortMap":
+        """init_undistort_map on the device: the maps of a new_w x new_h pinhole image K (3 x 3), optionally rotated."""
+        K = _f64(K, 9)
+        R = None if rotation is None else _f64(rotation, 9)
+        h = C.c_void_p()
+        rc = self.lib.ccal_undistort_map_create(self.handle, int(model), _dp(_f64(params)), _dp(K), _dp(R), int(new_w_h[0]),
+                                                int(new_w_h[1]), C.byref(h))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_undistort_map_create", self.last_error())
+        return UndistortMap(self, h, int(new_w_h[0]), int(new_w_h[1]))
+
+    def undistort_map_from_arrays(self, xmap, ymap) -> "UndistortMap":
+        """A device-resident map from caller-made f32 arrays [h, w]."""
+        xmap, ymap = check_maps(xmap, ymap)
+        fp = C.POINTER(C.c_float)
+        h = C.c_void_p()
+        rc = self.lib.ccal_undistort_map_from_host(self.handle, xmap.ctypes.data_as(fp), ymap.ctypes.data_as(fp), xmap.shape[1],
+                                                   xmap.shape[0], C.byref(h))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_undistort_map_from_host", self.last_error())
+        return UndistortMap(self, h, xmap.shape[1], xmap.shape[0])
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first
                 p.close()
             self.lib.ccal_ctx_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def check_maps(xmap, ymap):
+    """Two f32 arrays [h, w] of one shape (ValueError otherwise), C-contiguous."""
+    xmap, ymap = np.asarray(xmap), np.asarray(ymap)
+    if xmap.dtype != np.float32 or ymap.dtype != np.float32:
+        raise ValueError("maps: float32 arrays")
+    if xmap.ndim != 2 or xmap.shape != ymap.shape or xmap.size == 0:
+        raise ValueError("maps: two non-empty [h, w] arrays of the same shape")
+    return np.ascontiguousarray(xmap), np.ascontiguousarray(ymap)
+
+
+def check_images(images, batched: bool):
+    """uint8 [..][H][W], uint8 [..][H][W][3] or uint16 [..][H][W] (ValueError otherwise): (array, dtype code, channels)."""
+    images = np.asarray(images)
+    lead = 1 if batched else 0
+    if images.dtype not in (np.uint8, np.uint16):
+        raise ValueError("remap: uint8 or uint16 images")
+    if images.ndim not in (lead + 2, lead + 3) or images.size == 0:
+        raise ValueError("remap: images [n][H][W] or [n][H][W][3]" if batched else "remap: an image [H][W] or [H][W][3]")
+    channels = images.shape[lead + 2] if images.ndim == lead + 3 else 1
+    if (images.dtype == np.uint8 and channels not in (1, 3)) or (images.dtype == np.uint16 and channels != 1) or \
+            (images.ndim == lead + 3 and channels == 1):
+        raise ValueError("remap: one channel ([H][W]) of uint8 or uint16, or three interleaved channels of uint8")
+    return np.ascontiguousarray(images), (_ffi.PIX_U8 if images.dtype == np.uint8 else _ffi.PIX_U16), int(channels)
+
+
+class UndistortMap:
+    """A device-resident pair of undistortion maps (ccal_undistort_map): build once, remap every frame of a session."""
+
+    def __init__(self, ctx: Context, handle, w: int, h: int):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.handle = handle
+        self.w, self.h = int(w), int(h)
+        ctx._problems.add(self)               # closed before the context, like a problem
+
+    def download(self):
+        """(xmap, ymap), f32 [h, w]."""
+        xmap = np.empty((self.h, self.w), dtype=np.float32); ymap = np.empty((self.h, self.w), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        rc = self.lib.ccal_undistort_map_download(self.handle, xmap.ctypes.data_as(fp), ymap.ctypes.data_as(fp))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_undistort_map_download", self.ctx.last_error())
+        return xmap, ymap
+
+    def remap(self, images) -> np.ndarray:
+        """Bilinear resampling of a batch [n][H][W] (uint8 / uint16) or [n][H][W][3] (uint8) -> [n][h][w](, 3), same dtype."""
+        images, dtype, channels = check_images(images, True)
+        n, H, W = images.shape[:3]
+        out = np.empty((n, self.h, self.w) + images.shape[3:], dtype=images.dtype)
+        rc = self.lib.ccal_remap(self.handle, dtype, channels, W, H, n, C.c_void_p(images.ctypes.data), C.c_void_p(out.ctypes.data))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_remap", self.ctx.last_error())
+        return out
+
+    def remap_dev(self, src_ptr: int, dst_ptr: int, dtype: int, channels: int, src_w: int, src_h: int, n_img: int):
+        """Device pointers; only enqueues on the context's stream (Context.sync waits)."""
+        rc = self.lib.ccal_remap_dev(self.handle, int(dtype), int(channels), int(src_w), int(src_h), int(n_img),
+                                     C.c_void_p(src_ptr), C.c_void_p(dst_ptr))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_remap_dev", self.ctx.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.ccal_undistort_map_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -433,6 +433,48 @@ int ccal_convert_model(ccal_ctx* ctx, int src_model, const double* src_params, i
                        double* tgt_params_io, double width, double height, int disabled_distortions,
                        const ccal_solver_opts* opts, ccal_report* report);
 
+/* ---- applying a calibration: points, undistortion maps, remap ------------------------------------
+ * The tail of the reference's examples (examples/convert_model.rs:27-29, examples/test_pnp.rs:51,78-80): model.unproject,
+ * estimate_new_camera_matrix_for_undistort, init_undistort_map, remap.  `params` is a params() vector of `model` in the
+ * context's conventions (ocv5_order; the KB4 / unprojection small radii apply).  The EUCMT container: CCAL_ERR_UNSUPPORTED.
+ *
+ * ccal_project_points    GenericModel::project: xyz [n][3] -> uv_out [n][2], valid_out [n] (1 where project is defined: in front
+ *                        of the UCM / EUCM cone, a non-zero KB4 point, z > 1e-9 for OPENCV5); invalid rows are NaN, NaN.
+ * ccal_unproject_points  GenericModel::unproject: uv [n][2] -> rays_out [n][3] (a unit ray; (mx, my, 1) below KB4's small
+ *                        radius), valid_out [n]; invalid rows are NaN.  n == 0 is allowed in both.
+ * ccal_estimate_new_camera_matrix
+ *                        the pinhole K_out [9] (row-major [[f,0,cx],[0,f,cy],[0,0,1]]) whose new_w x new_h image (0, 0: width x
+ *                        height) holds the rays of the four edge midpoints (cx,0), (W-1,cy), (cx,H-1), (0,cy) of the model:
+ *                        with x/z, y/z of their unprojections, min_x = |min x/z|, max_x = max x/z (y alike),
+ *                        cx' = new_w min_x / (min_x + max_x), f = balance max(new_w / (min_x + max_x), new_h / (min_y + max_y))
+ *                        + (1 - balance) min(the same two).  balance outside [0, 1]: CCAL_ERR_INVALID_ARG.  A midpoint that
+ *                        cannot be unprojected or has z <= 0: CCAL_NO_RESULT.
+ * ccal_undistort_map_*   a device-resident pair of f32 maps [new_h][new_w]: for output pixel (x, y) the source pixel
+ *                        project(R^T ((x - cx) / fx, (y - cy) / fy, 1)) of K = [[fx,0,cx],[0,fy,cy],[0,0,1]] (row-major; R
+ *                        row-major, NULL = identity), NaN, NaN where project is undefined.  _from_host: any caller-made maps.
+ *                        A map holds its context like a problem does.  At most 2^31 - 1 pixels.
+ * ccal_remap / _dev      bilinear resampling of n_img interleaved images [n_img][src_h][src_w][channels] of one size through
+ *                        the map into [n_img][new_h][new_w][channels]; (dtype, channels) = (CCAL_PIX_U8, 1), (CCAL_PIX_U8, 3)
+ *                        or (CCAL_PIX_U16, 1).  A map entry (mx, my) is valid iff both are finite, 0 <= mx <= src_w - 1 and
+ *                        0 <= my <= src_h - 1 (-0.0 counts as 0); an invalid entry writes 0 in every channel.  Valid, in f32:
+ *                        x0 = floor(mx), ax = mx - x0, x1 = min(x0 + 1, src_w - 1), y alike,
+ *                        val = (1 - ay) ((1 - ax) p00 + ax p01) + ay ((1 - ax) p10 + ax p11), output floorf(val + 0.5f)
+ *                        clamped to the type's range.  ccal_remap: host pointers, returns when dst is written.
+ *                        ccal_remap_dev: device pointers, only enqueues on the context's stream (ccal_sync waits). */
+typedef struct ccal_undistort_map ccal_undistort_map;
+typedef enum { CCAL_PIX_U8 = 0, CCAL_PIX_U16 = 1 } ccal_pixel_type;
+int ccal_project_points(ccal_ctx* ctx, int model, const double* params, int64_t n, const double* xyz, double* uv_out, uint8_t* valid_out);
+int ccal_unproject_points(ccal_ctx* ctx, int model, const double* params, int64_t n, const double* uv, double* rays_out, uint8_t* valid_out);
+int ccal_estimate_new_camera_matrix(ccal_ctx* ctx, int model, const double* params, int width, int height, double balance,
+                                    int new_w, int new_h, double* K_out /* [9] */);
+int ccal_undistort_map_create(ccal_ctx* ctx, int model, const double* params, const double* K /* [9] */, const double* R /* [9] or NULL */,
+                              int new_w, int new_h, ccal_undistort_map** out);
+int ccal_undistort_map_from_host(ccal_ctx* ctx, const float* xmap, const float* ymap, int w, int h, ccal_undistort_map** out);
+int ccal_undistort_map_download(ccal_undistort_map* map, float* xmap_out, float* ymap_out);
+void ccal_undistort_map_destroy(ccal_undistort_map* map);
+int ccal_remap(ccal_undistort_map* map, int dtype, int channels, int src_w, int src_h, int n_img, const void* src, void* dst);
+int ccal_remap_dev(ccal_undistort_map* map, int dtype, int channels, int src_w, int src_h, int n_img, const void* src_dev, void* dst_dev);
+
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
                              double* err_out /* [n_corners] Euclidean px error */);
