@@ -320,7 +320,8 @@ def _intr_matrix(cameras: Sequence[GenericModel]) -> np.ndarray:
 def init_frame_poses(frame_feature_list: Sequence[Optional[FrameFeature]], generic_camera: GenericModel,
                      min_points: int = 10, ctx: Optional[Context] = None, devices: Optional[Sequence[int]] = None) -> Dict[int, RvecTvec]:
     """The pose initialisation inside calib_camera (src/util.rs:418-436): `unproject` the detections with
-    the current model, keep the valid ones, normalise by z, planar PnP -- one wavefront per frame."""
+    the current model, keep the valid ones, normalise by z, PnP -- one wavefront per frame (the planar homography for frames at
+    z = 0, the general PnP of ccal_pnp_batch for any other target)."""
     valid = [i for i, f in enumerate(frame_feature_list) if f is not None]
     if not valid:
         return {}
@@ -733,6 +734,16 @@ def homography_to_focal(h_mat) -> Optional[float]:
     if rc != _ffi.OK:
         raise CcalError(rc, "ccal_homography_to_focal")
     return float(f.value)
+
+
+def solve_pnp(p3ds, p2ds_z, ctx: Optional[Context] = None
+              ) -> Optional[Tuple[Tuple[float, float, float], Tuple[float, float, float]]]:
+    """sqpnp_simple::sqpnp_solve_glam(&p3ds, &p2ds_z) as the reference calls it (src/util.rs:431, examples/test_pnp.rs:61): 3-D points
+    [n, 3] - any point set - and their normalised image points [n, 2] -> (rvec, tvec), None without a pose."""
+    poses, used, _ = _ctx(ctx).pnp_batch([p3ds], [p2ds_z], 4, with_cost=False)
+    if used[0] == 0:
+        return None
+    return tuple(float(v) for v in poses[0, :3]), tuple(float(v) for v in poses[0, 3:])
 
 
 def init_pose(frame_feature: FrameFeature, lam: float, ctx: Optional[Context] = None

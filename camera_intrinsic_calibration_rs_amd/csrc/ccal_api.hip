@@ -234,6 +234,11 @@ int ccal_problem_create(ccal_ctx* ctx, const ccal_problem_desc* d, ccal_problem*
     if (p->n_corners >= ((int64_t)1 << 30)) return fail(ctx, CCAL_ERR_INVALID_ARG, "more than 2^30 - 1 corners in one problem: shard the frames (ccal_multi_problem_create)");
     const size_t nc = (size_t)p->n_corners;
     if (nc && (!d->p3d_x || !d->p3d_y || !d->p3d_z || !d->p2d_u || !d->p2d_v)) return fail(ctx, CCAL_ERR_INVALID_ARG, "null corner arrays");
+    {   // any z other than +-0 (pose initialisation: which kernels)
+        uint32_t any = 0;
+        for (size_t i = 0; i < nc; ++i) { uint32_t b; std::memcpy(&b, d->p3d_z + i, sizeof b); any |= b & 0x7fffffffu; }
+        p->has_nonplanar = any != 0;
+    }
     // ONE device allocation, cleared once, sliced (a calibration session creates its problem once: sixteen hipMalloc + memset pairs
     // were a third of ccal_problem_create's 0.25 ms at 600 frames).  One element of slack behind every uploaded array, as upload().
     const size_t ni = (size_t)d->n_cams * CCAL_PMAX, np6 = (size_t)std::max(d->n_slots, 1) * 6, ne = (size_t)d->n_cams * 6;

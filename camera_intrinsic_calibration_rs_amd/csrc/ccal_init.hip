@@ -1,6 +1,7 @@
 // C ABI of the from-detections initialisation (include/ccal.h): the batched RANSAC of radial_distortion_homography
 // (src/optimization/homography.rs:218-271; kernels in ccal_kernels_rdh.hip), homography_to_focal (:274-325, host code) and
-// the division-model pose initialisation init_pose (src/optimization/linear.rs:5-21; k_pose_init's division variant).
+// the division-model pose initialisation init_pose (src/optimization/linear.rs:5-21; k_pose_init's division variant), and the
+// batched general PnP (sqpnp_solve_glam for many problems in one launch; k_pose_pnp, ccal_kernels_pnp.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -149,6 +150,49 @@ int ccal_init_poses_division(ccal_problem* p, double lambda, int min_points, dou
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, "ccal_init_poses_division", e);
+    return CCAL_OK;
+    CCAL_API_CATCH(ctx)
+}
+
+int ccal_pnp_batch(ccal_ctx* ctx, int n_prob, const int64_t* offsets, const double* xyz, const double* xn, int min_points,
+                   double* poses_out, int32_t* n_used_out, double* cost_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    if (n_prob < 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: n_prob < 0");
+    if (n_prob == 0) return CCAL_OK;
+    if (!offsets || !poses_out || !n_used_out) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: NULL argument");
+    if (offsets[0] != 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: offsets[0] != 0");
+    for (int i = 0; i < n_prob; ++i) {
+        const int64_t n = offsets[i + 1] - offsets[i];
+        if (n < 0 || n > (1 << 24)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: offsets must not decrease, at most 2^24 points in a problem");
+    }
+    const size_t n_tot = (size_t)offsets[n_prob], np = (size_t)n_prob;
+    if (n_tot && (!xyz || !xn)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: NULL argument");
+    CCAL_API_TRY
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
+    // one block: offsets | points | image points | poses, costs | counts
+    const size_t b_off = up256((np + 1) * 8), b_xyz = up256((n_tot + 1) * 24), b_xn = up256((n_tot + 1) * 16), b_res = up256(np * 7 * 8), b_nu = up256(np * 4);
+    char* d = nullptr;
+    e = ctx_dev_alloc(ctx, (void**)&d, b_off + b_xyz + b_xn + b_res + b_nu);
+    if (e != hipSuccess) return hip_fail(ctx, "ccal_pnp_batch: allocation", e);
+    struct Guard { ccal_ctx* c; char* p; ~Guard() { (void)hipStreamSynchronize(c->stream); ctx_release(c, p, false); } } guard{ ctx, d };
+    int64_t* d_off = (int64_t*)d;
+    double* d_xyz = (double*)(d + b_off);
+    double* d_xn = (double*)(d + b_off + b_xyz);
+    double* d_po = (double*)(d + b_off + b_xyz + b_xn);
+    double* d_cost = d_po + np * 6;
+    int32_t* d_nu = (int32_t*)(d + b_off + b_xyz + b_xn + b_res);
+    hipStream_t s = ctx->stream;
+    e = test_poison_f64(ctx, d_po, b_res, false, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, (np + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_xyz, xyz, n_tot * 24, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_xn, xn, n_tot * 16, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_pnp_batch(n_prob, d_off, d_xyz, d_xn, min_points, d_po, d_nu, d_cost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(poses_out, d_po, np * 6 * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(n_used_out, d_nu, np * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && cost_out) e = hipMemcpyAsync(cost_out, d_cost, np * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(ctx, "ccal_pnp_batch", e);
     return CCAL_OK;
     CCAL_API_CATCH(ctx)
 }

@@ -202,6 +202,7 @@ struct ccal_problem {
     std::vector<int64_t> h_obs_off, h_joff;
     std::vector<int32_t> h_obs_cam, h_obs_slot;
     bool slot_ident = false;       // h_obs_slot[o] == o for every observation frame
+    bool has_nonplanar = false;    // some corner has z != 0: pose initialisation also launches the general PnP (ccal_kernels_pnp.hip)
     // single camera, ragged frames: the bins of the Gram launch and the sorted table int4 { frame, first corner, corners, slot } per
     // position (a slice of d_block); gram_bins.n_bins == 0: none
     ccal::GramBins gram_bins;
@@ -269,6 +270,14 @@ hipError_t launch_pose_init(const ccal_problem* p, int cam, const double* d_intr
                             int min_points, hipStream_t s);
 hipError_t launch_pose_init_division(const ccal_problem* p, int cam, double lambda, double* d_poses_obs, int32_t* d_valid,
                                      int min_points, hipStream_t s);
+// ccal_kernels_pnp.hip: the general PnP for the frames with a corner off the z = 0 plane (the others are passed over), and for
+// n_prob problems given as points + normalised image points (ccal_pnp_batch; d_cost may be nullptr)
+hipError_t launch_pose_pnp(const ccal_problem* p, int cam, const double* d_intr, double* d_poses_obs, int32_t* d_valid,
+                           int min_points, hipStream_t s);
+hipError_t launch_pose_pnp_division(const ccal_problem* p, int cam, double lambda, double* d_poses_obs, int32_t* d_valid,
+                                    int min_points, hipStream_t s);
+hipError_t launch_pnp_batch(int n_prob, const int64_t* d_off, const double* d_xyz, const double* d_xn, int min_points,
+                            double* d_poses, int32_t* d_n_used, double* d_cost, hipStream_t s);
 // Dynamic LDS above 48 KiB has to be enabled per kernel AND per device: remember the largest size enabled on each
 // device of this process (contexts on several GPUs may share the process).  Launchers run on any host thread
 // (ccal_solve_batch / ccal_solve_sharded drive one thread per context): the fast path is one atomic load, the

@@ -6,81 +6,9 @@
 //   least squares for H = [h11 h12 h13; h21 h22 h23; h31 h32 1]   (8 x 8 normal equations per frame)
 //   H ~ [r1 r2 t]  ->  scale, Gram-Schmidt, r3 = r1 x r2, quaternion -> rvec.
 // One wavefront per observation frame; lanes own corners, 44 lane-private sums, one shuffle reduction.
-#include "ccal_device.hpp"
-#include "ccal_internal.hpp"
+#include "ccal_pose_init.hpp"
 
 namespace ccal {
-
-// Not a camera model of the engine: the one-parameter division model of the two-frame initialisation (init_pose,
-// src/optimization/linear.rs:5-21) as an unprojection variant of k_pose_init.  th = [half, half, w/2, h/2, lambda]:
-// bearing = ((p2d - c) / half) / (1 + lambda r^2).
-constexpr int kUnprojDivision = 100;
-
-// unproject + divide by z: the model inverse as published (UCM/EUCM closed form, Usenko et al. 2018;
-// KB4 Newton on theta; OPENCV5 fixed-point undistortion).  Returns false where the reference's
-// `unproject` yields None (outside the model's domain) or the ray is not in front of the camera.
-template <int MODEL>
-__device__ __forceinline__ bool unproject_normalized(const double* th, double small_radius, double u, double v, double& xn, double& yn) {
-    const double mx = (u - th[2]) / th[0], my = (v - th[3]) / th[1];
-    const double r2 = mx * mx + my * my;
-    if constexpr (MODEL == kUnprojDivision) {
-        const double sc = 1.0 + th[4] * r2;
-        if (!(sc > 1e-9)) return false;                         // beyond the division model's domain: no ray
-        xn = mx / sc; yn = my / sc;
-        return true;
-    } else if constexpr (MODEL == kUCM || MODEL == kEUCM) {
-        const double alpha = th[4], beta = (MODEL == kEUCM) ? th[5] : 1.0;
-        if (alpha > 0.5 && r2 > 1.0 / (beta * (2.0 * alpha - 1.0))) return false;
-        const double t1 = 1.0 - (2.0 * alpha - 1.0) * beta * r2;
-        if (t1 < 0.0) return false;
-        const double k = (1.0 - alpha * alpha * beta * r2) / (alpha * sqrt(t1) + (1.0 - alpha));
-        if (!(k > 1e-3)) return false;
-        xn = mx / k; yn = my / k;
-        return true;
-    } else if constexpr (MODEL == kKB4) {
-        const double r = sqrt(r2);
-        if (r < small_radius) { xn = mx; yn = my; return true; }
-        double t = r;
-        for (int it = 0; it < 10; ++it) {
-            const double t2 = t * t;
-            const double f = t * (1.0 + t2 * (th[4] + t2 * (th[5] + t2 * (th[6] + t2 * th[7])))) - r;
-            const double fp = 1.0 + t2 * (3.0 * th[4] + t2 * (5.0 * th[5] + t2 * (7.0 * th[6] + t2 * 9.0 * th[7])));
-            t -= f / fp;
-        }
-        if (!(t > 0.0) || !(t < 1.5)) return false;             // theta < ~86 deg: in front of the camera
-        const double s = tan(t) / r;
-        xn = mx * s; yn = my * s;
-        return true;
-    } else {
-        const double k1 = th[OCV5_K1], k2 = th[OCV5_K2], p1 = th[OCV5_P1], p2 = th[OCV5_P2], k3 = th[OCV5_K3];
-        double x = mx, y = my;
-        for (int it = 0; it < 25; ++it) {
-            const double q = x * x + y * y;
-            const double rad = 1.0 + q * (k1 + q * (k2 + q * k3));
-            const double dx = 2.0 * p1 * x * y + p2 * (q + 2.0 * x * x);
-            const double dy = p1 * (q + 2.0 * y * y) + 2.0 * p2 * x * y;
-            x = (mx - dx) / rad; y = (my - dy) / rad;
-        }
-        // accept only if re-projection reproduces the input
-        const double q = x * x + y * y, rad = 1.0 + q * (k1 + q * (k2 + q * k3));
-        const double ex = x * rad + 2.0 * p1 * x * y + p2 * (q + 2.0 * x * x) - mx;
-        const double ey = y * rad + p1 * (q + 2.0 * y * y) + 2.0 * p2 * x * y - my;
-        if (!(fabs(ex) + fabs(ey) < 1e-9)) return false;
-        xn = x; yn = y;
-        return true;
-    }
-}
-
-struct InitArgs {
-    const float* x; const float* y; const float* z; const float* u; const float* v;
-    const int64_t* obs_off; const int32_t* list; int32_t n_list, cam;
-    const double* intr;
-    double* poses_obs;      // [n_obs][6]  T_cam_board
-    int32_t* valid_obs;     // [n_obs]     number of corners used, 0 = no pose
-    int32_t min_points;
-    ModelRt rt;             // the context's run-time conventions
-    double division[5];     // kUnprojDivision only: th as above
-};
 
 template <int MODEL>
 __global__ __launch_bounds__(256) void k_pose_init(const InitArgs a) {
@@ -195,23 +123,19 @@ __global__ __launch_bounds__(256) void k_pose_init(const InitArgs a) {
     a.valid_obs[o] = ok ? cnt : 0;
 }
 
-static InitArgs pose_init_args(const ccal_problem* p, int cam) {
-    InitArgs a = {};
-    a.x = p->d_x; a.y = p->d_y; a.z = p->d_z; a.u = p->d_u; a.v = p->d_v;
-    a.obs_off = p->d_obs_off; a.list = p->cams[cam].d_obs; a.n_list = (int32_t)p->cams[cam].obs.size(); a.cam = cam;
-    return a;
-}
+// Frames with a corner off the z = 0 plane - k_pose_init leaves them without a pose - go to the general PnP (ccal_kernels_pnp.hip),
+// which passes over every other frame; a problem without such a corner (has_nonplanar, set at creation) launches k_pose_init alone.
 
-// init_pose of the two-frame initialisation: centre and scale from the camera's image size, as linear.rs:6-9
 hipError_t launch_pose_init_division(const ccal_problem* p, int cam, double lambda, double* d_poses_obs, int32_t* d_valid, int min_points, hipStream_t s) {
     InitArgs a = pose_init_args(p, cam);
-    const double hw = 0.5 * p->cams[cam].width, hh = 0.5 * p->cams[cam].height, half = hw > hh ? hw : hh;
-    a.division[0] = half; a.division[1] = half; a.division[2] = hw; a.division[3] = hh; a.division[4] = lambda;
+    division_theta(p, cam, lambda, a.division);
     a.poses_obs = d_poses_obs; a.valid_obs = d_valid; a.min_points = min_points; a.rt = model_rt(p->ctx);
     const int blocks = (a.n_list + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_pose_init<kUnprojDivision>, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !p->has_nonplanar) return e;
+    return launch_pose_pnp_division(p, cam, lambda, d_poses_obs, d_valid, min_points, s);
 }
 
 hipError_t launch_pose_init(const ccal_problem* p, int cam, const double* d_intr, double* d_poses_obs, int32_t* d_valid, int min_points, hipStream_t s) {
@@ -226,7 +150,9 @@ hipError_t launch_pose_init(const ccal_problem* p, int cam, const double* d_intr
         case kOCV5: hipLaunchKernelGGL(k_pose_init<kOCV5>, dim3(blocks), dim3(256), 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !p->has_nonplanar) return e;
+    return launch_pose_pnp(p, cam, d_intr, d_poses_obs, d_valid, min_points, s);
 }
 
 }  // namespace ccal

@@ -127,6 +127,31 @@ class Context:
             out.update({k: v[:n] for k, v in hyp.items()})
         return out
 
+    # -- general PnP, batched (ccal_pnp_batch, ccal_kernels_pnp.hip) ------------------------------------------------------------
+    def pnp_batch(self, xyz_list, xn_list, min_points: int = 4, with_cost: bool = True):
+        """n independent PnP problems in one launch.  xyz_list: arrays [n_i, 3] of 3-D points (any point set); xn_list: arrays
+        [n_i, 2] of their normalised image points.  Returns (poses [n, 6] rvec,tvec, n_used [n] int32 - 0: no pose, six zeros -,
+        cost [n] = E at the result, or None without with_cost)."""
+        n = len(xyz_list)
+        if len(xn_list) != n:
+            raise ValueError("pnp_batch: one array of image points per array of points")
+        X = [_f64(a).reshape(-1, 3) for a in xyz_list]
+        U = [_f64(a).reshape(-1, 2) for a in xn_list]
+        if any(len(a) != len(b) for a, b in zip(X, U)):
+            raise ValueError("pnp_batch: a problem's points and image points differ in number")
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(a) for a in X], out=offs[1:])
+        allx = np.ascontiguousarray(np.concatenate(X)) if n else np.zeros((0, 3))
+        allu = np.ascontiguousarray(np.concatenate(U)) if n else np.zeros((0, 2))
+        m = max(n, 1)
+        poses = np.full((m, 6), np.nan); used = np.full(m, -2, dtype=np.int32)
+        cost = np.full(m, np.nan) if with_cost else None
+        rc = self.lib.ccal_pnp_batch(self.handle, n, offs.ctypes.data_as(C.POINTER(C.c_int64)), _dp(allx), _dp(allu), int(min_points),
+                                     _dp(poses), used.ctypes.data_as(C.POINTER(C.c_int32)), _dp(cost))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_pnp_batch", self.last_error())
+        return poses[:n], used[:n], (cost[:n] if with_cost else None)
+
     # -- applying a calibration: points, the new camera matrix, undistortion maps (ccal_kernels_undistort.hip) ---------------
     def _points(self, fn, where, model: int, params, pts, in_w: int, out_w: int):
         pts = _f64(pts)

@@ -11,6 +11,8 @@ This module is data generation only (numpy); it is not an implementation of the 
 from __future__ import annotations
 
 import dataclasses
+from typing import Optional
+
 import numpy as np
 
 MODEL_UCM, MODEL_EUCM, MODEL_KB4, MODEL_OPENCV5 = 0, 1, 2, 3
@@ -74,6 +76,32 @@ def aprilgrid_board(tag_size: float, tag_spacing: float, rows: int, cols: int) -
             sy = -np.float32(r) * pitch
             pts += [(sx, sy, 0.0), (sx + ts, sy, 0.0), (sx + ts, sy - ts, 0.0), (sx, sy - ts, 0.0)]
     return np.asarray(pts, dtype=np.float32)
+
+
+def hinged_boards() -> np.ndarray:
+    """Two default 6x6 grids meeting at 90 degrees along an edge, an open book facing the camera: [288, 3] float32.  With w the
+    grid's width, the spine is the line x = 0.33 (the default board's centre line), z = -w / sqrt 2; the first grid runs from
+    x = 0.33 - w / sqrt 2 at z = 0 down to the spine, the second from the spine up to x = 0.33 + w / sqrt 2 at z = 0."""
+    g = default_board().astype(np.float64)
+    w = g[:, 0].max()
+    h = np.sqrt(0.5)
+    x0 = 0.33 - w * h                                             # the spine above the default board's centre line
+    a = np.stack([x0 + g[:, 0] * h, g[:, 1], -g[:, 0] * h], axis=1)
+    b = np.stack([x0 + (w + g[:, 0]) * h, g[:, 1], -(w - g[:, 0]) * h], axis=1)
+    return np.concatenate([a, b]).astype(np.float32)
+
+
+def offset_board() -> np.ndarray:
+    """The default board rotated 0.3 rad about x and lifted to z = 0.25: coplanar, but no z is zero.  [144, 3] float32."""
+    g = default_board().astype(np.float64)
+    c, s = np.cos(0.3), np.sin(0.3)
+    return np.stack([g[:, 0], c * g[:, 1] - s * g[:, 2], s * g[:, 1] + c * g[:, 2] + 0.25], axis=1).astype(np.float32)
+
+
+def cube_points(n: int, seed: int = 0xC0BE) -> np.ndarray:
+    """n seeded points in a 0.5 m cube behind the default board's centre (x 0.08..0.58, y -0.58..-0.08, z -0.5..0): [n, 3] float32."""
+    u = uniform01(seed, 3 * n, stream=13).reshape(n, 3)
+    return (np.array([0.08, -0.58, -0.5]) + 0.5 * u).astype(np.float32)
 
 
 # ----------------------------------------------------------------------------- geometry (numpy, f64)
@@ -223,12 +251,14 @@ def _gen_poses(seed: int, n: int, dist_range, lateral: float):
 def make_problem(n_frames: int, model: str | int = "eucm", n_cams: int = 1, seed: int = 0xC0FFEE,
                  noise_px: float = 0.1, ragged: bool = False, xy_same_focal: bool = False,
                  outlier_frac: float = 0.0, huber_delta: float = 1.0, init_perturb: float = 0.05,
-                 shuffle_corners: bool = False) -> SynthProblem:
+                 shuffle_corners: bool = False, board: Optional[np.ndarray] = None) -> SynthProblem:
     """Synthetic single- or multi-camera problem, `n_frames` frame slots x 144 corners (or 24..144
-    when `ragged`).  Camera c>0 sits at T_c0 = rvec (0.01,-0.02,0.005)*c, tvec (-0.101,0.002,0.001)*c."""
+    when `ragged`).  Camera c>0 sits at T_c0 = rvec (0.01,-0.02,0.005)*c, tvec (-0.101,0.002,0.001)*c.
+    `board`: the target's points [nb, 3] float32 (hinged_boards(), offset_board(), cube_points(n), ...) in place of
+    default_board(); every count above then reads nb for 144."""
     m = MODEL_NAMES[model] if isinstance(model, str) else int(model)
     P = MODEL_NPARAMS[m]
-    board = default_board()
+    board = default_board() if board is None else np.ascontiguousarray(board, dtype=np.float32).reshape(-1, 3)
     nb = board.shape[0]
     W, H = GT_SIZE
     gt = np.asarray(GT_PARAMS[m], dtype=np.float64)

@@ -30,6 +30,7 @@
  *   ccal_rdh_batch / ccal_radial_distortion_homography
  *                            radial_distortion_homography                 src/optimization/homography.rs:218-271
  *   ccal_homography_to_focal homography_to_focal                          src/optimization/homography.rs:274-325
+ *   ccal_pnp_batch           sqpnp_solve_glam (any 3-D point set), batched  src/util.rs:431
  *   ccal_init_poses_division init_pose                                    src/optimization/linear.rs:5-21
  *
  * Parameter layout.
@@ -371,8 +372,42 @@ int ccal_multi_solve(ccal_multi_problem* mp, const ccal_solver_opts* opts,
  * keep the valid ones, divide by z, planar PnP (the reference calls sqpnp_simple; here a plane-induced
  * homography -- same basin, the joint solve refines it).  poses_obs [n_obs][6] = T_cam_board of every
  * observation frame; n_used [n_obs] = corners that entered the estimate, 0 = no pose (the reference skips
- * frames with fewer than 10 valid unprojections: pass min_points = 10). */
+ * frames with fewer than 10 valid unprojections: pass min_points = 10).
+ *
+ * The homography serves frames whose corners all have z == 0 (z = -0 counts).  A frame with any z != 0 - a board whose coordinates
+ * are not at z = 0, boards hinged at an angle, any 3-D target - takes a general PnP instead (ccal_pnp_batch below: the same
+ * estimator, the same rules for "no pose"); one call may mix both kinds of frame, for any camera of a rig.  The same holds for
+ * ccal_init_poses_division and ccal_multi_init_poses. */
 int ccal_init_poses(ccal_problem* p, const double* intr, int min_points, double* poses_obs, int32_t* n_used);
+
+/* ---- general PnP, batched (sqpnp_simple::sqpnp_solve_glam: src/util.rs:431, src/optimization/linear.rs:19, examples/test_pnp.rs:61)
+ * n_prob independent problems in one launch, one wavefront each.  Problem i holds the points [offsets[i], offsets[i + 1]) of
+ * xyz [.][3] (any 3-D point set, planar ones included) and xn [.][2], their NORMALISED image points (x / z, y / z of the unprojected
+ * detections); offsets[0] == 0; points with a coordinate that is not finite are left out.  The estimator minimises the cost SQPnP is
+ * built on: with Q_i = [1 0 -x_i; 0 1 -y_i],
+ *     E(R, t) = sum_i | Q_i (R X_i + t) |^2
+ * is quadratic in t, so t*(R) = P vec(R) and E(R) = vec(R)^T Omega vec(R) with a 9 x 9 Omega from per-point sums (the X_i centred on
+ * their centroid).  E(R) is minimised over SO(3) from 64 fixed, well-spread starting rotations, 24 damped Gauss-Newton steps and 2
+ * undamped ones each;
+ * the result is the candidate of lowest E among those with the points in front of the camera, sum_i (R X_i + t)_z > 0 (the mirror
+ * twin of a coplanar target has the same E and negative depth: it loses), ties to the lowest start index.  The outputs are a pure
+ * function of a problem's points: they do not depend on what else is in the batch.
+ * poses_out [n_prob][6] = rvec (from the quaternion with qw >= 0), tvec = t*(R); n_used_out [n_prob] = points that entered, 0 = no
+ * pose; cost_out [n_prob] (or NULL) = E at the result.  A problem gets NO pose - six zeros, n_used 0, cost 0 - when
+ *   - fewer than max(min_points, 4) points are valid,
+ *   - sum_i Q_i^T Q_i is singular (n sum(x^2 + y^2) - (sum x)^2 - (sum y)^2 <= 1e-12 n sum(x^2 + y^2): one image point),
+ *   - the points are collinear: the second eigenvalue of the centred scatter sum (X_i - c)(X_i - c)^T is <= 1e-6 x the largest,
+ *   - no candidate is in front of the camera: none of the 64 has sum_i (R X_i + t)_z > 0, or the points lie BEHIND the camera -
+ *     the lowest E among the candidates at negative depth is below 0.5 x the lowest in front - 5e-5 trace(Omega).  (Points behind
+ *     the camera put the global minimum of E at negative depth and leave only poor local minima in front.  trace(Omega) / 3 is the
+ *     mean of E over all rotations; the term keeps the rule away from frames whose pose in front fits to noise or rounding level,
+ *     where a coplanar target's mirror twin may come out lower by chance.)  Or
+ *   - the result is not finite.
+ * The call returns CCAL_OK in all these cases.  n_prob == 0 is allowed (nothing is read or written).  offsets[0] != 0, decreasing
+ * offsets, more than 2^24 points in a problem or a NULL required pointer: CCAL_ERR_INVALID_ARG, nothing is launched. */
+int ccal_pnp_batch(ccal_ctx* ctx, int n_prob, const int64_t* offsets /* [n_prob + 1] */, const double* xyz /* [.][3] */,
+                   const double* xn /* [.][2] */, int min_points, double* poses_out /* [n_prob][6] */, int32_t* n_used_out,
+                   double* cost_out /* [n_prob] or NULL */);
 
 /* ---- initialisation from detections alone (try_init_camera, src/util.rs:107-159) --------------
  * radial_distortion_homography (src/optimization/homography.rs:218-271): RANSAC over a six-point minimal solver for a
