@@ -589,6 +589,48 @@ def validation(cam_idx: int, final_result: GenericModel, rtvec_list: Dict[int, R
         return prob.validation(0, _intr_matrix([final_result]), poses, None)
 
 
+_REFINE_MIN_POINTS = 4
+
+
+def refine_poses(frame_feature_list: Sequence[Optional[FrameFeature]], model: GenericModel,
+                 rtvec_map: Optional[Dict[int, RvecTvec]] = None, huber_delta: float = 1.0,
+                 ctx: Optional[Context] = None) -> Dict[int, RvecTvec]:
+    """The board pose of every frame under the FIXED model `model`: the minimiser of the Huber cost of the pixel reprojection
+    error (the ReprojectionFactor of the joint solve over rvec | tvec alone), one wavefront per frame, all frames in one launch
+    (ccal_refine_poses_batch).  Starts from rtvec_map where one is given, otherwise from init_frame_poses.  Frames that are None,
+    have fewer than 4 points, no starting pose or no result are absent from the returned map, as in calib_camera."""
+    model._usable("refine_poses")
+    cand = [i for i, f in enumerate(frame_feature_list) if f is not None and len(f.features) >= _REFINE_MIN_POINTS]
+    if rtvec_map is not None:
+        cand = [i for i in cand if i in rtvec_map]
+    if not cand:
+        return {}
+    if rtvec_map is None:
+        only = [f if i in set(cand) else None for i, f in enumerate(frame_feature_list)]
+        rtvec_map = init_frame_poses(only, model, ctx=ctx)
+        cand = [i for i in cand if i in rtvec_map]
+        if not cand:
+            return {}
+    X, U = [], []
+    for i in cand:
+        ff = frame_feature_list[i]
+        ids = sorted(ff.features.keys())
+        # the reference holds detections and board points in f32 (src/detected_points.rs:6-9)
+        X.append(np.asarray([ff.features[k].p3d for k in ids], dtype=np.float32).astype(np.float64))
+        U.append(np.asarray([ff.features[k].p2d for k in ids], dtype=np.float32).astype(np.float64))
+    poses0 = np.stack([rtvec_map[i].as6() for i in cand])
+    poses, status, _, _, _, _ = _ctx(ctx).refine_poses_batch(model.model_id, model._params, X, U, poses0, huber_delta,
+                                                             _REFINE_MIN_POINTS)
+    return {fi: RvecTvec.from6(poses[k]) for k, fi in enumerate(cand) if status[k] in (_ffi.OK, _ffi.ERR_NO_CONVERGENCE)}
+
+
+def validation_holdout(cam_idx: int, model: GenericModel, frame_feature_list: Sequence[Optional[FrameFeature]],
+                       ctx: Optional[Context] = None) -> Tuple[float, float]:
+    """util::validation (src/util.rs:721-795) on frames the fit did not see: their poses are fitted with the model fixed
+    (refine_poses), then the same statistics - (avg of the lowest 99 %, median) reprojection error in px."""
+    return validation(cam_idx, model, refine_poses(frame_feature_list, model, ctx=ctx), frame_feature_list, ctx=ctx)
+
+
 class ReprojectionFactor:
     """optimization::factors::ReprojectionFactor (src/optimization/factors.rs:126-173).
     residual_func(params) with params = [intrinsics (P_eff), rvec, tvec] evaluates the block on the GPU;

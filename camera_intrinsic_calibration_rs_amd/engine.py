@@ -152,6 +152,46 @@ class Context:
             raise CcalError(rc, "ccal_pnp_batch", self.last_error())
         return poses[:n], used[:n], (cost[:n] if with_cost else None)
 
+    # -- pose refinement under fixed intrinsics, batched (ccal_refine_poses_batch, ccal_kernels_refine.hip) -----------------------
+    def refine_poses_batch(self, model: int, params, xyz_list, uv_list, poses0, huber_delta: float = 1.0, min_points: int = 4,
+                           opts: "_ffi.SolverOpts | None" = None, with_errors: bool = False):
+        """n independent frames in one launch: the pose of each that minimises the Huber cost of the pixel reprojection error
+        through the model `model` with the params() vector `params`, which stays fixed.  xyz_list: arrays [n_i, 3] of board
+        points; uv_list: arrays [n_i, 2] of detections in pixels; poses0 [n, 6]: the starting rvec, tvec.  Returns (poses [n, 6],
+        status [n] int32 - _ffi.OK, ERR_NO_CONVERGENCE, ERR_NONFINITE, NO_RESULT: pose as given -, iterations [n], n_used [n],
+        cost0 [n], cost [n]) and, with_errors, a list of per-frame arrays of pixel errors at the result (NaN: point left out)."""
+        n = len(xyz_list)
+        if len(uv_list) != n:
+            raise ValueError("refine_poses_batch: one array of detections per array of points")
+        X = [_f64(a).reshape(-1, 3) for a in xyz_list]
+        U = [_f64(a).reshape(-1, 2) for a in uv_list]
+        if any(len(a) != len(b) for a, b in zip(X, U)):
+            raise ValueError("refine_poses_batch: a frame's points and detections differ in number")
+        m = max(n, 1)
+        poses = np.full((m, 6), np.nan)
+        poses[:n] = _f64(poses0).reshape(n, 6)
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(a) for a in X], out=offs[1:])
+        allx = np.ascontiguousarray(np.concatenate(X)) if n else np.zeros((0, 3))
+        allu = np.ascontiguousarray(np.concatenate(U)) if n else np.zeros((0, 2))
+        par = np.zeros(PMAX)
+        p = _f64(params).ravel()
+        par[:len(p)] = p
+        status = np.full(m, -2, dtype=np.int32); iters = np.full(m, -2, dtype=np.int32); used = np.full(m, -2, dtype=np.int32)
+        cost0 = np.full(m, np.nan); cost = np.full(m, np.nan)
+        err = np.full(max(int(offs[-1]), 1), np.nan) if with_errors else None
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.lib.ccal_refine_poses_batch(self.handle, int(model), _dp(par), float(huber_delta), n,
+                                              offs.ctypes.data_as(C.POINTER(C.c_int64)), _dp(allx), _dp(allu), int(min_points),
+                                              C.byref(opts) if opts is not None else None, _dp(poses), ip(status), ip(iters),
+                                              ip(used), _dp(cost0), _dp(cost), _dp(err))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_refine_poses_batch", self.last_error())
+        out = (poses[:n], status[:n], iters[:n], used[:n], cost0[:n], cost[:n])
+        if with_errors:
+            out += ([err[int(offs[i]):int(offs[i + 1])] for i in range(n)],)
+        return out
+
     # -- applying a calibration: points, the new camera matrix, undistortion maps (ccal_kernels_undistort.hip) ---------------
     def _points(self, fn, where, model: int, params, pts, in_w: int, out_w: int):
         pts = _f64(pts)

@@ -32,6 +32,7 @@
  *   ccal_homography_to_focal homography_to_focal                          src/optimization/homography.rs:274-325
  *   ccal_pnp_batch           sqpnp_solve_glam (any 3-D point set), batched  src/util.rs:431
  *   ccal_init_poses_division init_pose                                    src/optimization/linear.rs:5-21
+ *   ccal_refine_poses_batch  ReprojectionFactor + HuberLoss over the pose alone, intrinsics fixed, batched
  *
  * Parameter layout.
  *   intr   [n_cams][CCAL_PMAX]  FULL model parameters [fx,fy,cx,cy,dist...] per camera, like
@@ -408,6 +409,58 @@ int ccal_init_poses(ccal_problem* p, const double* intr, int min_points, double*
 int ccal_pnp_batch(ccal_ctx* ctx, int n_prob, const int64_t* offsets /* [n_prob + 1] */, const double* xyz /* [.][3] */,
                    const double* xn /* [.][2] */, int min_points, double* poses_out /* [n_prob][6] */, int32_t* n_used_out,
                    double* cost_out /* [n_prob] or NULL */);
+
+/* ---- pose refinement under fixed intrinsics, batched (the ReprojectionFactor of src/optimization/factors.rs:152-173 with its
+ * HuberLoss, over rvec | tvec only; what examples/test_pnp.rs needs after its PnP, and what an error on held-out frames needs)
+ * n_prob independent frames in one launch, one wavefront each.  Frame i holds the points [offsets[i], offsets[i + 1]) of xyz [.][3]
+ * (board points) and uv [.][2] (their detections, pixels); offsets[0] == 0; points with a coordinate that is not finite are left
+ * out.  params: the camera's params() vector in the context's conventions (ocv5_order, KB4 small radius); it stays fixed.  For
+ * every frame the call minimises, from the pose given in poses_io, the Huber objective
+ *     F(rvec, tvec) = sum_i rho(s_i),   s_i = | project(params, R(rvec) X_i + tvec) - uv_i |^2,
+ *     rho(s) = s for s <= delta^2, else 2 delta sqrt(s) - delta^2;  rho'(s) = 1, else delta / sqrt(s);  huber_delta <= 0: rho(s) = s,
+ * with the Huber corrector of the joint solve: residual and Jacobian rows scaled by sqrt(rho'(s)), so that g below is half the
+ * gradient of F.  The cost REPORTED (cost0_out, cost_out) is the library's cost (ccal_report), sum_i rho'(s_i) s_i.  While no corner
+ * is beyond delta the two are the same function.  With outliers they are not (delta sqrt(s) per outlier against 2 delta sqrt(s) -
+ * delta^2) and their minima differ: steps and stop rules are judged on F, the function the step descends - judged on the reported
+ * cost, the iteration would end between the two minima, at a stationary point of neither.  That is the one place where the rule
+ * below departs from ccal_solve's LM mode, which judges on the reported cost.  The optimizer is always Levenberg-Marquardt
+ * (opts->method is ignored; opts == NULL: the values of ccal_set_defaults), the rule of ccal_solve's LM mode with one state PER
+ * FRAME:
+ *     radius = lm_initial_radius, dec = 2;  H = J^T J, g = J^T r (corrected rows) at the accepted pose
+ *     step:   (H + lambda D) d = -g,  lambda = 1 / radius,  D_ii = clamp(H_ii, lm_min_diagonal, lm_max_diagonal);
+ *             model decrease mc = d^T (lambda D d - g);  trial = pose + d;  rho = (F - F_trial) / mc;  iterations += 1
+ *     - mc >= 0 and the model decrease (in the error metric) < min_abs_error_decrease or < min_rel_error_decrease x error:
+ *       converged - the trial is taken if its F is lower - CCAL_OK
+ *     - else mc > 0 and rho > 0: the trial is accepted, radius = min(1e16, radius / max(1/3, 1 - (2 rho - 1)^3)), dec = 2; CCAL_OK
+ *       when error < min_error, |error decrease| < min_abs_error_decrease or |error decrease| / last error < min_rel_error_decrease
+ *     - else (also: the system is not positive definite, the trial cost is not finite): rejected, radius /= dec, dec *= 2;
+ *       radius < 1e-32: CCAL_ERR_NO_CONVERGENCE
+ *     - iterations >= max_iterations: CCAL_ERR_NO_CONVERGENCE (the pose is the best accepted one)
+ * "error" is F, or its square root with error_metric = CCAL_ERROR_NORM.  A frame stops by its own rule: it neither waits
+ * for nor is held up by the other frames of the batch.
+ * A corner whose projection is undefined at a pose (not finite: a point at depth 0 for OPENCV5, on the singular cone of UCM / EUCM)
+ * has no rule of its own, as in ccal_eval / ccal_solve: its residual makes F and the cost NaN.  At the starting pose that ends the frame
+ * with CCAL_ERR_NONFINITE (pose untouched, cost0 = cost = that value); at a trial pose the step is rejected like any other step to
+ * a cost that is not finite.
+ * Per frame: status_out is CCAL_OK, CCAL_ERR_NO_CONVERGENCE, CCAL_ERR_NONFINITE, CCAL_NO_RESULT (fewer than max(min_points, 3)
+ * valid points or a starting pose that is not finite: pose untouched, iterations 0, n_used 0, both costs 0, every err_out row of
+ * the frame NaN); CCAL_ERR_NOT_PD belongs to the set of values a caller should expect but the LM rule above turns a failed
+ * factorisation into a rejected step.  iters_out = steps tried, n_used_out = valid points, cost0_out / cost_out = the reported
+ * cost at the start / at the result; any of these four may be NULL.  err_out [n_points] (or NULL) = | project - uv | in pixels at the result,
+ * NaN in the rows of left-out points.  The call returns CCAL_OK in all these cases; n_prob == 0 is allowed (nothing is read or
+ * written).  A frame's outputs are a pure function of that frame's inputs: they do not depend on its place in the batch or on the
+ * other frames, and are bit-identical from run to run (lane-private sums in f64, one xor-shuffle butterfly, no atomics).
+ * The EUCMT container: CCAL_ERR_UNSUPPORTED.  An unknown model, offsets[0] != 0, decreasing offsets, more than 2^24 points in a
+ * frame or a NULL required pointer (params, offsets, poses_io, status_out; xyz / uv when there are points): CCAL_ERR_INVALID_ARG.
+ * Nothing is launched or written in either case. */
+int ccal_refine_poses_batch(ccal_ctx* ctx, int model, const double* params, double huber_delta,
+                            int n_prob, const int64_t* offsets /* [n_prob + 1] */,
+                            const double* xyz /* [.][3] */, const double* uv /* [.][2] pixels */,
+                            int min_points, const ccal_solver_opts* opts /* NULL: defaults */,
+                            double* poses_io /* [n_prob][6] in: start, out: result */,
+                            int32_t* status_out, int32_t* iters_out, int32_t* n_used_out,
+                            double* cost0_out, double* cost_out,      /* [n_prob] each, any may be NULL except status */
+                            double* err_out /* [n_points] pixel error at the result, or NULL */);
 
 /* ---- initialisation from detections alone (try_init_camera, src/util.rs:107-159) --------------
  * radial_distortion_homography (src/optimization/homography.rs:218-271): RANSAC over a six-point minimal solver for a

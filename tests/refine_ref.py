@@ -1,0 +1,109 @@
+"""numpy f64 yardstick for the pose refinement under fixed intrinsics (ccal_refine_poses_batch, csrc/ccal_kernels_refine.hip),
+written independently of the kernel.
+
+With r_i = synth.project(model, params, R(rvec) X_i + tvec) - uv_i, s_i = |r_i|^2 and the Huber loss
+    rho(s) = s for s <= delta^2, else 2 delta sqrt(s) - delta^2;    rho'(s) = 1, else delta / sqrt(s)    (delta <= 0: rho(s) = s),
+the library's corrector scales residual and Jacobian rows by sqrt(rho'(s)): a Gauss-Newton step of the corrected system solves
+J^T W J d = -J^T W r, which vanishes where the gradient of objective() = sum_i rho(s_i) does.  cost() = sum_i rho'(s_i) s_i is the
+figure the library REPORTS (ccal_report, cost_out); on frames without outliers the two are the same function, with outliers cost()
+counts each outlier delta sqrt(s) and is not stationary where the iteration stops.  The minimiser here is that iteration in
+numpy: Levenberg-Marquardt on the corrected system with central-difference Jacobians of r through synth.project (no analytic
+derivative anywhere), a step taken when objective() decreases, run until the step stalls.  solve() starts it both from the
+given pose and from the ground truth and keeps the lower objective.
+"""
+import numpy as np
+
+from camera_intrinsic_calibration_rs_amd import synth
+
+_H = 1e-6          # central-difference step on rvec (rad) and tvec (m): truncation ~h^2, rounding ~1e-16 / h
+
+
+def residuals(model, params, X, uv, pose):
+    """pose [6] -> r [n, 2]; poses [k, 6] -> r [k, n, 2]."""
+    pose = np.asarray(pose, dtype=np.float64)
+    R = synth.rodrigues(pose[..., :3])
+    pc = np.einsum("...ij,nj->...ni", R, np.asarray(X, dtype=np.float64)) + pose[..., None, 3:]
+    return synth.project(model, params, pc) - np.asarray(uv, dtype=np.float64)
+
+
+def weights(s, delta):
+    """rho'(s) of the Huber loss as the library evaluates it."""
+    if not delta > 0.0:
+        return np.ones_like(s)
+    return np.where(s > delta * delta, delta / np.sqrt(np.where(s > 0, s, 1.0)), 1.0)
+
+
+def corrected(model, params, X, uv, pose, delta):
+    """c = sqrt(rho') r, flattened per pose: [2 n] or [k, 2 n]."""
+    r = residuals(model, params, X, uv, pose)
+    s = (r * r).sum(axis=-1)
+    c = r * np.sqrt(weights(s, delta))[..., None]
+    return c.reshape(c.shape[:-2] + (-1,))
+
+
+def cost(model, params, X, uv, pose, delta):
+    r = residuals(model, params, X, uv, pose)
+    s = (r * r).sum(axis=-1)
+    c = (weights(s, delta) * s).sum(axis=-1)
+    return float(c) if c.ndim == 0 else c
+
+
+def objective(model, params, X, uv, pose, delta):
+    """sum rho(s): the function whose stationary point the corrected Gauss-Newton iteration finds."""
+    r = residuals(model, params, X, uv, pose)
+    s = (r * r).sum(axis=-1)
+    if delta > 0.0:
+        s = np.where(s > delta * delta, 2.0 * delta * np.sqrt(s) - delta * delta, s)
+    c = s.sum(axis=-1)
+    return float(c) if c.ndim == 0 else c
+
+
+def _stencil(pose, h):
+    pose = np.asarray(pose, dtype=np.float64)
+    return np.concatenate([pose + h * np.eye(6), pose - h * np.eye(6)])
+
+
+def gradient(model, params, X, uv, pose, delta, h=_H):
+    """Central-difference gradient of objective() with respect to rvec | tvec."""
+    c = objective(model, params, X, uv, _stencil(pose, h), delta)
+    return (c[:6] - c[6:]) / (2 * h)
+
+
+def _corrected_system(model, params, X, uv, pose, delta, h=_H):
+    """(J, c): central-difference Jacobian of r and r itself, rows scaled by sqrt(rho')."""
+    r = residuals(model, params, X, uv, pose)
+    sw = np.sqrt(weights((r * r).sum(axis=-1), delta))
+    rs = residuals(model, params, X, uv, _stencil(pose, h))
+    J = (rs[:6] - rs[6:]) / (2 * h)                                   # [6, n, 2]
+    return (J * sw[None, :, None]).reshape(6, -1).T, (r * sw[:, None]).ravel()
+
+
+def refine(model, params, X, uv, pose0, delta, max_iter=300):
+    """LM from pose0 until the step stalls: (pose, cost() there)."""
+    x = np.asarray(pose0, dtype=np.float64).copy()
+    F = objective(model, params, X, uv, x, delta)
+    lam = 1e-4
+    for _ in range(max_iter):
+        J, c = _corrected_system(model, params, X, uv, x, delta)
+        H = J.T @ J
+        g = J.T @ c
+        moved = False
+        while lam < 1e12:
+            d = -np.linalg.solve(H + lam * np.diag(np.maximum(np.diag(H), 1e-12)), g)
+            Fn = objective(model, params, X, uv, x + d, delta)
+            if Fn < F:
+                x = x + d; F = Fn; lam = max(lam * 0.1, 1e-15); moved = True
+                break
+            if np.abs(d).max() < 1e-15:
+                break
+            lam *= 10.0
+        if not moved or np.abs(d).max() < 1e-14:
+            break
+    return x, cost(model, params, X, uv, x, delta)
+
+
+def solve(model, params, X, uv, pose_start, pose_gt, delta):
+    """The yardstick's answer for one frame: of the runs from pose_start and from pose_gt the one with the lower objective."""
+    a = refine(model, params, X, uv, pose_start, delta)
+    b = refine(model, params, X, uv, pose_gt, delta)
+    return a if objective(model, params, X, uv, a[0], delta) <= objective(model, params, X, uv, b[0], delta) else b

@@ -1,0 +1,71 @@
+"""CPU: the numpy yardstick of the pose refinement (tests/refine_ref.py) holds on its own - it recovers the ground truth on
+noise-free frames of each model and ends at a stationary point of its cost - and api.refine_poses sorts out frames it cannot use
+before anything reaches the library."""
+import numpy as np
+import pytest
+
+from camera_intrinsic_calibration_rs_amd import api, synth
+
+import refine_ref
+
+MODELS = ["ucm", "eucm", "kb4", "opencv5"]
+
+
+def _exact_frames(model, n_frames):
+    """Frames of synth.make_problem with uv recomputed in f64 at the true pose: (model id, params, [(X, uv)], poses_gt)."""
+    sp = synth.make_problem(n_frames, model, noise_px=0)
+    m = int(sp.model[0])
+    par = sp.intr_gt[0, :synth.MODEL_NPARAMS[m]]
+    fr = []
+    for f in range(n_frames):
+        a, b = int(sp.obs_offsets[f]), int(sp.obs_offsets[f + 1])
+        X = sp.p3d[a:b].astype(np.float64)
+        pc = X @ synth.rodrigues(sp.poses_gt[f, :3]).T + sp.poses_gt[f, 3:]
+        fr.append((X, synth.project(m, par, pc)))
+    return m, par, fr, sp.poses_gt
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_yardstick_recovers_ground_truth(model):
+    m, par, fr, gt = _exact_frames(model, 3)
+    for f, (X, uv) in enumerate(fr):
+        start = gt[f] + np.array([0.05, -0.05, 0.05, 0.02, 0.02, -0.02])
+        pose, c = refine_ref.refine(m, par, X, uv, start, 1.0)
+        dR = np.abs(synth.rodrigues(pose[:3]) - synth.rodrigues(gt[f, :3])).max()
+        dt = np.abs(pose[3:] - gt[f, 3:]).max()
+        # exact data: the cost at the truth is 0 and every step of the LM is a Gauss-Newton step on a zero-residual problem
+        assert c < 1e-18, c
+        assert dR < 1e-10 and dt < 1e-10, (dR, dt)
+
+
+def test_yardstick_cost_is_stationary():
+    """Noisy frames with outliers: the central-difference gradient of the cost at the yardstick's result is 1e-7 of the gradient
+    at its start or less (the difference quotient of a cost of ~100 px^2 with h = 1e-6 resolves ~1e-8 of a gradient of ~1e5)."""
+    sp = synth.make_problem(4, "eucm", noise_px=0.1, ragged=True, outlier_frac=0.05)
+    m = int(sp.model[0])
+    par = sp.intr_gt[0, :synth.MODEL_NPARAMS[m]]
+    for f in range(4):
+        a, b = int(sp.obs_offsets[f]), int(sp.obs_offsets[f + 1])
+        X, uv = sp.p3d[a:b].astype(np.float64), sp.p2d[a:b].astype(np.float64)
+        pose, c = refine_ref.solve(m, par, X, uv, sp.poses0[f], sp.poses_gt[f], 1.0)
+        g0 = np.linalg.norm(refine_ref.gradient(m, par, X, uv, sp.poses0[f], 1.0))
+        g = np.linalg.norm(refine_ref.gradient(m, par, X, uv, pose, 1.0))
+        assert c <= refine_ref.cost(m, par, X, uv, sp.poses0[f], 1.0)
+        assert g <= 1e-7 * g0, (g, g0)
+
+
+def test_refine_poses_unusable_frames_never_reach_the_library(monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("the library was touched")
+    monkeypatch.setattr(api, "_ctx", boom)
+    monkeypatch.setattr(api, "init_frame_poses", boom)
+    cam = api.GenericModel("eucm", synth.GT_PARAMS[synth.MODEL_NAMES["eucm"]], 512, 512)
+    few = api.FrameFeature(0, (512, 512), {k: api.FeaturePoint((10.0 * k, 5.0), (0.1 * k, 0.0, 0.0)) for k in range(3)})
+    pose = api.RvecTvec((0.0, 0.0, 0.0), (0.0, 0.0, 1.0))
+    assert api.refine_poses([], cam) == {}
+    assert api.refine_poses([None, None], cam) == {}
+    assert api.refine_poses([None, few], cam) == {}
+    assert api.refine_poses([None, few], cam, {0: pose, 1: pose}) == {}
+    # a usable frame without a starting pose in the map is left out as well
+    ok = api.FrameFeature(0, (512, 512), {k: api.FeaturePoint((10.0 * k, 5.0), (0.1 * k, 0.01 * k * k, 0.0)) for k in range(6)})
+    assert api.refine_poses([ok, None], cam, {1: pose}) == {}
