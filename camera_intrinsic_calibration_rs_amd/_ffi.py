@@ -116,6 +116,8 @@ SYMBOLS = [
     ("ccal_pnp_batch", C.c_int, [_vp, C.c_int, _lp, _dp, _dp, C.c_int, _dp, _ip, _dp]),
     ("ccal_refine_poses_batch", C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_int, _lp, _dp, _dp, C.c_int, C.POINTER(SolverOpts),
                                           _dp, _ip, _ip, _ip, _dp, _dp, _dp]),
+    ("ccal_refine_rig_poses_batch", C.c_int, [_vp, C.c_int, _ip, _dp, _dp, C.c_double, C.c_int, _lp, _ip, _lp, _dp, _dp, C.c_int,
+                                              C.POINTER(SolverOpts), _dp, _ip, _ip, _ip, _dp, _dp, _dp]),
     ("ccal_init_poses_division", C.c_int, [_vp, C.c_double, C.c_int, _dp, _ip]),
     ("ccal_pin_buffer", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("ccal_unpin_buffer", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -631,6 +631,64 @@ def validation_holdout(cam_idx: int, model: GenericModel, frame_feature_list: Se
     return validation(cam_idx, model, refine_poses(frame_feature_list, model, ctx=ctx), frame_feature_list, ctx=ctx)
 
 
+def refine_rig_poses(cams_detected_feature_frames: Sequence[Sequence[Optional[FrameFeature]]], cameras: Sequence[GenericModel],
+                     t_cam_i_0: Sequence[RvecTvec], board_rtvecs: Optional[Dict[int, RvecTvec]] = None, huber_delta: float = 1.0,
+                     ctx: Optional[Context] = None, opts: "Optional[_ffi.SolverOpts]" = None) -> Dict[int, RvecTvec]:
+    """The board pose T_0_b of every frame index under the FIXED rig `cameras`, `t_cam_i_0`: the minimiser of the Huber cost of the
+    pixel reprojection error over ALL cameras that saw the frame (the OtherCamReprojectionFactor of the joint solve over rvec_0_b |
+    tvec_0_b alone), one wavefront per frame, all frames in one launch (ccal_refine_rig_poses_batch).  A frame seen by several
+    cameras gets one pose.  Every entry of t_cam_i_0 is used as given (the reference's camera 0 is the identity).  Starts from
+    board_rtvecs where given, otherwise by the rule of the joint solve (src/util.rs:576-651): T_c_0^-1 o T_c_b with the
+    init_frame_poses result T_c_b of the first camera that has one (camera 0's own result where t_cam_i_0[0] is the identity).
+    Frames without a start or without a result are absent from the returned map.  `opts`: the stop rules of the solve (None: the
+    library's defaults)."""
+    n_cams = len(cameras)
+    if len(t_cam_i_0) != n_cams or len(cams_detected_feature_frames) != n_cams:
+        raise ValueError("refine_rig_poses: one frame list and one T_c_0 per camera")
+    for m in cameras:
+        m._usable("refine_rig_poses")
+    n_frames = max((len(f) for f in cams_detected_feature_frames), default=0)
+    seen = [[c for c in range(n_cams) if fi < len(cams_detected_feature_frames[c]) and cams_detected_feature_frames[c][fi] is not None]
+            for fi in range(n_frames)]
+    if board_rtvecs is None:
+        board_rtvecs = {}
+        cam_rtvecs = [init_frame_poses(cams_detected_feature_frames[c], cameras[c], ctx=ctx) for c in range(n_cams)]
+        for fi in range(n_frames):
+            for c in range(n_cams):
+                if fi in cam_rtvecs[c]:
+                    board_rtvecs[fi] = t_cam_i_0[c].inverse().compose(cam_rtvecs[c][fi])
+                    break
+    cand = [fi for fi in range(n_frames) if seen[fi] and fi in board_rtvecs]
+    if not cand:
+        return {}
+    slots = []
+    for fi in cand:
+        segs = []
+        for c in seen[fi]:
+            ff = cams_detected_feature_frames[c][fi]
+            ids = sorted(ff.features.keys())
+            # the reference holds detections and board points in f32 (src/detected_points.rs:6-9)
+            segs.append((c, np.asarray([ff.features[k].p3d for k in ids], dtype=np.float32).astype(np.float64).reshape(-1, 3),
+                         np.asarray([ff.features[k].p2d for k in ids], dtype=np.float32).astype(np.float64).reshape(-1, 2)))
+        slots.append(segs)
+    poses0 = np.stack([board_rtvecs[fi].as6() for fi in cand])
+    poses, status, _, _, _, _ = _ctx(ctx).refine_rig_poses_batch([m.model_id for m in cameras], [m._params for m in cameras],
+                                                                 np.stack([t.as6() for t in t_cam_i_0]), slots, poses0, huber_delta,
+                                                                 _REFINE_MIN_POINTS, opts)
+    return {fi: RvecTvec.from6(poses[k]) for k, fi in enumerate(cand) if status[k] in (_ffi.OK, _ffi.ERR_NO_CONVERGENCE)}
+
+
+def validation_holdout_rig(cameras: Sequence[GenericModel], t_cam_i_0: Sequence[RvecTvec],
+                           cams_detected_feature_frames: Sequence[Sequence[Optional[FrameFeature]]],
+                           ctx: Optional[Context] = None, opts: "Optional[_ffi.SolverOpts]" = None) -> List[Tuple[float, float]]:
+    """The with-extrinsics branch of save_and_validate_results (src/bin/camera_calibration.rs:277-307) on frames the fit did not
+    see: the board poses T_0_b are fitted with the whole rig fixed (refine_rig_poses), then per camera util::validation at
+    T_i_0 o T_0_b - (avg of the lowest 99 %, median) reprojection error in px for every camera.  `opts` as in refine_rig_poses."""
+    t_0_b = refine_rig_poses(cams_detected_feature_frames, cameras, t_cam_i_0, ctx=ctx, opts=opts)
+    return [validation(c, cameras[c], {k: t_cam_i_0[c].compose(t) for k, t in t_0_b.items() if k < len(cams_detected_feature_frames[c])},
+                       cams_detected_feature_frames[c], ctx=ctx) for c in range(len(cameras))]
+
+
 class ReprojectionFactor:
     """optimization::factors::ReprojectionFactor (src/optimization/factors.rs:126-173).
     residual_func(params) with params = [intrinsics (P_eff), rvec, tvec] evaluates the block on the GPU;

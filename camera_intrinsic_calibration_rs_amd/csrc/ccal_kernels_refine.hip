@@ -20,9 +20,7 @@
 #include <cmath>
 #include <string>
 
-#include "ccal_device.hpp"
-#include "ccal_fused.hpp"
-#include "ccal_internal.hpp"
+#include "ccal_refine.hpp"
 
 namespace ccal {
 
@@ -35,116 +33,15 @@ struct RefineArgs {
     int32_t* status; int32_t* iters; int32_t* n_used;
     double* cost0; double* cost;        // [n_prob]
     double* err;                        // [n_points] pixel error at the result, or nullptr
-    double delta;
-    double radius0, min_diag, max_diag, min_error, min_abs, min_rel;
-    int32_t n_prob, min_points, max_iter, error_metric;
+    RefineRule rule;
 };
 
-constexpr int kRefTri = 21;             // packed lower triangle of the 6 x 6 system: entry (i, j <= i) at i (i + 1) / 2 + j
-
-__device__ __forceinline__ bool refine_finite(double v) { return fabs(v) < __builtin_inf(); }
-
-// One pass over the frame's corners at `pose`: H = J^T J (packed lower), g = J^T r, cost = sum rho'(s) s, obj = sum rho(s), the same
-// on all lanes.
-// err != nullptr: also the pixel error of every corner (NaN for a corner that is left out).
-template <int MODEL>
-__device__ __forceinline__ void refine_pass(const double* th, const double* pose, const double* xyz, const double* uv, double* err,
-                                            const int n, const int lane, const double delta, double* H, double* g, double& cost, double& obj) {
-    constexpr int P = model_np(MODEL);
-    double fc[FC_N0];
-    frame_setup<false>(pose, nullptr, fc);
-#pragma unroll
-    for (int i = 0; i < kRefTri; ++i) H[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) g[i] = 0.0;
-    cost = 0.0; obj = 0.0;
-    for (int c = lane; c < n; c += 64) {
-        const double X = xyz[3 * (int64_t)c], Y = xyz[3 * (int64_t)c + 1], Z = xyz[3 * (int64_t)c + 2];
-        const double uo = uv[2 * (int64_t)c], vo = uv[2 * (int64_t)c + 1];
-        const bool valid = refine_finite(X) && refine_finite(Y) && refine_finite(Z) && refine_finite(uo) && refine_finite(vo);
-        if (!valid) {
-            if (err) err[c] = __builtin_nan("");
-            continue;
-        }
-        double ru, rv, Ju[P + 6], Jv[P + 6];
-        corner_block<MODEL, false, false>(th, fc, X, Y, Z, uo, vo, ru, rv, Ju, Jv);
-        const double s = ru * ru + rv * rv;
-        if (err) err[c] = sqrt(s);
-        const double sw = huber_sqrt_weight(s, delta);
-        ru *= sw; rv *= sw;
-        const double cs = ru * ru + rv * rv;            // rho'(s) s: s, or delta sqrt(s) for a corner beyond delta
-        cost += cs;
-        obj += (delta > 0.0 && s > delta * delta) ? 2.0 * cs - delta * delta : cs;      // rho(s): s, or 2 delta sqrt(s) - delta^2
-        double a[6], b[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) { a[i] = sw * Ju[P + i]; b[i] = sw * Jv[P + i]; }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-#pragma unroll
-            for (int j = 0; j <= i; ++j) H[i * (i + 1) / 2 + j] += a[i] * a[j] + b[i] * b[j];
-            g[i] += a[i] * ru + b[i] * rv;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < kRefTri; ++i) H[i] += __shfl_xor(H[i], off, 64);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) g[i] += __shfl_xor(g[i], off, 64);
-        cost += __shfl_xor(cost, off, 64);
-        obj += __shfl_xor(obj, off, 64);
-    }
-}
-
-// (H + diag(D)) d = -g by Cholesky, in registers (the arithmetic of chol_solve_reg).  false: not positive definite (d = 0).
-__device__ __forceinline__ bool refine_solve(const double* H, const double* D, const double* g, double* d) {
-    double M[kRefTri], v[6];
-#pragma unroll
-    for (int i = 0; i < kRefTri; ++i) M[i] = H[i];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) { M[i * (i + 1) / 2 + i] += D[i]; v[i] = -g[i]; }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double dj = M[j * (j + 1) / 2 + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) dj -= M[j * (j + 1) / 2 + k] * M[j * (j + 1) / 2 + k];
-        ok = ok && (dj > 0.0) && (dj < 1.7e308);
-        double sq, rs;
-        fast_sqrt_rsqrt(ok ? dj : 1.0, sq, rs);
-        M[j * (j + 1) / 2 + j] = rs;                       // inverted diagonal
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double t = M[i * (i + 1) / 2 + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) t -= M[i * (i + 1) / 2 + k] * M[j * (j + 1) / 2 + k];
-            M[i * (i + 1) / 2 + j] = t * rs;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double t = v[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) t -= M[i * (i + 1) / 2 + k] * v[k];
-        v[i] = t * M[i * (i + 1) / 2 + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double t = v[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) t -= M[k * (k + 1) / 2 + i] * v[k];
-        v[i] = t * M[i * (i + 1) / 2 + i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) d[i] = ok ? v[i] : 0.0;
-    return ok;
-}
-
+// The pass, solve and decide steps are in ccal_refine.hpp, shared with the rig's kernel (ccal_kernels_rig_refine.hip).
 template <int MODEL>
 __global__ __launch_bounds__(256) void k_pose_refine(const RefineArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int o = blockIdx.x * WAVES_PER_BLOCK + wave;
-    if (o >= a.n_prob) return;
+    if (o >= a.rule.n_prob) return;
     const int64_t start = a.off[o];
     const int n = (int)(a.off[o + 1] - start);
     const double* xyz = a.xyz + 3 * start;
@@ -153,20 +50,15 @@ __global__ __launch_bounds__(256) void k_pose_refine(const RefineArgs a) {
     double th[th_len<MODEL>()];
     load_theta<MODEL, false>(a.th, a.rt, th);
 
-    double pose[6], trial[6];
+    double pose[6];
     bool start_ok = true;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) { pose[i] = a.poses[(int64_t)o * 6 + i]; trial[i] = pose[i]; start_ok = start_ok && refine_finite(pose[i]); }
+    for (int i = 0; i < 6; ++i) { pose[i] = a.poses[(int64_t)o * 6 + i]; start_ok = start_ok && refine_finite(pose[i]); }
     int cnt = 0;
-    for (int c = lane; c < n; c += 64) {
-        bool v = refine_finite(uv[2 * (int64_t)c]) && refine_finite(uv[2 * (int64_t)c + 1]);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v = v && refine_finite(xyz[3 * (int64_t)c + k]);
-        cnt += v ? 1 : 0;
-    }
+    for (int c = lane; c < n; c += 64) cnt += refine_point_valid(xyz, uv, c) ? 1 : 0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if (!start_ok || cnt < (a.min_points > 3 ? a.min_points : 3)) {      // no result: the pose stays as the caller gave it
+    if (!start_ok || cnt < (a.rule.min_points > 3 ? a.rule.min_points : 3)) {      // no result: the pose stays as the caller gave it
         if (err) for (int c = lane; c < n; c += 64) err[c] = __builtin_nan("");
         if (lane == 0) {
             a.status[o] = CCAL_NO_RESULT; a.iters[o] = 0; a.n_used[o] = 0; a.cost0[o] = 0.0; a.cost[o] = 0.0;
@@ -174,81 +66,29 @@ __global__ __launch_bounds__(256) void k_pose_refine(const RefineArgs a) {
         return;
     }
 
-    // the frame's optimizer state (optimizer_decide's LM branch, ccal_fused.hpp, with the frame's own radius and stop rules)
-    // cur: sum rho(s) at the accepted pose, what the steps and the stop rules are judged on; rep: the reported cost there
-    double H[kRefTri], g[6], cur = 0.0, rep = 0.0, cost0 = 0.0;
-    double radius = a.radius0, dec = 2.0, mc = 0.0;
-    int iter = 0, done = 0;               // done: ccal_status + 1
-    bool first = true, lin_ok = true, final_pass = false;
-    const int em = a.error_metric;
-    for (;;) {
-        double Ht[kRefTri], gt[6], rt, ct;
-        refine_pass<MODEL>(th, trial, xyz, uv, final_pass ? err : nullptr, n, lane, a.delta, Ht, gt, rt, ct);
-        if (final_pass) break;
-        bool accept = false;
-        if (first) {
-            first = false; accept = true; cost0 = rt;
-            if (!(fabs(ct) < 1.7e308)) done = CCAL_ERR_NONFINITE + 1;
-        } else {
-            iter += 1;
-            const double rho = (cur - ct) / mc;
-            const bool fin = fabs(ct) < 1.7e308;
-            const double mce = model_decrease_of(cur, mc, em);
-            if (lin_ok && fin && mc >= 0.0 && (mce < a.min_abs || mce < a.min_rel * error_of(cur, em))) {
-                // predicted decrease below the thresholds: converged
-                accept = ct < cur;
-                done = CCAL_OK + 1;
-            } else if (lin_ok && fin && mc > 0.0 && rho > 0.0) {
-                accept = true;
-                const double t = 2.0 * rho - 1.0;
-                radius = fmin(1e16, radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-                dec = 2.0;
-                const double le = error_of(cur, em), ce = error_of(ct, em);
-                if (ce < a.min_error) done = CCAL_OK + 1;
-                else if (fabs(le - ce) < a.min_abs) done = CCAL_OK + 1;
-                else if (fabs(le - ce) / le < a.min_rel) done = CCAL_OK + 1;
-            } else {
-                radius /= dec; dec *= 2.0;
-                if (radius < 1e-32) done = CCAL_ERR_NO_CONVERGENCE + 1;
-            }
-            if (!done && iter >= a.max_iter) done = CCAL_ERR_NO_CONVERGENCE + 1;
-        }
-        if (accept) {
-            cur = ct; rep = rt;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) { pose[i] = trial[i]; g[i] = gt[i]; }
-#pragma unroll
-            for (int i = 0; i < kRefTri; ++i) H[i] = Ht[i];
-        }
-        if (done) {
-            if (!err) break;
-            final_pass = true;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) trial[i] = pose[i];
-            continue;
-        }
-        // the damped step from the accepted point and its model decrease  d^T (D d - g)
-        const double lambda = 1.0 / radius;
-        double D[6], d[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) D[i] = lambda * fmin(fmax(H[i * (i + 1) / 2 + i], a.min_diag), a.max_diag);
-        lin_ok = refine_solve(H, D, g, d);
-        mc = 0.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) { mc += d[i] * (D[i] * d[i] - g[i]); trial[i] = pose[i] + d[i]; }
-    }
+    // one pass over the frame's corners at the pose p: the totals on all lanes
+    const double delta = a.rule.delta;
+    auto pass = [&](const double* p, const bool with_err, double* H, double* g, double& rep, double& obj) {
+        double fc[FC_N0];
+        frame_setup<false>(p, nullptr, fc);
+        refine_zero(H, g, rep, obj);
+        refine_corners<MODEL, false>(th, fc, xyz, uv, with_err ? err : nullptr, n, lane, delta, H, g, rep, obj);
+        refine_reduce(H, g, rep, obj);
+    };
+    int iter;
+    double cost0, cost;
+    const int status = refine_lm(a.rule, err != nullptr, pass, pose, iter, cost0, cost);
     if (lane == 0) {
-        const bool nonfinite = done == CCAL_ERR_NONFINITE + 1;          // (the start itself: the pose stays, the costs are what they are)
 #pragma unroll
         for (int i = 0; i < 6; ++i) a.poses[(int64_t)o * 6 + i] = pose[i];
-        a.status[o] = done - 1; a.iters[o] = iter; a.n_used[o] = cnt;
-        a.cost0[o] = cost0; a.cost[o] = nonfinite ? cost0 : rep;
+        a.status[o] = status; a.iters[o] = iter; a.n_used[o] = cnt;
+        a.cost0[o] = cost0; a.cost[o] = cost;
     }
 }
 
 template <int MODEL>
 static hipError_t launch_refine(const RefineArgs& a, hipStream_t s) {
-    const int blocks = (a.n_prob + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    const int blocks = (a.rule.n_prob + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_pose_refine<MODEL>, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -265,7 +105,6 @@ int hip_fail(ccal_ctx* ctx, const char* where, hipError_t e) {
     try { ctx->err = std::string(where) + ": " + hipGetErrorString(e); } catch (...) { }
     return CCAL_ERR_HIP;
 }
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -296,8 +135,8 @@ int ccal_refine_poses_batch(ccal_ctx* ctx, int model, const double* params, doub
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
     // one block: offsets | points | image points | poses, cost0, cost | errors | status, iterations, counts
-    const size_t b_off = up256((np + 1) * 8), b_xyz = up256((n_tot + 1) * 24), b_uv = up256((n_tot + 1) * 16), b_res = up256(np * 8 * 8);
-    const size_t b_err = err_out ? up256((n_tot + 1) * 8) : 0, b_int = up256(np * 3 * 4);
+    const size_t b_off = refine_up256((np + 1) * 8), b_xyz = refine_up256((n_tot + 1) * 24), b_uv = refine_up256((n_tot + 1) * 16), b_res = refine_up256(np * 8 * 8);
+    const size_t b_err = err_out ? refine_up256((n_tot + 1) * 8) : 0, b_int = refine_up256(np * 3 * 4);
     char* d = nullptr;
     e = ctx_dev_alloc(ctx, (void**)&d, b_off + b_xyz + b_uv + b_res + b_err + b_int);
     if (e != hipSuccess) return hip_fail(ctx, "ccal_refine_poses_batch: allocation", e);
@@ -315,10 +154,7 @@ int ccal_refine_poses_batch(ccal_ctx* ctx, int model, const double* params, doub
     a.off = d_off; a.xyz = d_xyz; a.uv = d_uv;
     a.poses = d_po; a.cost0 = d_po + np * 6; a.cost = d_po + np * 7; a.err = d_err;
     a.status = d_int; a.iters = d_int + np; a.n_used = d_int + 2 * np;
-    a.delta = huber_delta;
-    a.radius0 = o.lm_initial_radius; a.min_diag = o.lm_min_diagonal; a.max_diag = o.lm_max_diagonal;
-    a.min_error = o.min_error; a.min_abs = o.min_abs_error_decrease; a.min_rel = o.min_rel_error_decrease;
-    a.n_prob = n_prob; a.min_points = min_points; a.max_iter = o.max_iterations; a.error_metric = o.error_metric ? 1 : 0;
+    a.rule = refine_rule(huber_delta, o, n_prob, min_points);
     hipStream_t s = ctx->stream;
     e = test_poison_f64(ctx, d_xyz, b_xyz + b_uv + b_res + b_err, false, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, (np + 1) * 8, hipMemcpyHostToDevice, s);

@@ -192,6 +192,58 @@ class Context:
             out += ([err[int(offs[i]):int(offs[i + 1])] for i in range(n)],)
         return out
 
+    # -- board poses of a rig under fixed intrinsics and extrinsics, batched (ccal_refine_rig_poses_batch, ccal_kernels_rig_refine.hip) --
+    def refine_rig_poses_batch(self, models, params, extr, slots, poses0, huber_delta: float = 1.0, min_points: int = 4,
+                               opts: "_ffi.SolverOpts | None" = None, with_errors: bool = False):
+        """n independent frame slots of one rig in one launch: the board pose T_0_b of each that minimises the Huber cost of the pixel
+        reprojection error summed over every camera that saw the slot.  models [n_cams], params (one params() vector per camera)
+        and extr [n_cams, 6] (rvec, tvec of T_c_0, every row used as given) stay fixed.  slots: one list per slot of segments
+        (cam, xyz [n_j, 3], uv [n_j, 2]); poses0 [n, 6]: the starting rvec, tvec.  Returns the tuple of refine_poses_batch with
+        "frame" read as "slot": (poses [n, 6], status [n], iterations [n], n_used [n] - over all the slot's cameras -, cost0 [n],
+        cost [n]) and, with_errors, a list of per-slot arrays of pixel errors at the result, the slot's segments one after the other."""
+        n = len(slots)
+        n_cams = len(models)
+        if len(params) != n_cams:
+            raise ValueError("refine_rig_poses_batch: one parameter vector per camera")
+        mod = np.ascontiguousarray(models, dtype=np.int32).reshape(n_cams)
+        par = np.zeros((max(n_cams, 1), PMAX))
+        for c, p in enumerate(params):
+            p = _f64(p).ravel()[:PMAX]
+            par[c, :len(p)] = p
+        ex = _f64(extr).reshape(n_cams, 6)
+        cams, X, U = [], [], []
+        seg_offs = np.zeros(n + 1, dtype=np.int64)
+        for s, segs in enumerate(slots):
+            for cam, x, u in segs:
+                cams.append(int(cam)); X.append(_f64(x).reshape(-1, 3)); U.append(_f64(u).reshape(-1, 2))
+            seg_offs[s + 1] = len(cams)
+        if any(len(a) != len(b) for a, b in zip(X, U)):
+            raise ValueError("refine_rig_poses_batch: a segment's points and detections differ in number")
+        n_seg = len(cams)
+        seg_cam = np.asarray(cams + [0], dtype=np.int32)
+        pt_offs = np.zeros(n_seg + 1, dtype=np.int64)
+        np.cumsum([len(a) for a in X], out=pt_offs[1:])
+        allx = np.ascontiguousarray(np.concatenate(X)) if n_seg else np.zeros((0, 3))
+        allu = np.ascontiguousarray(np.concatenate(U)) if n_seg else np.zeros((0, 2))
+        m = max(n, 1)
+        poses = np.full((m, 6), np.nan)
+        poses[:n] = _f64(poses0).reshape(n, 6)
+        status = np.full(m, -2, dtype=np.int32); iters = np.full(m, -2, dtype=np.int32); used = np.full(m, -2, dtype=np.int32)
+        cost0 = np.full(m, np.nan); cost = np.full(m, np.nan)
+        err = np.full(max(int(pt_offs[-1]), 1), np.nan) if with_errors else None
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        rc = self.lib.ccal_refine_rig_poses_batch(self.handle, n_cams, ip(mod), _dp(par), _dp(ex), float(huber_delta), n, lp(seg_offs),
+                                                  ip(seg_cam), lp(pt_offs), _dp(allx), _dp(allu), int(min_points),
+                                                  C.byref(opts) if opts is not None else None, _dp(poses), ip(status), ip(iters),
+                                                  ip(used), _dp(cost0), _dp(cost), _dp(err))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_refine_rig_poses_batch", self.last_error())
+        out = (poses[:n], status[:n], iters[:n], used[:n], cost0[:n], cost[:n])
+        if with_errors:
+            out += ([err[int(pt_offs[seg_offs[s]]):int(pt_offs[seg_offs[s + 1]])] for s in range(n)],)
+        return out
+
     # -- applying a calibration: points, the new camera matrix, undistortion maps (ccal_kernels_undistort.hip) ---------------
     def _points(self, fn, where, model: int, params, pts, in_w: int, out_w: int):
         pts = _f64(pts)

@@ -33,6 +33,8 @@
  *   ccal_pnp_batch           sqpnp_solve_glam (any 3-D point set), batched  src/util.rs:431
  *   ccal_init_poses_division init_pose                                    src/optimization/linear.rs:5-21
  *   ccal_refine_poses_batch  ReprojectionFactor + HuberLoss over the pose alone, intrinsics fixed, batched
+ *   ccal_refine_rig_poses_batch
+ *                            OtherCamReprojectionFactor + HuberLoss over T_0_b alone, intrinsics and extrinsics fixed, batched
  *
  * Parameter layout.
  *   intr   [n_cams][CCAL_PMAX]  FULL model parameters [fx,fy,cx,cy,dist...] per camera, like
@@ -461,6 +463,42 @@ int ccal_refine_poses_batch(ccal_ctx* ctx, int model, const double* params, doub
                             int32_t* status_out, int32_t* iters_out, int32_t* n_used_out,
                             double* cost0_out, double* cost_out,      /* [n_prob] each, any may be NULL except status */
                             double* err_out /* [n_points] pixel error at the result, or NULL */);
+
+/* ---- board poses of a rig under fixed intrinsics AND extrinsics, batched (the OtherCamReprojectionFactor of
+ * src/optimization/factors.rs:179-228 with its HuberLoss, over rvec_0_b | tvec_0_b only: what a rig's error on held-out frames
+ * needs, and examples/test_pnp.rs for a rig) - ccal_refine_poses_batch with the sum taken over every camera that saw the board.
+ * n_slots independent frame slots in one launch, one wavefront each.  Slot s owns the segments [seg_offsets[s], seg_offsets[s + 1]);
+ * segment j is one camera's observation of the slot: camera seg_cam[j] (0 .. n_cams - 1; a camera may appear more than once) and
+ * the points [pt_offsets[j], pt_offsets[j + 1]) of xyz [.][3] (board points) and uv [.][2] (their detections, pixels);
+ * seg_offsets[0] == 0, pt_offsets[0] == 0.  model [n_cams], params [n_cams][CCAL_PMAX] (each row a params() vector in the
+ * context's conventions: ocv5_order, KB4 small radius) and extr [n_cams][6] (rvec | tvec of T_c_0) stay fixed.  EVERY row of extr
+ * is used as given; zeros make that camera the rig frame, as the reference fixes camera 0.  For every slot the call minimises,
+ * from the pose T_0_b given in poses_io,
+ *     F(rvec, tvec) = sum over the slot's segments j, points i of  rho(s_i),
+ *     s_i = | project(params_c, R(rvec_c_0) (R(rvec) X_i + tvec) + tvec_c_0) - uv_i |^2,   c = seg_cam[j],
+ * and everything else is, word for word, the rule stated at ccal_refine_poses_batch with "frame" read as "slot" and every sum
+ * taken over all the slot's segments: rho and the corrector, the reported cost sum rho'(s_i) s_i against the judged F, the
+ * Levenberg-Marquardt rule with one state per slot, points with a coordinate that is not finite left out (NaN in their err_out
+ * row), a projection undefined at the start: CCAL_ERR_NONFINITE, the per-slot statuses and outputs, which of them may be NULL,
+ * the pure-function and bit-reproducibility statement (the order of summation is that of the slot's own segments).
+ * CCAL_NO_RESULT: fewer than max(min_points, 3) valid points OVER ALL CAMERAS of the slot (a slot seen by two cameras with two
+ * corners each has a pose at min_points = 4) or a starting pose that is not finite: pose untouched, iterations 0, n_used 0, both
+ * costs 0, every err_out row of the slot NaN.  n_slots == 0, a slot without segments and a segment without points are valid.
+ * n_cams outside 1 .. CCAL_MAX_CAMS, an unknown model, seg_cam out of range, offsets that do not start at 0 or decrease, more than
+ * 2^24 points in a slot or a NULL required pointer (model, params, extr; with n_slots > 0 seg_offsets, poses_io, status_out; seg_cam
+ * / pt_offsets when there are segments; xyz / uv when there are points): CCAL_ERR_INVALID_ARG.  An EUCMT camera:
+ * CCAL_ERR_UNSUPPORTED.  Nothing is launched or written in either case. */
+int ccal_refine_rig_poses_batch(ccal_ctx* ctx, int n_cams, const int32_t* model /* [n_cams] */,
+                                const double* params /* [n_cams][CCAL_PMAX] */,
+                                const double* extr /* [n_cams][6] rvec|tvec of T_c_0 */,
+                                double huber_delta, int n_slots, const int64_t* seg_offsets /* [n_slots + 1] */,
+                                const int32_t* seg_cam /* [n_seg] */, const int64_t* pt_offsets /* [n_seg + 1] */,
+                                const double* xyz /* [.][3] */, const double* uv /* [.][2] pixels */,
+                                int min_points, const ccal_solver_opts* opts /* NULL: defaults */,
+                                double* poses_io /* [n_slots][6] T_0_b in: start, out: result */,
+                                int32_t* status_out, int32_t* iters_out, int32_t* n_used_out,
+                                double* cost0_out, double* cost_out,      /* [n_slots] each, any may be NULL except status */
+                                double* err_out /* [n_points] pixel error at the result, or NULL */);
 
 /* ---- initialisation from detections alone (try_init_camera, src/util.rs:107-159) --------------
  * radial_distortion_homography (src/optimization/homography.rs:218-271): RANSAC over a six-point minimal solver for a
