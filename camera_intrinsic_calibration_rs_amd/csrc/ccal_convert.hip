@@ -19,16 +19,6 @@
 #include "ccal_internal.hpp"
 #include "ccal_model_inverse.hpp"
 
-#define HIP_TRY(ctx, expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
-            return CCAL_ERR_HIP;                                                                   \
-        }                                                                                          \
-    } while (0)
-#define HIP_TRYN(ctx, expr) HIP_TRY(ctx, expr)      /* inside lambdas returning int */
-
 namespace ccal {
 
 constexpr int CONV_REC = 6;          // x, y, z, u0, v0, state (0 dropped, 1 both projections defined so far, 2 source undefined)
@@ -210,16 +200,16 @@ extern "C" int ccal_convert_model(ccal_ctx* ctx, int src_model, const double* sr
 
     double out[64];
     auto eval = [&](const double* t) -> int {
-        HIP_TRYN(ctx, hipMemcpyAsync(d_buf + 10, t, sizeof(double) * P, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_buf + 10, t, sizeof(double) * P, hipMemcpyHostToDevice, st));
         switch (tgt_model) {
             case kUCM: hipLaunchKernelGGL(k_convert_gram<kUCM>, dim3(1), dim3(256), 0, st, a); break;
             case kEUCM: hipLaunchKernelGGL(k_convert_gram<kEUCM>, dim3(1), dim3(256), 0, st, a); break;
             case kKB4: hipLaunchKernelGGL(k_convert_gram<kKB4>, dim3(1), dim3(256), 0, st, a); break;
             default: hipLaunchKernelGGL(k_convert_gram<kOCV5>, dim3(1), dim3(256), 0, st, a); break;
         }
-        HIP_TRYN(ctx, hipGetLastError());
-        HIP_TRYN(ctx, hipMemcpyAsync(out, d_buf + 20, sizeof(double) * NA, hipMemcpyDeviceToHost, st));
-        HIP_TRYN(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(out, d_buf + 20, sizeof(double) * NA, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
         return 0;
     };
     if (eval(th) != 0) return CCAL_ERR_HIP;

@@ -7,19 +7,12 @@
 #include <cstring>
 #include <vector>
 
-#include "ccal_internal.hpp"
+#include "ccal_call.hpp"
 #include "ccal_rdh.hpp"
 
 using namespace ccal;
 
 namespace {
-
-int fail(ccal_ctx* ctx, int code, const char* msg) { note_error(ctx, msg); return code; }
-int hip_fail(ccal_ctx* ctx, const char* where, hipError_t e) {
-    try { ctx->err = std::string(where) + ": " + hipGetErrorString(e); } catch (...) { }
-    return CCAL_ERR_HIP;
-}
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // one of the two focal estimates of homography_to_focal: the larger of (va, vb) first; both positive: the one whose
 // denominator of the ORIGINAL order is larger in magnitude selects first / second (homography.rs:291-301, 309-319)
@@ -71,48 +64,41 @@ int ccal_rdh_batch(ccal_ctx* ctx, int n_prob, const int64_t* pair_offsets, const
     const int n_blocks = (n_hyp + 63) / 64;
     if (nh > ((size_t)1 << 28)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_rdh_batch: n_prob * n_hyp too large");
     CCAL_API_TRY
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
     // one block: inputs | workgroup records | results | per-hypothesis results (doubles first, then the 32-bit arrays)
-    const size_t b_off = up256((np + 1) * 8), b_seed = up256(np * 8), b_pairs = up256(n_tot * 32), b_part = up256(np * (size_t)n_blocks * sizeof(RdhPartial));
-    const size_t b_out = up256(np * 11 * 8), b_hl = hyp_lambda ? up256(nh * 8) : 0, b_hH = hyp_H ? up256(nh * 72) : 0, b_hs = hyp_score ? up256(nh * 8) : 0;
-    const size_t b_oi = up256(np * 8), b_hsamp = hyp_sample ? up256(nh * 24) : 0;
-    char* d = nullptr;
-    e = ctx_dev_alloc(ctx, (void**)&d, b_off + b_seed + b_pairs + b_part + b_out + b_hl + b_hH + b_hs + b_oi + b_hsamp);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_rdh_batch: allocation", e);
-    struct Guard { ccal_ctx* c; char* p; ~Guard() { (void)hipStreamSynchronize(c->stream); ctx_release(c, p, false); } } guard{ ctx, d };
-    char* q = d;
-    int64_t* d_off = (int64_t*)q; q += b_off;
-    uint64_t* d_seed = (uint64_t*)q; q += b_seed;
-    double* d_pairs = (double*)q; q += b_pairs;
+    CallBlock blk(ctx);
+    const auto s_off = blk.add<int64_t>(np + 1);
+    const auto s_seed = blk.add<uint64_t>(np);
+    const auto s_pairs = blk.add<double>(n_tot * 4);
+    const auto s_part = blk.add<RdhPartial>(np * (size_t)n_blocks);
+    const auto s_out = blk.add<double>(np * 11);                         // lambda | score | H
+    const auto s_hl = blk.add<double>(hyp_lambda ? nh : 0);
+    const auto s_hH = blk.add<double>(hyp_H ? nh * 9 : 0);
+    const auto s_hs = blk.add<double>(hyp_score ? nh : 0);
+    const auto s_oi = blk.add<int32_t>(np * 2);                          // best index | valid hypotheses
+    const auto s_hsamp = blk.add<int32_t>(hyp_sample ? nh * 6 : 0);
+    if (!blk.alloc()) return blk.finish("ccal_rdh_batch");
     RdhArgs a = {};
-    a.part = (RdhPartial*)q; q += b_part;
-    char* d_res = q;
-    a.out_lambda = (double*)q; a.out_score = a.out_lambda + np; a.out_H = a.out_score + np; q += b_out;
-    a.h_lambda = hyp_lambda ? (double*)q : nullptr; q += b_hl;
-    a.h_H = hyp_H ? (double*)q : nullptr; q += b_hH;
-    a.h_score = hyp_score ? (double*)q : nullptr; q += b_hs;
-    a.out_idx = (int32_t*)q; a.out_nvalid = a.out_idx + np; q += b_oi;
-    a.h_sample = hyp_sample ? (int32_t*)q : nullptr; q += b_hsamp;
-    a.pair_off = d_off; a.seeds = d_seed; a.pairs = d_pairs; a.n_hyp = n_hyp; a.n_blocks = n_blocks;
-    hipStream_t s = ctx->stream;
-    e = test_poison_f64(ctx, d_res, b_out + b_hl + b_hH + b_hs, false, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, pair_offsets, (np + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_seed, seeds, np * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pairs, pairs, n_tot * 32, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = launch_rdh(a, n_prob, (int)max_pairs, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(lambda_out, a.out_lambda, np * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(score_out, a.out_score, np * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(H_out, a.out_H, np * 72, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(best_idx_out, a.out_idx, np * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_valid_out, a.out_nvalid, np * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && hyp_lambda) e = hipMemcpyAsync(hyp_lambda, a.h_lambda, nh * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && hyp_H) e = hipMemcpyAsync(hyp_H, a.h_H, nh * 72, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && hyp_score) e = hipMemcpyAsync(hyp_score, a.h_score, nh * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && hyp_sample) e = hipMemcpyAsync(hyp_sample, a.h_sample, nh * 24, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_rdh_batch", e);
-    return CCAL_OK;
+    a.pair_off = blk.at(s_off); a.seeds = blk.at(s_seed); a.pairs = blk.at(s_pairs); a.part = blk.at(s_part);
+    a.out_lambda = blk.at(s_out); a.out_score = a.out_lambda + np; a.out_H = a.out_score + np;
+    a.h_lambda = blk.at(s_hl); a.h_H = blk.at(s_hH); a.h_score = blk.at(s_hs);
+    a.out_idx = blk.at(s_oi); a.out_nvalid = a.out_idx + np;
+    a.h_sample = blk.at(s_hsamp);
+    a.n_hyp = n_hyp; a.n_blocks = n_blocks;
+    blk.poison(s_out, s_hs);
+    blk.upload(s_off, pair_offsets, np + 1);
+    blk.upload(s_seed, seeds, np);
+    blk.upload(s_pairs, pairs, n_tot * 4);
+    if (blk.ok()) blk.note(launch_rdh(a, n_prob, (int)max_pairs, ctx->stream));
+    blk.download(lambda_out, a.out_lambda, np);
+    blk.download(score_out, a.out_score, np);
+    blk.download(H_out, a.out_H, np * 9);
+    blk.download(best_idx_out, a.out_idx, np);
+    blk.download(n_valid_out, a.out_nvalid, np);
+    blk.download(hyp_lambda, a.h_lambda, nh);
+    blk.download(hyp_H, a.h_H, nh * 9);
+    blk.download(hyp_score, a.h_score, nh);
+    blk.download(hyp_sample, a.h_sample, nh * 6);
+    return blk.finish("ccal_rdh_batch");
     CCAL_API_CATCH(ctx)
 }
 
@@ -132,25 +118,17 @@ int ccal_init_poses_division(ccal_problem* p, double lambda, int min_points, dou
     ccal_ctx* ctx = p->ctx;
     if (!(lambda == lambda)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_init_poses_division: lambda is NaN");
     CCAL_API_TRY
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
-    const size_t no = (size_t)std::max(p->n_obs, 1);
-    const size_t b_po = up256(no * 6 * sizeof(double)), b_va = up256(no * sizeof(int32_t));
-    char* d = nullptr;
-    e = ctx_dev_alloc(ctx, (void**)&d, b_po + b_va);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_init_poses_division: allocation", e);
-    struct Guard { ccal_ctx* c; char* p; ~Guard() { (void)hipStreamSynchronize(c->stream); ctx_release(c, p, false); } } guard{ ctx, d };
-    double* d_po = (double*)d; int32_t* d_va = (int32_t*)(d + b_po);
-    e = test_poison_f64(ctx, d_po, b_po, false, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_va, 0, no * sizeof(int32_t), ctx->stream);
-    for (int c = 0; c < p->n_cams && e == hipSuccess; ++c) e = launch_pose_init_division(p, c, lambda, d_po, d_va, min_points, ctx->stream);
-    if (e == hipSuccess && p->n_obs) {
-        e = hipMemcpyAsync(poses_obs, d_po, (size_t)p->n_obs * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(n_used, d_va, (size_t)p->n_obs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_init_poses_division", e);
-    return CCAL_OK;
+    const size_t no = (size_t)std::max(p->n_obs, 1), n_obs = (size_t)p->n_obs;
+    CallBlock blk(ctx);
+    const auto s_po = blk.add<double>(no * 6);
+    const auto s_va = blk.add<int32_t>(no);
+    if (!blk.alloc()) return blk.finish("ccal_init_poses_division");
+    blk.poison(s_po, s_po);
+    blk.memset(s_va, 0, no);
+    for (int c = 0; c < p->n_cams && blk.ok(); ++c) blk.note(launch_pose_init_division(p, c, lambda, blk.at(s_po), blk.at(s_va), min_points, ctx->stream));
+    blk.download(poses_obs, blk.at(s_po), n_obs * 6);
+    blk.download(n_used, blk.at(s_va), n_obs);
+    return blk.finish("ccal_init_poses_division");
     CCAL_API_CATCH(ctx)
 }
 
@@ -168,32 +146,25 @@ int ccal_pnp_batch(ccal_ctx* ctx, int n_prob, const int64_t* offsets, const doub
     const size_t n_tot = (size_t)offsets[n_prob], np = (size_t)n_prob;
     if (n_tot && (!xyz || !xn)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: NULL argument");
     CCAL_API_TRY
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
     // one block: offsets | points | image points | poses, costs | counts
-    const size_t b_off = up256((np + 1) * 8), b_xyz = up256((n_tot + 1) * 24), b_xn = up256((n_tot + 1) * 16), b_res = up256(np * 7 * 8), b_nu = up256(np * 4);
-    char* d = nullptr;
-    e = ctx_dev_alloc(ctx, (void**)&d, b_off + b_xyz + b_xn + b_res + b_nu);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_pnp_batch: allocation", e);
-    struct Guard { ccal_ctx* c; char* p; ~Guard() { (void)hipStreamSynchronize(c->stream); ctx_release(c, p, false); } } guard{ ctx, d };
-    int64_t* d_off = (int64_t*)d;
-    double* d_xyz = (double*)(d + b_off);
-    double* d_xn = (double*)(d + b_off + b_xyz);
-    double* d_po = (double*)(d + b_off + b_xyz + b_xn);
+    CallBlock blk(ctx);
+    const auto s_off = blk.add<int64_t>(np + 1);
+    const auto s_xyz = blk.add<double>((n_tot + 1) * 3);
+    const auto s_xn = blk.add<double>((n_tot + 1) * 2);
+    const auto s_res = blk.add<double>(np * 7);                          // poses | cost
+    const auto s_nu = blk.add<int32_t>(np);
+    if (!blk.alloc()) return blk.finish("ccal_pnp_batch");
+    double* d_po = blk.at(s_res);
     double* d_cost = d_po + np * 6;
-    int32_t* d_nu = (int32_t*)(d + b_off + b_xyz + b_xn + b_res);
-    hipStream_t s = ctx->stream;
-    e = test_poison_f64(ctx, d_po, b_res, false, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, (np + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_xyz, xyz, n_tot * 24, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_xn, xn, n_tot * 16, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = launch_pnp_batch(n_prob, d_off, d_xyz, d_xn, min_points, d_po, d_nu, d_cost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(poses_out, d_po, np * 6 * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_used_out, d_nu, np * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && cost_out) e = hipMemcpyAsync(cost_out, d_cost, np * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_pnp_batch", e);
-    return CCAL_OK;
+    blk.poison(s_res, s_res);
+    blk.upload(s_off, offsets, np + 1);
+    blk.upload(s_xyz, xyz, n_tot * 3);
+    blk.upload(s_xn, xn, n_tot * 2);
+    if (blk.ok()) blk.note(launch_pnp_batch(n_prob, blk.at(s_off), blk.at(s_xyz), blk.at(s_xn), min_points, d_po, blk.at(s_nu), d_cost, ctx->stream));
+    blk.download(poses_out, d_po, np * 6);
+    blk.download(n_used_out, blk.at(s_nu), np);
+    blk.download(cost_out, d_cost, np);
+    return blk.finish("ccal_pnp_batch");
     CCAL_API_CATCH(ctx)
 }
 

@@ -241,12 +241,51 @@ struct ccal_problem {
     catch (const std::exception& e_) { ccal::note_error((ctx_expr), e_.what()); return CCAL_ERR_HIP; }                \
     catch (...) { ccal::note_error((ctx_expr), "unknown C++ exception"); return CCAL_ERR_HIP; }
 
+// A HIP call of a function that returns a ccal_status: on failure the context's message is "<the call>: <HIP's text>" and the
+// function returns CCAL_ERR_HIP.
+#define HIP_TRY(ctx, expr)                                                                         \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
+            return CCAL_ERR_HIP;                                                                   \
+        }                                                                                          \
+    } while (0)
+
 namespace ccal {
 inline void note_error(ccal_ctx* ctx, const char* msg) noexcept {
     if (!ctx) return;
     try { ctx->err = msg; } catch (...) { }
 }
 inline void note_error(const ccal_ctx*, const char*) noexcept {}
+// model id check shared by the entry points that take one camera model (or one per camera): CCAL_OK, or the status with the message set
+inline int check_model(ccal_ctx* ctx, int model, const char* where) {
+    const bool eucmt = model == CCAL_MODEL_EUCMT;
+    if (!eucmt && model >= 0 && model < kNumModels) return CCAL_OK;
+    try {
+        ctx->err = std::string(where) + (eucmt ? ": EUCMT is a parameter container in this build (its projection is only in the absent camera-intrinsic-model crate)"
+                                               : ": unknown camera model");
+    } catch (...) { }
+    return eucmt ? CCAL_ERR_UNSUPPORTED : CCAL_ERR_INVALID_ARG;
+}
+// caller's params() vector -> th[CCAL_PMAX] in the kernels' canonical order (OPENCV5: k1, k2, p1, p2, k3, permuted here from
+// ccal_model_conventions.ocv5_order; the rest 0) and the conventions of kernels that take their parameters that way
+inline void canonical_theta(const ccal_ctx* ctx, int model, const double* params, double* th, ModelRt* rt) {
+    for (int i = 0; i < CCAL_PMAX; ++i) th[i] = 0.0;
+    for (int i = 0; i < model_np(model); ++i) th[i] = params[(model == kOCV5 && i >= 4) ? 4 + ctx->conv.ocv5_order[i - 4] : i];
+    *rt = model_rt(ctx);
+    rt->ocv5_perm = kOcv5IdentityPerm;
+}
+// the host's switch on a (checked) model id: Launch<MODEL>::go(grid, stream, args) launches the kernel's instance
+template <template <int> class Launch, class Args>
+void launch_model(int model, int grid, hipStream_t st, const Args& a) {
+    switch (model) {
+        case kUCM: Launch<kUCM>::go(grid, st, a); break;
+        case kEUCM: Launch<kEUCM>::go(grid, st, a); break;
+        case kKB4: Launch<kKB4>::go(grid, st, a); break;
+        default: Launch<kOCV5>::go(grid, st, a); break;
+    }
+}
 // kernel launchers (ccal_kernels.hip)
 hipError_t launch_eval(const ccal_problem* p, int cam, const KArgs& a, hipStream_t s);
 hipError_t launch_reproj_err(const ccal_problem* p, int cam, const KArgs& a, hipStream_t s);

@@ -18,8 +18,7 @@
 // residual is NaN and so is the cost, as in the joint solve - CCAL_ERR_NONFINITE at the start, a rejected step at a trial pose.
 #include <algorithm>
 #include <cmath>
-#include <string>
-
+#include "ccal_call.hpp"
 #include "ccal_refine.hpp"
 
 namespace ccal {
@@ -86,27 +85,11 @@ __global__ __launch_bounds__(256) void k_pose_refine(const RefineArgs a) {
     }
 }
 
-template <int MODEL>
-static hipError_t launch_refine(const RefineArgs& a, hipStream_t s) {
-    const int blocks = (a.rule.n_prob + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pose_refine<MODEL>, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
+template <int M> struct LaunchRefine { static void go(int g, hipStream_t st, const RefineArgs& a) { hipLaunchKernelGGL(k_pose_refine<M>, dim3(g), dim3(256), 0, st, a); } };
 
 }  // namespace ccal
 
 using namespace ccal;
-
-namespace {
-
-int fail(ccal_ctx* ctx, int code, const char* msg) { note_error(ctx, msg); return code; }
-int hip_fail(ccal_ctx* ctx, const char* where, hipError_t e) {
-    try { ctx->err = std::string(where) + ": " + hipGetErrorString(e); } catch (...) { }
-    return CCAL_ERR_HIP;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -115,9 +98,8 @@ int ccal_refine_poses_batch(ccal_ctx* ctx, int model, const double* params, doub
                             int32_t* status_out, int32_t* iters_out, int32_t* n_used_out, double* cost0_out, double* cost_out,
                             double* err_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
-    if (model == CCAL_MODEL_EUCMT)
-        return fail(ctx, CCAL_ERR_UNSUPPORTED, "ccal_refine_poses_batch: EUCMT is a parameter container in this build (its projection is only in the absent camera-intrinsic-model crate)");
-    if (model < 0 || model >= kNumModels) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: unknown camera model");
+    const int rc = check_model(ctx, model, "ccal_refine_poses_batch");
+    if (rc != CCAL_OK) return rc;
     if (n_prob < 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: n_prob < 0");
     if (!params) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: NULL argument");
     if (n_prob == 0) return CCAL_OK;
@@ -132,53 +114,38 @@ int ccal_refine_poses_batch(ccal_ctx* ctx, int model, const double* params, doub
     ccal_solver_opts o;
     if (opts) o = *opts; else ccal_set_defaults(&o);
     CCAL_API_TRY
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
     // one block: offsets | points | image points | poses, cost0, cost | errors | status, iterations, counts
-    const size_t b_off = refine_up256((np + 1) * 8), b_xyz = refine_up256((n_tot + 1) * 24), b_uv = refine_up256((n_tot + 1) * 16), b_res = refine_up256(np * 8 * 8);
-    const size_t b_err = err_out ? refine_up256((n_tot + 1) * 8) : 0, b_int = refine_up256(np * 3 * 4);
-    char* d = nullptr;
-    e = ctx_dev_alloc(ctx, (void**)&d, b_off + b_xyz + b_uv + b_res + b_err + b_int);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_refine_poses_batch: allocation", e);
-    struct Guard { ccal_ctx* c; char* p; ~Guard() { (void)hipStreamSynchronize(c->stream); ctx_release(c, p, false); } } guard{ ctx, d };
+    CallBlock blk(ctx);
+    const auto s_off = blk.add<int64_t>(np + 1);
+    const auto s_xyz = blk.add<double>((n_tot + 1) * 3);
+    const auto s_uv = blk.add<double>((n_tot + 1) * 2);
+    const auto s_res = blk.add<double>(np * 8);
+    const auto s_err = blk.add<double>(err_out ? n_tot + 1 : 0);
+    const auto s_int = blk.add<int32_t>(np * 3);
+    if (!blk.alloc()) return blk.finish("ccal_refine_poses_batch");
     RefineArgs a = {};
-    for (int i = 0; i < model_np(model); ++i) a.th[i] = params[(model == kOCV5 && i >= 4) ? 4 + ctx->conv.ocv5_order[i - 4] : i];
-    a.rt = model_rt(ctx);
-    a.rt.ocv5_perm = kOcv5IdentityPerm;
-    int64_t* d_off = (int64_t*)d;
-    double* d_xyz = (double*)(d + b_off);
-    double* d_uv = (double*)(d + b_off + b_xyz);
-    double* d_po = (double*)(d + b_off + b_xyz + b_uv);
-    double* d_err = err_out ? (double*)(d + b_off + b_xyz + b_uv + b_res) : nullptr;
-    int32_t* d_int = (int32_t*)(d + b_off + b_xyz + b_uv + b_res + b_err);
-    a.off = d_off; a.xyz = d_xyz; a.uv = d_uv;
-    a.poses = d_po; a.cost0 = d_po + np * 6; a.cost = d_po + np * 7; a.err = d_err;
-    a.status = d_int; a.iters = d_int + np; a.n_used = d_int + 2 * np;
+    canonical_theta(ctx, model, params, a.th, &a.rt);
+    a.off = blk.at(s_off); a.xyz = blk.at(s_xyz); a.uv = blk.at(s_uv);
+    a.poses = blk.at(s_res); a.cost0 = a.poses + np * 6; a.cost = a.poses + np * 7; a.err = blk.at(s_err);
+    a.status = blk.at(s_int); a.iters = a.status + np; a.n_used = a.status + 2 * np;
     a.rule = refine_rule(huber_delta, o, n_prob, min_points);
-    hipStream_t s = ctx->stream;
-    e = test_poison_f64(ctx, d_xyz, b_xyz + b_uv + b_res + b_err, false, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, (np + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_xyz, xyz, n_tot * 24, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_uv, uv, n_tot * 16, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_po, poses_io, np * 6 * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        switch (model) {
-            case kUCM: e = launch_refine<kUCM>(a, s); break;
-            case kEUCM: e = launch_refine<kEUCM>(a, s); break;
-            case kKB4: e = launch_refine<kKB4>(a, s); break;
-            default: e = launch_refine<kOCV5>(a, s); break;
-        }
+    blk.poison(s_xyz, s_err);
+    blk.upload(s_off, offsets, np + 1);
+    blk.upload(s_xyz, xyz, n_tot * 3);
+    blk.upload(s_uv, uv, n_tot * 2);
+    blk.upload(s_res, poses_io, np * 6);
+    if (blk.ok()) {
+        launch_model<LaunchRefine>(model, (n_prob + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, ctx->stream, a);
+        blk.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(poses_io, d_po, np * 6 * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(status_out, a.status, np * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && iters_out) e = hipMemcpyAsync(iters_out, a.iters, np * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && n_used_out) e = hipMemcpyAsync(n_used_out, a.n_used, np * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && cost0_out) e = hipMemcpyAsync(cost0_out, a.cost0, np * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && cost_out) e = hipMemcpyAsync(cost_out, a.cost, np * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && err_out && n_tot) e = hipMemcpyAsync(err_out, d_err, n_tot * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_refine_poses_batch", e);
-    return CCAL_OK;
+    blk.download(poses_io, a.poses, np * 6);
+    blk.download(status_out, a.status, np);
+    blk.download(iters_out, a.iters, np);
+    blk.download(n_used_out, a.n_used, np);
+    blk.download(cost0_out, a.cost0, np);
+    blk.download(cost_out, a.cost, np);
+    blk.download(err_out, a.err, n_tot);
+    return blk.finish("ccal_refine_poses_batch");
     CCAL_API_CATCH(ctx)
 }
 

@@ -15,8 +15,7 @@
 //   result does not depend on the batch around it.  No atomics, no LDS.
 // A segment shorter than 64 corners leaves lanes idle in its pass; two short segments are NOT packed into one pass (the lanes of a
 // pass would then run two model bodies one after the other under exec masks - DESIGN.md).
-#include <string>
-
+#include "ccal_call.hpp"
 #include "ccal_refine.hpp"
 
 namespace ccal {
@@ -114,16 +113,6 @@ __global__ __launch_bounds__(256) void k_rig_pose_refine(const RigRefineArgs a) 
 
 using namespace ccal;
 
-namespace {
-
-int fail(ccal_ctx* ctx, int code, const char* msg) { note_error(ctx, msg); return code; }
-int hip_fail(ccal_ctx* ctx, const char* where, hipError_t e) {
-    try { ctx->err = std::string(where) + ": " + hipGetErrorString(e); } catch (...) { }
-    return CCAL_ERR_HIP;
-}
-
-}  // namespace
-
 extern "C" {
 
 int ccal_refine_rig_poses_batch(ccal_ctx* ctx, int n_cams, const int32_t* model, const double* params, const double* extr,
@@ -134,12 +123,11 @@ int ccal_refine_rig_poses_batch(ccal_ctx* ctx, int n_cams, const int32_t* model,
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     if (n_cams < 1 || n_cams > CCAL_MAX_CAMS) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: n_cams outside 1 .. CCAL_MAX_CAMS");
     if (!model || !params || !extr) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: NULL argument");
-    for (int c = 0; c < n_cams; ++c)
-        if (model[c] != CCAL_MODEL_EUCMT && (model[c] < 0 || model[c] >= kNumModels))
-            return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: unknown camera model");
-    for (int c = 0; c < n_cams; ++c)
-        if (model[c] == CCAL_MODEL_EUCMT)
-            return fail(ctx, CCAL_ERR_UNSUPPORTED, "ccal_refine_rig_poses_batch: EUCMT is a parameter container in this build (its projection is only in the absent camera-intrinsic-model crate)");
+    for (int pass = 0; pass < 2; ++pass)          // an unknown id of any camera is reported ahead of EUCMT
+        for (int c = 0; c < n_cams; ++c) {
+            const int rc = pass || model[c] != CCAL_MODEL_EUCMT ? check_model(ctx, model[c], "ccal_refine_rig_poses_batch") : CCAL_OK;
+            if (rc != CCAL_OK) return rc;
+        }
     if (n_slots < 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: n_slots < 0");
     if (n_slots == 0) return CCAL_OK;
     if (!seg_offsets || !poses_io || !status_out) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: NULL argument");
@@ -161,61 +149,47 @@ int ccal_refine_rig_poses_batch(ccal_ctx* ctx, int n_cams, const int32_t* model,
     ccal_solver_opts o;
     if (opts) o = *opts; else ccal_set_defaults(&o);
     CCAL_API_TRY
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, "hipSetDevice", e);
     // one block: segment offsets | point offsets | segment cameras | points | image points | poses, cost0, cost | errors |
     // status, iterations, counts
-    const size_t b_sof = refine_up256((ns + 1) * 8), b_pof = refine_up256((n_seg + 1) * 8), b_cam = refine_up256((n_seg + 1) * 4);
-    const size_t b_xyz = refine_up256((n_tot + 1) * 24), b_uv = refine_up256((n_tot + 1) * 16), b_res = refine_up256(ns * 8 * 8);
-    const size_t b_err = err_out ? refine_up256((n_tot + 1) * 8) : 0, b_int = refine_up256(ns * 3 * 4);
-    char* d = nullptr;
-    e = ctx_dev_alloc(ctx, (void**)&d, b_sof + b_pof + b_cam + b_xyz + b_uv + b_res + b_err + b_int);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_refine_rig_poses_batch: allocation", e);
-    struct Guard { ccal_ctx* c; char* p; ~Guard() { (void)hipStreamSynchronize(c->stream); ctx_release(c, p, false); } } guard{ ctx, d };
+    CallBlock blk(ctx);
+    const auto s_sof = blk.add<int64_t>(ns + 1);
+    const auto s_pof = blk.add<int64_t>(n_seg + 1);
+    const auto s_cam = blk.add<int32_t>(n_seg + 1);
+    const auto s_xyz = blk.add<double>((n_tot + 1) * 3);
+    const auto s_uv = blk.add<double>((n_tot + 1) * 2);
+    const auto s_res = blk.add<double>(ns * 8);
+    const auto s_err = blk.add<double>(err_out ? n_tot + 1 : 0);
+    const auto s_int = blk.add<int32_t>(ns * 3);
+    if (!blk.alloc()) return blk.finish("ccal_refine_rig_poses_batch");
     RigRefineArgs a = {};
     for (int c = 0; c < n_cams; ++c) {
-        const double* pc = params + (size_t)c * CCAL_PMAX;
-        for (int i = 0; i < model_np(model[c]); ++i) a.th[c][i] = pc[(model[c] == kOCV5 && i >= 4) ? 4 + ctx->conv.ocv5_order[i - 4] : i];
+        canonical_theta(ctx, model[c], params + (size_t)c * CCAL_PMAX, a.th[c], &a.rt);
         for (int i = 0; i < 6; ++i) a.extr[c][i] = extr[(size_t)c * 6 + i];
         a.model[c] = model[c];
     }
-    a.rt = model_rt(ctx);
-    a.rt.ocv5_perm = kOcv5IdentityPerm;
-    int64_t* d_sof = (int64_t*)d;
-    int64_t* d_pof = (int64_t*)(d + b_sof);
-    int32_t* d_cam = (int32_t*)(d + b_sof + b_pof);
-    char* dd = d + b_sof + b_pof + b_cam;            // the blocks of doubles
-    double* d_xyz = (double*)dd;
-    double* d_uv = (double*)(dd + b_xyz);
-    double* d_po = (double*)(dd + b_xyz + b_uv);
-    double* d_err = err_out ? (double*)(dd + b_xyz + b_uv + b_res) : nullptr;
-    int32_t* d_int = (int32_t*)(dd + b_xyz + b_uv + b_res + b_err);
-    a.seg_off = d_sof; a.pt_off = d_pof; a.seg_cam = d_cam; a.xyz = d_xyz; a.uv = d_uv;
-    a.poses = d_po; a.cost0 = d_po + ns * 6; a.cost = d_po + ns * 7; a.err = d_err;
-    a.status = d_int; a.iters = d_int + ns; a.n_used = d_int + 2 * ns;
+    a.seg_off = blk.at(s_sof); a.pt_off = blk.at(s_pof); a.seg_cam = blk.at(s_cam); a.xyz = blk.at(s_xyz); a.uv = blk.at(s_uv);
+    a.poses = blk.at(s_res); a.cost0 = a.poses + ns * 6; a.cost = a.poses + ns * 7; a.err = blk.at(s_err);
+    a.status = blk.at(s_int); a.iters = a.status + ns; a.n_used = a.status + 2 * ns;
     a.rule = refine_rule(huber_delta, o, n_slots, min_points);
-    hipStream_t s = ctx->stream;
-    e = test_poison_f64(ctx, d_xyz, b_xyz + b_uv + b_res + b_err, false, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sof, seg_offsets, (ns + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_seg) e = hipMemcpyAsync(d_pof, pt_offsets, (n_seg + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_seg) e = hipMemcpyAsync(d_cam, seg_cam, n_seg * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_xyz, xyz, n_tot * 24, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_tot) e = hipMemcpyAsync(d_uv, uv, n_tot * 16, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_po, poses_io, ns * 6 * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_rig_pose_refine, dim3((n_slots + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0, s, a);
-        e = hipGetLastError();
+    blk.poison(s_xyz, s_err);
+    blk.upload(s_sof, seg_offsets, ns + 1);
+    blk.upload(s_pof, pt_offsets, n_seg ? n_seg + 1 : 0);
+    blk.upload(s_cam, seg_cam, n_seg);
+    blk.upload(s_xyz, xyz, n_tot * 3);
+    blk.upload(s_uv, uv, n_tot * 2);
+    blk.upload(s_res, poses_io, ns * 6);
+    if (blk.ok()) {
+        hipLaunchKernelGGL(k_rig_pose_refine, dim3((n_slots + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0, ctx->stream, a);
+        blk.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(poses_io, d_po, ns * 6 * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(status_out, a.status, ns * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && iters_out) e = hipMemcpyAsync(iters_out, a.iters, ns * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && n_used_out) e = hipMemcpyAsync(n_used_out, a.n_used, ns * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && cost0_out) e = hipMemcpyAsync(cost0_out, a.cost0, ns * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && cost_out) e = hipMemcpyAsync(cost_out, a.cost, ns * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && err_out && n_tot) e = hipMemcpyAsync(err_out, d_err, n_tot * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(ctx, "ccal_refine_rig_poses_batch", e);
-    return CCAL_OK;
+    blk.download(poses_io, a.poses, ns * 6);
+    blk.download(status_out, a.status, ns);
+    blk.download(iters_out, a.iters, ns);
+    blk.download(n_used_out, a.n_used, ns);
+    blk.download(cost0_out, a.cost0, ns);
+    blk.download(cost_out, a.cost, ns);
+    blk.download(err_out, a.err, n_tot);
+    return blk.finish("ccal_refine_rig_poses_batch");
     CCAL_API_CATCH(ctx)
 }
 

@@ -6,7 +6,7 @@
 // 128-bit FIXED POINT (2^-80 px): integer addition is associative, so the result does not depend on the order of the values at all
 // (what the sort used to guarantee) - the same bits on one GPU and over the shards of several, whatever the frame order.  Hand-written: the
 // header-only library sort this replaced (hipCUB radix sort) was 5 MB of the 13 MB library for this one small step.
-#include "ccal_internal.hpp"
+#include "ccal_call.hpp"
 
 namespace ccal {
 
@@ -47,7 +47,7 @@ __device__ __forceinline__ double from_fixed(const u128 f) {
     const double hi = (double)(unsigned long long)(f >> 64), lo = (double)(unsigned long long)f;
     return (hi * 18446744073709551616.0 + lo) * 8.271806125530277e-25;          // x 2^-80
 }
-size_t order_stats_work_bytes() { return (sizeof(SelWork) + 255) & ~(size_t)255; }
+size_t order_stats_work_bytes() { return CallPlan::up256(sizeof(SelWork)); }
 
 // What the histogram of pass p - 1 says about both targets: every workgroup derives it for itself (the same counts: the same
 // answer), workgroup 0 leaves it for the next launch.  state[p] = state at the ENTRY of pass p.  Wavefront t of the workgroup takes
@@ -282,7 +282,6 @@ static hipError_t ensure_scratch(ccal_problem* p, size_t total, size_t f64_off, 
     if (e == hipSuccess) return test_poison_f64(p->ctx, p->d_scratch + f64_off, f64_bytes, false, p->ctx->stream);
     return e;
 }
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // One camera's errors out of the per-corner errors of the whole problem (device), packed in observation-frame order into the
 // problem's scratch block [offsets | values | room for the statistics' work area] (*d_out: the values, valid until the next call
@@ -296,7 +295,7 @@ static hipError_t gather_camera_errors(ccal_problem* p, int cam, const double* d
     for (int i = 0; i < n_list; ++i) dst[i + 1] = dst[i] + (p->h_obs_off[cl.obs[i] + 1] - p->h_obs_off[cl.obs[i]]);
     const int64_t n = dst[n_list];
     if (n <= 0) return hipSuccess;
-    const size_t b_off = up256((size_t)(n_list + 1) * sizeof(int64_t)), b_val = up256((size_t)n * sizeof(double));
+    const size_t b_off = CallPlan::up256((size_t)(n_list + 1) * sizeof(int64_t)), b_val = CallPlan::up256((size_t)n * sizeof(double));
     hipError_t e = ensure_scratch(p, b_off + b_val + order_stats_work_bytes(), b_off, b_val);
     if (e != hipSuccess) return e;
     int64_t* d_dst = reinterpret_cast<int64_t*>(p->d_scratch);
@@ -324,15 +323,15 @@ hipError_t validation_stats_device(ccal_problem* p, int cam, const double* d_err
     hipError_t e = gather_camera_errors(p, cam, d_err, &d_a, &n, s, dst, false);
     if (e != hipSuccess) return e;
     if (n <= 0) return hipErrorInvalidValue;
-    char* work = reinterpret_cast<char*>(d_a) + up256((size_t)n * sizeof(double));
+    char* work = reinterpret_cast<char*>(d_a) + CallPlan::up256((size_t)n * sizeof(double));
     return order_stats_device(d_a, n, work, avg_99, median, s);
 }
 
 // the multi-GPU form: block = [values (n) | work area], sized by order_stats_block_bytes and kept by the caller between calls
-size_t order_stats_block_bytes(int64_t n, hipStream_t) { return n <= 0 ? 0 : up256((size_t)n * sizeof(double)) + order_stats_work_bytes(); }
+size_t order_stats_block_bytes(int64_t n, hipStream_t) { return n <= 0 ? 0 : CallPlan::up256((size_t)n * sizeof(double)) + order_stats_work_bytes(); }
 hipError_t order_stats_block(char* block, size_t block_bytes, int64_t n, double* avg_99, double* median, hipStream_t s) {
     if (n <= 0 || !block || order_stats_block_bytes(n, s) > block_bytes) return hipErrorInvalidValue;
-    return order_stats_device(reinterpret_cast<const double*>(block), n, block + up256((size_t)n * sizeof(double)), avg_99, median, s);
+    return order_stats_device(reinterpret_cast<const double*>(block), n, block + CallPlan::up256((size_t)n * sizeof(double)), avg_99, median, s);
 }
 
 }  // namespace ccal

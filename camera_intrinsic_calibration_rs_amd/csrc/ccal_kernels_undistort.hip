@@ -15,18 +15,9 @@
 #include <memory>
 #include <string>
 
+#include "ccal_call.hpp"
 #include "ccal_device.hpp"
-#include "ccal_internal.hpp"
 #include "ccal_model_inverse.hpp"
-
-#define HIP_TRY(ctx, expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
-            return CCAL_ERR_HIP;                                                                   \
-        }                                                                                          \
-    } while (0)
 
 struct ccal_undistort_map {
     ccal_ctx* ctx = nullptr;
@@ -225,45 +216,9 @@ namespace {
 
 inline int grid_for(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 2048); }
 
-// model id checks shared by the entry points: CCAL_OK, or the status with the context's message set
-int check_model(ccal_ctx* ctx, int model, const char* where) {
-    if (model == CCAL_MODEL_EUCMT) {
-        ctx->err = std::string(where) + ": EUCMT is a parameter container in this build (its projection is only in the absent camera-intrinsic-model crate)";
-        return CCAL_ERR_UNSUPPORTED;
-    }
-    if (model < 0 || model >= kNumModels) { ctx->err = std::string(where) + ": unknown camera model"; return CCAL_ERR_INVALID_ARG; }
-    return CCAL_OK;
-}
-
-// caller's params() vector -> the kernels' canonical order; the kernels' conventions
-void canonical_theta(const ccal_ctx* ctx, int model, const double* params, double* th, ModelRt* rt) {
-    const int P = model_np(model);
-    for (int i = 0; i < CCAL_PMAX; ++i) th[i] = 0.0;
-    for (int i = 0; i < P; ++i) th[i] = params[(model == kOCV5 && i >= 4) ? 4 + ctx->conv.ocv5_order[i - 4] : i];
-    *rt = model_rt(ctx);
-    rt->ocv5_perm = kOcv5IdentityPerm;
-}
-
-template <template <int> class Launch, class Args>
-void launch_model(int model, int grid, hipStream_t st, const Args& a) {
-    switch (model) {
-        case kUCM: Launch<kUCM>::go(grid, st, a); break;
-        case kEUCM: Launch<kEUCM>::go(grid, st, a); break;
-        case kKB4: Launch<kKB4>::go(grid, st, a); break;
-        default: Launch<kOCV5>::go(grid, st, a); break;
-    }
-}
 template <int M> struct LaunchProject { static void go(int g, hipStream_t st, const PointArgs& a) { hipLaunchKernelGGL(k_project_points<M>, dim3(g), dim3(256), 0, st, a); } };
 template <int M> struct LaunchUnproject { static void go(int g, hipStream_t st, const PointArgs& a) { hipLaunchKernelGGL(k_unproject_points<M>, dim3(g), dim3(256), 0, st, a); } };
 template <int M> struct LaunchMap { static void go(int g, hipStream_t st, const MapArgs& a) { hipLaunchKernelGGL(k_undistort_map<M>, dim3(g), dim3(256), 0, st, a); } };
-
-// a block of the context's allocator that goes back to it on every way out
-struct CtxBlock {
-    ccal_ctx* ctx; void* p = nullptr;
-    explicit CtxBlock(ccal_ctx* c) : ctx(c) {}
-    ~CtxBlock() { if (p) ctx_release(ctx, p, false); }
-    CtxBlock(const CtxBlock&) = delete; CtxBlock& operator=(const CtxBlock&) = delete;
-};
 
 // project (in_w = 3, out_w = 2) or unproject (2, 3) of n host points through one device block [in | out | valid]
 int points_call(ccal_ctx* ctx, bool project, int model, const double* params, int64_t n, const double* in, double* out, uint8_t* valid_out,
@@ -273,25 +228,24 @@ int points_call(ccal_ctx* ctx, bool project, int model, const double* params, in
     if (rc != CCAL_OK) return rc;
     if (n == 0) return CCAL_OK;
     const size_t in_w = project ? 3 : 2, out_w = project ? 2 : 3;
-    const size_t b_in = sizeof(double) * in_w * (size_t)n, b_out = sizeof(double) * out_w * (size_t)n;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    CtxBlock blk(ctx);
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, &blk.p, b_in + b_out + (size_t)n));
-    char* d = static_cast<char*>(blk.p);
-    HIP_TRY(ctx, test_poison_f64(ctx, d, b_in + b_out + (size_t)n, false, st));
+    CallBlock blk(ctx);
+    const auto s_in = blk.add<double>(in_w * (size_t)n);
+    const auto s_out = blk.add<double>(out_w * (size_t)n);
+    const auto s_valid = blk.add<uint8_t>((size_t)n);
+    if (!blk.alloc()) return blk.finish(where);
+    blk.poison(s_in, s_valid);
     PointArgs a;
     canonical_theta(ctx, model, params, a.th, &a.rt);
-    a.n = n; a.in = reinterpret_cast<const double*>(d); a.out = reinterpret_cast<double*>(d + b_in);
-    a.valid = reinterpret_cast<uint8_t*>(d + b_in + b_out);
-    HIP_TRY(ctx, hipMemcpyAsync(d, in, b_in, hipMemcpyHostToDevice, st));
-    if (project) launch_model<LaunchProject>(model, grid_for(n), st, a);
-    else launch_model<LaunchUnproject>(model, grid_for(n), st, a);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out, d + b_in, b_out, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(valid_out, d + b_in + b_out, (size_t)n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return CCAL_OK;
+    a.n = n; a.in = blk.at(s_in); a.out = blk.at(s_out); a.valid = blk.at(s_valid);
+    blk.upload(s_in, in, in_w * (size_t)n);
+    if (blk.ok()) {
+        if (project) launch_model<LaunchProject>(model, grid_for(n), ctx->stream, a);
+        else launch_model<LaunchUnproject>(model, grid_for(n), ctx->stream, a);
+        blk.launched();
+    }
+    blk.download(out, a.out, out_w * (size_t)n);
+    blk.download(valid_out, a.valid, (size_t)n);
+    return blk.finish(where);
 }
 
 int map_alloc(ccal_ctx* ctx, int32_t w, int32_t h, ccal_undistort_map** out) {
@@ -312,8 +266,8 @@ bool pix_combo_ok(int dtype, int channels) {
     return (dtype == CCAL_PIX_U8 && (channels == 1 || channels == 3)) || (dtype == CCAL_PIX_U16 && channels == 1);
 }
 
-int remap_launch(const ccal_undistort_map* map, int dtype, int channels, int src_w, int src_h, int n_img, const void* d_src, void* d_dst,
-                 hipStream_t st) {
+void remap_launch(const ccal_undistort_map* map, int dtype, int channels, int src_w, int src_h, int n_img, const void* d_src, void* d_dst,
+                  hipStream_t st) {
     RemapArgs a;
     a.xmap = map->xmap(); a.ymap = map->ymap(); a.n_pix = (int64_t)map->w * map->h;
     a.src_w = src_w; a.src_h = src_h; a.n_img = n_img; a.src = d_src; a.dst = d_dst;
@@ -328,9 +282,6 @@ int remap_launch(const ccal_undistort_map* map, int dtype, int channels, int src
     if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL((k_remap<uint16_t, 1>), grid, dim3(256), 0, st, a);
     else if (channels == 3) hipLaunchKernelGGL((k_remap<uint8_t, 3>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_remap<uint8_t, 1>), grid, dim3(256), 0, st, a);
-    ccal_ctx* ctx = map->ctx;
-    HIP_TRY(ctx, hipGetLastError());
-    return CCAL_OK;
 }
 
 int remap_check(const ccal_undistort_map* map, int dtype, int channels, int src_w, int src_h, int n_img, const void* src, void* dst) {
@@ -479,19 +430,18 @@ int ccal_remap(ccal_undistort_map* map, int dtype, int channels, int src_w, int 
     const size_t es = dtype == CCAL_PIX_U16 ? 2 : 1;
     const size_t b_src = es * (size_t)channels * (size_t)src_w * (size_t)src_h * (size_t)n_img;
     const size_t b_dst = es * (size_t)channels * (size_t)map->w * (size_t)map->h * (size_t)n_img;
-    const size_t off_dst = (b_src + 255) & ~(size_t)255;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    CtxBlock blk(ctx);
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, &blk.p, off_dst + b_dst));
-    char* d = static_cast<char*>(blk.p);
-    HIP_TRY(ctx, test_poison_f64(ctx, d, off_dst + b_dst, false, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d, src, b_src, hipMemcpyHostToDevice, st));
-    const int rc = remap_launch(map, dtype, channels, src_w, src_h, n_img, d, d + off_dst, st);
-    if (rc != CCAL_OK) { (void)hipStreamSynchronize(st); return rc; }
-    HIP_TRY(ctx, hipMemcpyAsync(dst, d + off_dst, b_dst, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return CCAL_OK;
+    CallBlock blk(ctx);
+    const auto s_src = blk.add<char>(b_src);
+    const auto s_dst = blk.add<char>(b_dst);
+    if (!blk.alloc()) return blk.finish("ccal_remap");
+    blk.poison(s_src, s_dst);
+    blk.upload(s_src, src, b_src);
+    if (blk.ok()) {
+        remap_launch(map, dtype, channels, src_w, src_h, n_img, blk.at(s_src), blk.at(s_dst), ctx->stream);
+        blk.launched();
+    }
+    blk.download(dst, blk.at(s_dst), b_dst);
+    return blk.finish("ccal_remap");
     CCAL_API_CATCH(ctx)
 }
 
@@ -502,7 +452,9 @@ int ccal_remap_dev(ccal_undistort_map* map, int dtype, int channels, int src_w, 
     const int rc0 = remap_check(map, dtype, channels, src_w, src_h, n_img, src_dev, dst_dev);
     if (rc0 != CCAL_OK) return rc0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return remap_launch(map, dtype, channels, src_w, src_h, n_img, src_dev, dst_dev, ctx->stream);
+    remap_launch(map, dtype, channels, src_w, src_h, n_img, src_dev, dst_dev, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return CCAL_OK;
     CCAL_API_CATCH(ctx)
 }
 

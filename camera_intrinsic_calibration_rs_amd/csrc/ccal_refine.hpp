@@ -221,7 +221,4 @@ __device__ __forceinline__ int refine_lm(const RefineRule& a, const bool want_er
     return done - 1;
 }
 
-// host side of both entry points
-inline size_t refine_up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace ccal
