@@ -292,6 +292,14 @@ class _Opened:
         return False
 
 
+def _points_f32(ff: FrameFeature):
+    """(ids, p3d [n, 3], p2d [n, 2]) of a frame in the order of its sorted feature ids, f64 values of the f32 numbers that the
+    reference holds detections and board points in (src/detected_points.rs:6-9)."""
+    ids = sorted(ff.features.keys())
+    return (ids, np.asarray([ff.features[k].p3d for k in ids], dtype=np.float32).astype(np.float64).reshape(-1, 3),
+            np.asarray([ff.features[k].p2d for k in ids], dtype=np.float32).astype(np.float64).reshape(-1, 2))
+
+
 def _flatten(cams_frames: Sequence[Sequence[Optional[FrameFeature]]], use: Sequence[Sequence[int]]):
     """(cam, frame index) observation frames -> CSR + SoA arrays; slots = sorted union of frame indices."""
     slots = sorted({i for idxs in use for i in idxs})
@@ -592,6 +600,11 @@ def validation(cam_idx: int, final_result: GenericModel, rtvec_list: Dict[int, R
 _REFINE_MIN_POINTS = 4
 
 
+def _accepted(cand, poses, status) -> Dict[int, RvecTvec]:
+    """{frame: pose} of the problems with a result: converged, or stopped at max_iterations (the reference keeps that result)."""
+    return {fi: RvecTvec.from6(poses[k]) for k, fi in enumerate(cand) if status[k] in (_ffi.OK, _ffi.ERR_NO_CONVERGENCE)}
+
+
 def refine_poses(frame_feature_list: Sequence[Optional[FrameFeature]], model: GenericModel,
                  rtvec_map: Optional[Dict[int, RvecTvec]] = None, huber_delta: float = 1.0,
                  ctx: Optional[Context] = None) -> Dict[int, RvecTvec]:
@@ -611,17 +624,11 @@ def refine_poses(frame_feature_list: Sequence[Optional[FrameFeature]], model: Ge
         cand = [i for i in cand if i in rtvec_map]
         if not cand:
             return {}
-    X, U = [], []
-    for i in cand:
-        ff = frame_feature_list[i]
-        ids = sorted(ff.features.keys())
-        # the reference holds detections and board points in f32 (src/detected_points.rs:6-9)
-        X.append(np.asarray([ff.features[k].p3d for k in ids], dtype=np.float32).astype(np.float64))
-        U.append(np.asarray([ff.features[k].p2d for k in ids], dtype=np.float32).astype(np.float64))
+    _, X, U = zip(*(_points_f32(frame_feature_list[i]) for i in cand))
     poses0 = np.stack([rtvec_map[i].as6() for i in cand])
     poses, status, _, _, _, _ = _ctx(ctx).refine_poses_batch(model.model_id, model._params, X, U, poses0, huber_delta,
                                                              _REFINE_MIN_POINTS)
-    return {fi: RvecTvec.from6(poses[k]) for k, fi in enumerate(cand) if status[k] in (_ffi.OK, _ffi.ERR_NO_CONVERGENCE)}
+    return _accepted(cand, poses, status)
 
 
 def validation_holdout(cam_idx: int, model: GenericModel, frame_feature_list: Sequence[Optional[FrameFeature]],
@@ -661,21 +668,12 @@ def refine_rig_poses(cams_detected_feature_frames: Sequence[Sequence[Optional[Fr
     cand = [fi for fi in range(n_frames) if seen[fi] and fi in board_rtvecs]
     if not cand:
         return {}
-    slots = []
-    for fi in cand:
-        segs = []
-        for c in seen[fi]:
-            ff = cams_detected_feature_frames[c][fi]
-            ids = sorted(ff.features.keys())
-            # the reference holds detections and board points in f32 (src/detected_points.rs:6-9)
-            segs.append((c, np.asarray([ff.features[k].p3d for k in ids], dtype=np.float32).astype(np.float64).reshape(-1, 3),
-                         np.asarray([ff.features[k].p2d for k in ids], dtype=np.float32).astype(np.float64).reshape(-1, 2)))
-        slots.append(segs)
+    slots = [[(c,) + _points_f32(cams_detected_feature_frames[c][fi])[1:] for c in seen[fi]] for fi in cand]
     poses0 = np.stack([board_rtvecs[fi].as6() for fi in cand])
     poses, status, _, _, _, _ = _ctx(ctx).refine_rig_poses_batch([m.model_id for m in cameras], [m._params for m in cameras],
                                                                  np.stack([t.as6() for t in t_cam_i_0]), slots, poses0, huber_delta,
                                                                  _REFINE_MIN_POINTS, opts)
-    return {fi: RvecTvec.from6(poses[k]) for k, fi in enumerate(cand) if status[k] in (_ffi.OK, _ffi.ERR_NO_CONVERGENCE)}
+    return _accepted(cand, poses, status)
 
 
 def validation_holdout_rig(cameras: Sequence[GenericModel], t_cam_i_0: Sequence[RvecTvec],

@@ -3,8 +3,10 @@
 //   CallPlan   the slices in order and the total - plain arithmetic, no context and no HIP call (tests/test_call_block_cpu.py)
 //   CallBlock  the plan, the block and a sticky hipError_t: after the first failure every step is a no-op and finish() reports it;
 //              the destructor drains the stream before the block goes back to the context's cache, on every way out
+//   check_offsets  the argument check of a batched call's CSR offsets, with the call's name in the message
 // Host only; for the translation units of the one-shot entry points ("One-shot calls").
 #pragma once
+#include <cstdio>
 #include "ccal_internal.hpp"
 
 namespace ccal {
@@ -14,6 +16,19 @@ inline int fail(ccal_ctx* ctx, int code, const char* msg) { note_error(ctx, msg)
 inline int hip_fail(ccal_ctx* ctx, const char* where, hipError_t e) {
     try { ctx->err = std::string(where) + ": " + hipGetErrorString(e); } catch (...) { }
     return CCAL_ERR_HIP;
+}
+
+// offsets[0] == 0, then over the n problems offsets[0 .. n]: no decrease and, with max_span > 0 (2^24, what the kernels index a
+// problem by), no problem of more points.  CCAL_OK, or CCAL_ERR_INVALID_ARG with "<where>: <name>..." as the context's message.
+inline int check_offsets(ccal_ctx* ctx, const char* where, const char* name, const int64_t* offsets, size_t n, int64_t max_span) {
+    const char* bad = offsets[0] != 0 ? "%s: %s[0] != 0" : nullptr;
+    for (size_t i = 0; i < n && !bad; ++i)
+        if (offsets[i + 1] < offsets[i] || (max_span > 0 && offsets[i + 1] - offsets[i] > max_span))
+            bad = max_span > 0 ? "%s: %s must not decrease, at most 2^24 points in a problem" : "%s: %s must not decrease";
+    if (!bad) return CCAL_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, bad, where, name);
+    return fail(ctx, CCAL_ERR_INVALID_ARG, msg);
 }
 
 template <class T> struct Slice { size_t off = 0, bytes = 0; };        // bytes: rounded up; 0 = absent (an optional output not asked for)

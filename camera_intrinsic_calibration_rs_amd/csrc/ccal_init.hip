@@ -59,7 +59,7 @@ int ccal_rdh_batch(ccal_ctx* ctx, int n_prob, const int64_t* pair_offsets, const
         if (n > (1 << 24)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_rdh_batch: more than 2^24 pairs in a problem");
         max_pairs = std::max(max_pairs, n);
     }
-    if (pair_offsets[0] != 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_rdh_batch: pair_offsets[0] != 0");
+    if (check_offsets(ctx, "ccal_rdh_batch", "pair_offsets", pair_offsets, 0, 0)) return CCAL_ERR_INVALID_ARG;      // (the spans: above)
     const size_t n_tot = (size_t)pair_offsets[n_prob], np = (size_t)n_prob, nh = np * (size_t)n_hyp;
     const int n_blocks = (n_hyp + 63) / 64;
     if (nh > ((size_t)1 << 28)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_rdh_batch: n_prob * n_hyp too large");
@@ -138,11 +138,7 @@ int ccal_pnp_batch(ccal_ctx* ctx, int n_prob, const int64_t* offsets, const doub
     if (n_prob < 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: n_prob < 0");
     if (n_prob == 0) return CCAL_OK;
     if (!offsets || !poses_out || !n_used_out) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: NULL argument");
-    if (offsets[0] != 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: offsets[0] != 0");
-    for (int i = 0; i < n_prob; ++i) {
-        const int64_t n = offsets[i + 1] - offsets[i];
-        if (n < 0 || n > (1 << 24)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: offsets must not decrease, at most 2^24 points in a problem");
-    }
+    if (check_offsets(ctx, "ccal_pnp_batch", "offsets", offsets, n_prob, 1 << 24)) return CCAL_ERR_INVALID_ARG;
     const size_t n_tot = (size_t)offsets[n_prob], np = (size_t)n_prob;
     if (n_tot && (!xyz || !xn)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pnp_batch: NULL argument");
     CCAL_API_TRY

@@ -27,46 +27,39 @@ struct RefineArgs {
     double th[CCAL_PMAX];               // the camera's parameters in the kernels' canonical order
     ModelRt rt;
     const int64_t* off;                 // [n_prob + 1]
-    const double* xyz; const double* uv;     // [.][3], [.][2] pixels
-    double* poses;                      // [n_prob][6] in: start, out: result
-    int32_t* status; int32_t* iters; int32_t* n_used;
-    double* cost0; double* cost;        // [n_prob]
-    double* err;                        // [n_points] pixel error at the result, or nullptr
-    RefineRule rule;
+    RefineIO io;
 };
 
-// The pass, solve and decide steps are in ccal_refine.hpp, shared with the rig's kernel (ccal_kernels_rig_refine.hip).
+// The pass, solve and decide steps, the count of valid points, both result stores and the host's result slices (RefineIO,
+// RefineResults) are in ccal_refine.hpp, shared with the rig's kernel (ccal_kernels_rig_refine.hip).
 template <int MODEL>
 __global__ __launch_bounds__(256) void k_pose_refine(const RefineArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int o = blockIdx.x * WAVES_PER_BLOCK + wave;
-    if (o >= a.rule.n_prob) return;
+    if (o >= a.io.rule.n_prob) return;
     const int64_t start = a.off[o];
     const int n = (int)(a.off[o + 1] - start);
-    const double* xyz = a.xyz + 3 * start;
-    const double* uv = a.uv + 2 * start;
-    double* err = a.err ? a.err + start : nullptr;
+    const double* xyz = a.io.xyz + 3 * start;
+    const double* uv = a.io.uv + 2 * start;
+    double* err = a.io.err ? a.io.err + start : nullptr;
     double th[th_len<MODEL>()];
     load_theta<MODEL, false>(a.th, a.rt, th);
 
     double pose[6];
     bool start_ok = true;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) { pose[i] = a.poses[(int64_t)o * 6 + i]; start_ok = start_ok && refine_finite(pose[i]); }
+    for (int i = 0; i < 6; ++i) { pose[i] = a.io.poses[(int64_t)o * 6 + i]; start_ok = start_ok && refine_finite(pose[i]); }
     int cnt = 0;
     for (int c = lane; c < n; c += 64) cnt += refine_point_valid(xyz, uv, c) ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if (!start_ok || cnt < (a.rule.min_points > 3 ? a.rule.min_points : 3)) {      // no result: the pose stays as the caller gave it
+    refine_count(cnt);
+    if (!start_ok || cnt < refine_min_points(a.io)) {
         if (err) for (int c = lane; c < n; c += 64) err[c] = __builtin_nan("");
-        if (lane == 0) {
-            a.status[o] = CCAL_NO_RESULT; a.iters[o] = 0; a.n_used[o] = 0; a.cost0[o] = 0.0; a.cost[o] = 0.0;
-        }
+        refine_store_none(a.io, o, lane);
         return;
     }
 
     // one pass over the frame's corners at the pose p: the totals on all lanes
-    const double delta = a.rule.delta;
+    const double delta = a.io.rule.delta;
     auto pass = [&](const double* p, const bool with_err, double* H, double* g, double& rep, double& obj) {
         double fc[FC_N0];
         frame_setup<false>(p, nullptr, fc);
@@ -76,13 +69,8 @@ __global__ __launch_bounds__(256) void k_pose_refine(const RefineArgs a) {
     };
     int iter;
     double cost0, cost;
-    const int status = refine_lm(a.rule, err != nullptr, pass, pose, iter, cost0, cost);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) a.poses[(int64_t)o * 6 + i] = pose[i];
-        a.status[o] = status; a.iters[o] = iter; a.n_used[o] = cnt;
-        a.cost0[o] = cost0; a.cost[o] = cost;
-    }
+    const int status = refine_lm(a.io.rule, err != nullptr, pass, pose, iter, cost0, cost);
+    refine_store(a.io, o, lane, pose, status, iter, cnt, cost0, cost);
 }
 
 template <int M> struct LaunchRefine { static void go(int g, hipStream_t st, const RefineArgs& a) { hipLaunchKernelGGL(k_pose_refine<M>, dim3(g), dim3(256), 0, st, a); } };
@@ -104,47 +92,31 @@ int ccal_refine_poses_batch(ccal_ctx* ctx, int model, const double* params, doub
     if (!params) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: NULL argument");
     if (n_prob == 0) return CCAL_OK;
     if (!offsets || !poses_io || !status_out) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: NULL argument");
-    if (offsets[0] != 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: offsets[0] != 0");
-    for (int i = 0; i < n_prob; ++i) {
-        const int64_t n = offsets[i + 1] - offsets[i];
-        if (n < 0 || n > (1 << 24)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: offsets must not decrease, at most 2^24 points in a problem");
-    }
+    if (check_offsets(ctx, "ccal_refine_poses_batch", "offsets", offsets, n_prob, 1 << 24)) return CCAL_ERR_INVALID_ARG;
     const size_t n_tot = (size_t)offsets[n_prob], np = (size_t)n_prob;
     if (n_tot && (!xyz || !uv)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_poses_batch: NULL argument");
-    ccal_solver_opts o;
-    if (opts) o = *opts; else ccal_set_defaults(&o);
     CCAL_API_TRY
     // one block: offsets | points | image points | poses, cost0, cost | errors | status, iterations, counts
     CallBlock blk(ctx);
     const auto s_off = blk.add<int64_t>(np + 1);
     const auto s_xyz = blk.add<double>((n_tot + 1) * 3);
     const auto s_uv = blk.add<double>((n_tot + 1) * 2);
-    const auto s_res = blk.add<double>(np * 8);
-    const auto s_err = blk.add<double>(err_out ? n_tot + 1 : 0);
-    const auto s_int = blk.add<int32_t>(np * 3);
+    const RefineResults res(blk, np, n_tot, err_out != nullptr);
     if (!blk.alloc()) return blk.finish("ccal_refine_poses_batch");
     RefineArgs a = {};
     canonical_theta(ctx, model, params, a.th, &a.rt);
-    a.off = blk.at(s_off); a.xyz = blk.at(s_xyz); a.uv = blk.at(s_uv);
-    a.poses = blk.at(s_res); a.cost0 = a.poses + np * 6; a.cost = a.poses + np * 7; a.err = blk.at(s_err);
-    a.status = blk.at(s_int); a.iters = a.status + np; a.n_used = a.status + 2 * np;
-    a.rule = refine_rule(huber_delta, o, n_prob, min_points);
-    blk.poison(s_xyz, s_err);
+    a.off = blk.at(s_off); a.io.xyz = blk.at(s_xyz); a.io.uv = blk.at(s_uv);
+    a.io.rule = refine_rule(huber_delta, opts, n_prob, min_points);
+    blk.poison(s_xyz, res.s_err);
     blk.upload(s_off, offsets, np + 1);
     blk.upload(s_xyz, xyz, n_tot * 3);
     blk.upload(s_uv, uv, n_tot * 2);
-    blk.upload(s_res, poses_io, np * 6);
+    res.start(a.io, poses_io);
     if (blk.ok()) {
         launch_model<LaunchRefine>(model, (n_prob + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, ctx->stream, a);
         blk.launched();
     }
-    blk.download(poses_io, a.poses, np * 6);
-    blk.download(status_out, a.status, np);
-    blk.download(iters_out, a.iters, np);
-    blk.download(n_used_out, a.n_used, np);
-    blk.download(cost0_out, a.cost0, np);
-    blk.download(cost_out, a.cost, np);
-    blk.download(err_out, a.err, n_tot);
+    res.download(a.io, poses_io, status_out, iters_out, n_used_out, cost0_out, cost_out, err_out);
     return blk.finish("ccal_refine_poses_batch");
     CCAL_API_CATCH(ctx)
 }

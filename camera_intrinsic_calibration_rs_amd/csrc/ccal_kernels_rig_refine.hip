@@ -15,6 +15,7 @@
 //   result does not depend on the batch around it.  No atomics, no LDS.
 // A segment shorter than 64 corners leaves lanes idle in its pass; two short segments are NOT packed into one pass (the lanes of a
 // pass would then run two model bodies one after the other under exec masks - DESIGN.md).
+#include <algorithm>
 #include "ccal_call.hpp"
 #include "ccal_refine.hpp"
 
@@ -28,12 +29,7 @@ struct RigRefineArgs {
     const int64_t* seg_off;             // [n_slots + 1]
     const int64_t* pt_off;              // [n_seg + 1]
     const int32_t* seg_cam;             // [n_seg]
-    const double* xyz; const double* uv;     // [.][3], [.][2] pixels
-    double* poses;                      // [n_slots][6] in: start, out: result
-    int32_t* status; int32_t* iters; int32_t* n_used;
-    double* cost0; double* cost;        // [n_slots]
-    double* err;                        // [n_points] pixel error at the result, or nullptr
-    RefineRule rule;                    // n_prob: the number of slots
+    RefineIO io;                        // a problem: a slot
 };
 
 // one segment's corners through its camera's model
@@ -49,34 +45,31 @@ __device__ __forceinline__ void rig_segment(const double* th_g, const ModelRt& r
 __global__ __launch_bounds__(256) void k_rig_pose_refine(const RigRefineArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int o = blockIdx.x * WAVES_PER_BLOCK + wave;
-    if (o >= a.rule.n_prob) return;
+    if (o >= a.io.rule.n_prob) return;
     const int64_t s0 = a.seg_off[o], s1 = a.seg_off[o + 1];
 
     double pose[6];
     bool start_ok = true;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) { pose[i] = a.poses[(int64_t)o * 6 + i]; start_ok = start_ok && refine_finite(pose[i]); }
+    for (int i = 0; i < 6; ++i) { pose[i] = a.io.poses[(int64_t)o * 6 + i]; start_ok = start_ok && refine_finite(pose[i]); }
     int cnt = 0;
     for (int64_t j = s0; j < s1; ++j) {
         const int64_t p0 = a.pt_off[j];
         const int n = (int)(a.pt_off[j + 1] - p0);
-        for (int c = lane; c < n; c += 64) cnt += refine_point_valid(a.xyz + 3 * p0, a.uv + 2 * p0, c) ? 1 : 0;
+        for (int c = lane; c < n; c += 64) cnt += refine_point_valid(a.io.xyz + 3 * p0, a.io.uv + 2 * p0, c) ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if (!start_ok || cnt < (a.rule.min_points > 3 ? a.rule.min_points : 3)) {      // no result: the pose stays as the caller gave it
-        if (a.err && s1 > s0) {
+    refine_count(cnt);
+    if (!start_ok || cnt < refine_min_points(a.io)) {
+        if (a.io.err && s1 > s0) {
             const int64_t p0 = a.pt_off[s0], p1 = a.pt_off[s1];        // a slot's segments, and so its points, are contiguous
-            for (int64_t c = p0 + lane; c < p1; c += 64) a.err[c] = __builtin_nan("");
+            for (int64_t c = p0 + lane; c < p1; c += 64) a.io.err[c] = __builtin_nan("");
         }
-        if (lane == 0) {
-            a.status[o] = CCAL_NO_RESULT; a.iters[o] = 0; a.n_used[o] = 0; a.cost0[o] = 0.0; a.cost[o] = 0.0;
-        }
+        refine_store_none(a.io, o, lane);
         return;
     }
 
     // one pass over all the slot's segments at the pose p: the totals on all lanes
-    const double delta = a.rule.delta;
+    const double delta = a.io.rule.delta;
     auto pass = [&](const double* p, const bool with_err, double* H, double* g, double& rep, double& obj) {
         refine_zero(H, g, rep, obj);
         for (int64_t j = s0; j < s1; ++j) {
@@ -84,9 +77,9 @@ __global__ __launch_bounds__(256) void k_rig_pose_refine(const RigRefineArgs a) 
             const int n = (int)(a.pt_off[j + 1] - p0);
             if (n == 0) continue;
             const int cam = a.seg_cam[j];
-            const double* xyz = a.xyz + 3 * p0;
-            const double* uv = a.uv + 2 * p0;
-            double* err = with_err ? a.err + p0 : nullptr;
+            const double* xyz = a.io.xyz + 3 * p0;
+            const double* uv = a.io.uv + 2 * p0;
+            double* err = with_err ? a.io.err + p0 : nullptr;
             double fc[FC_SIZE];
             frame_setup<true>(p, a.extr[cam], fc);
             switch (a.model[cam]) {
@@ -100,13 +93,8 @@ __global__ __launch_bounds__(256) void k_rig_pose_refine(const RigRefineArgs a) 
     };
     int iter;
     double cost0, cost;
-    const int status = refine_lm(a.rule, a.err != nullptr, pass, pose, iter, cost0, cost);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) a.poses[(int64_t)o * 6 + i] = pose[i];
-        a.status[o] = status; a.iters[o] = iter; a.n_used[o] = cnt;
-        a.cost0[o] = cost0; a.cost[o] = cost;
-    }
+    const int status = refine_lm(a.io.rule, a.io.err != nullptr, pass, pose, iter, cost0, cost);
+    refine_store(a.io, o, lane, pose, status, iter, cnt, cost0, cost);
 }
 
 }  // namespace ccal
@@ -131,23 +119,19 @@ int ccal_refine_rig_poses_batch(ccal_ctx* ctx, int n_cams, const int32_t* model,
     if (n_slots < 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: n_slots < 0");
     if (n_slots == 0) return CCAL_OK;
     if (!seg_offsets || !poses_io || !status_out) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: NULL argument");
-    if (seg_offsets[0] != 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: seg_offsets[0] != 0");
-    for (int i = 0; i < n_slots; ++i)
-        if (seg_offsets[i + 1] < seg_offsets[i]) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: seg_offsets must not decrease");
+    if (check_offsets(ctx, "ccal_refine_rig_poses_batch", "seg_offsets", seg_offsets, n_slots, 0)) return CCAL_ERR_INVALID_ARG;
     const size_t n_seg = (size_t)seg_offsets[n_slots], ns = (size_t)n_slots;
     if (n_seg && (!seg_cam || !pt_offsets)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: NULL argument");
-    if (n_seg && pt_offsets[0] != 0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: pt_offsets[0] != 0");
-    for (size_t j = 0; j < n_seg; ++j) {
-        if (pt_offsets[j + 1] < pt_offsets[j]) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: pt_offsets must not decrease");
-        if (seg_cam[j] < 0 || seg_cam[j] >= n_cams) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: seg_cam out of range");
-    }
+    // segment by segment, its point offsets ahead of its camera: the offsets up to the first camera out of range, then that camera
+    size_t j_cam = 0;
+    while (j_cam < n_seg && seg_cam[j_cam] >= 0 && seg_cam[j_cam] < n_cams) ++j_cam;
+    if (n_seg && check_offsets(ctx, "ccal_refine_rig_poses_batch", "pt_offsets", pt_offsets, std::min(j_cam + 1, n_seg), 0)) return CCAL_ERR_INVALID_ARG;
+    if (j_cam < n_seg) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: seg_cam out of range");
     for (int i = 0; i < n_slots && n_seg; ++i)
         if (pt_offsets[seg_offsets[i + 1]] - pt_offsets[seg_offsets[i]] > (1 << 24))
             return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: at most 2^24 points in a slot");
     const size_t n_tot = n_seg ? (size_t)pt_offsets[n_seg] : 0;
     if (n_tot && (!xyz || !uv)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_refine_rig_poses_batch: NULL argument");
-    ccal_solver_opts o;
-    if (opts) o = *opts; else ccal_set_defaults(&o);
     CCAL_API_TRY
     // one block: segment offsets | point offsets | segment cameras | points | image points | poses, cost0, cost | errors |
     // status, iterations, counts
@@ -157,9 +141,7 @@ int ccal_refine_rig_poses_batch(ccal_ctx* ctx, int n_cams, const int32_t* model,
     const auto s_cam = blk.add<int32_t>(n_seg + 1);
     const auto s_xyz = blk.add<double>((n_tot + 1) * 3);
     const auto s_uv = blk.add<double>((n_tot + 1) * 2);
-    const auto s_res = blk.add<double>(ns * 8);
-    const auto s_err = blk.add<double>(err_out ? n_tot + 1 : 0);
-    const auto s_int = blk.add<int32_t>(ns * 3);
+    const RefineResults res(blk, ns, n_tot, err_out != nullptr);
     if (!blk.alloc()) return blk.finish("ccal_refine_rig_poses_batch");
     RigRefineArgs a = {};
     for (int c = 0; c < n_cams; ++c) {
@@ -167,28 +149,20 @@ int ccal_refine_rig_poses_batch(ccal_ctx* ctx, int n_cams, const int32_t* model,
         for (int i = 0; i < 6; ++i) a.extr[c][i] = extr[(size_t)c * 6 + i];
         a.model[c] = model[c];
     }
-    a.seg_off = blk.at(s_sof); a.pt_off = blk.at(s_pof); a.seg_cam = blk.at(s_cam); a.xyz = blk.at(s_xyz); a.uv = blk.at(s_uv);
-    a.poses = blk.at(s_res); a.cost0 = a.poses + ns * 6; a.cost = a.poses + ns * 7; a.err = blk.at(s_err);
-    a.status = blk.at(s_int); a.iters = a.status + ns; a.n_used = a.status + 2 * ns;
-    a.rule = refine_rule(huber_delta, o, n_slots, min_points);
-    blk.poison(s_xyz, s_err);
+    a.seg_off = blk.at(s_sof); a.pt_off = blk.at(s_pof); a.seg_cam = blk.at(s_cam); a.io.xyz = blk.at(s_xyz); a.io.uv = blk.at(s_uv);
+    a.io.rule = refine_rule(huber_delta, opts, n_slots, min_points);
+    blk.poison(s_xyz, res.s_err);
     blk.upload(s_sof, seg_offsets, ns + 1);
     blk.upload(s_pof, pt_offsets, n_seg ? n_seg + 1 : 0);
     blk.upload(s_cam, seg_cam, n_seg);
     blk.upload(s_xyz, xyz, n_tot * 3);
     blk.upload(s_uv, uv, n_tot * 2);
-    blk.upload(s_res, poses_io, ns * 6);
+    res.start(a.io, poses_io);
     if (blk.ok()) {
         hipLaunchKernelGGL(k_rig_pose_refine, dim3((n_slots + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), 0, ctx->stream, a);
         blk.launched();
     }
-    blk.download(poses_io, a.poses, ns * 6);
-    blk.download(status_out, a.status, ns);
-    blk.download(iters_out, a.iters, ns);
-    blk.download(n_used_out, a.n_used, ns);
-    blk.download(cost0_out, a.cost0, ns);
-    blk.download(cost_out, a.cost, ns);
-    blk.download(err_out, a.err, n_tot);
+    res.download(a.io, poses_io, status_out, iters_out, n_used_out, cost0_out, cost_out, err_out);
     return blk.finish("ccal_refine_rig_poses_batch");
     CCAL_API_CATCH(ctx)
 }

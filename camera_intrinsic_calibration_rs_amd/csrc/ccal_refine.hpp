@@ -7,7 +7,11 @@
 //   refine_solve     (H + D) d = -g by a 6 x 6 Cholesky in registers on every lane
 //   refine_lm        the Levenberg-Marquardt rule stated at ccal_refine_poses_batch (ccal.h), one state per wavefront, around a
 //                    `pass` that a kernel supplies: everything between the starting pose and the result, nothing to the host between
+//   RefineIO         what both argument structs end with, and the frame around the pass: refine_count / refine_min_points (the
+//                    wave's valid points and what they are held against), refine_store_none / refine_store (lane 0's writes)
+//   RefineResults    host: the result slices of a call's block, bound to a RefineIO; the start poses up, the seven results down
 #pragma once
+#include "ccal_call.hpp"
 #include "ccal_device.hpp"
 #include "ccal_fused.hpp"
 #include "ccal_internal.hpp"
@@ -21,7 +25,9 @@ struct RefineRule {
     int32_t n_prob, min_points, max_iter, error_metric;
 };
 
-inline RefineRule refine_rule(double huber_delta, const ccal_solver_opts& o, int n_prob, int min_points) {
+inline RefineRule refine_rule(double huber_delta, const ccal_solver_opts* opts, int n_prob, int min_points) {      // opts NULL: the defaults
+    ccal_solver_opts o;
+    if (opts) o = *opts; else ccal_set_defaults(&o);
     RefineRule r;
     r.delta = huber_delta;
     r.radius0 = o.lm_initial_radius; r.min_diag = o.lm_min_diagonal; r.max_diag = o.lm_max_diagonal;
@@ -29,6 +35,36 @@ inline RefineRule refine_rule(double huber_delta, const ccal_solver_opts& o, int
     r.n_prob = n_prob; r.min_points = min_points; r.max_iter = o.max_iterations; r.error_metric = o.error_metric ? 1 : 0;
     return r;
 }
+
+// what both kernels' argument structs end with (o: a problem - a frame, or a slot of a rig)
+struct RefineIO {
+    const double* xyz; const double* uv;     // [.][3], [.][2] pixels
+    double* poses;                      // [n_prob][6] in: start, out: result
+    int32_t* status; int32_t* iters; int32_t* n_used;
+    double* cost0; double* cost;        // [n_prob]
+    double* err;                        // [n_points] pixel error at the result, or nullptr
+    RefineRule rule;
+};
+
+// The result part of a refine call's block, added where this is constructed: poses, cost0, cost | errors | status, iterations, counts
+struct RefineResults {
+    CallBlock& blk;
+    const size_t np, n_tot;
+    const Slice<double> s_res, s_err;
+    const Slice<int32_t> s_int;
+    RefineResults(CallBlock& b, size_t n_prob, size_t n_points, bool want_err)
+        : blk(b), np(n_prob), n_tot(n_points), s_res(b.add<double>(np * 8)), s_err(b.add<double>(want_err ? n_tot + 1 : 0)), s_int(b.add<int32_t>(np * 3)) {}
+    void start(RefineIO& a, const double* poses_io) const {          // after alloc() and poison(): the pointers, the start poses up
+        a.poses = blk.at(s_res); a.cost0 = a.poses + np * 6; a.cost = a.poses + np * 7; a.err = blk.at(s_err);
+        a.status = blk.at(s_int); a.iters = a.status + np; a.n_used = a.status + 2 * np;
+        blk.upload(s_res, poses_io, np * 6);
+    }
+    void download(const RefineIO& a, double* poses, int32_t* status, int32_t* iters, int32_t* n_used, double* cost0, double* cost, double* err) const {
+        blk.download(poses, a.poses, np * 6); blk.download(status, a.status, np); blk.download(iters, a.iters, np);
+        blk.download(n_used, a.n_used, np); blk.download(cost0, a.cost0, np); blk.download(cost, a.cost, np);
+        blk.download(err, a.err, n_tot);
+    }
+};
 
 constexpr int kRefTri = 21;             // packed lower triangle of the 6 x 6 system: entry (i, j <= i) at i (i + 1) / 2 + j
 
@@ -39,6 +75,31 @@ __device__ __forceinline__ bool refine_point_valid(const double* xyz, const doub
 #pragma unroll
     for (int k = 0; k < 3; ++k) v = v && refine_finite(xyz[3 * (int64_t)c + k]);
     return v;
+}
+
+// cnt: in, a lane's valid points; out, the wave's
+__device__ __forceinline__ void refine_count(int& cnt) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+}
+
+__device__ __forceinline__ int refine_min_points(const RefineIO& a) { return a.rule.min_points > 3 ? a.rule.min_points : 3; }   // for a result
+
+// no result: the pose stays as the caller gave it (the NaN fill of the problem's pixel errors is the kernel's)
+__device__ __forceinline__ void refine_store_none(const RefineIO& a, const int o, const int lane) {
+    if (lane == 0) {
+        a.status[o] = CCAL_NO_RESULT; a.iters[o] = 0; a.n_used[o] = 0; a.cost0[o] = 0.0; a.cost[o] = 0.0;
+    }
+}
+
+__device__ __forceinline__ void refine_store(const RefineIO& a, const int o, const int lane, const double* pose, const int status,
+                                             const int iter, const int cnt, const double cost0, const double cost) {
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) a.poses[(int64_t)o * 6 + i] = pose[i];
+        a.status[o] = status; a.iters[o] = iter; a.n_used[o] = cnt;
+        a.cost0[o] = cost0; a.cost[o] = cost;
+    }
 }
 
 __device__ __forceinline__ void refine_zero(double* H, double* g, double& cost, double& obj) {

@@ -32,6 +32,42 @@ def _dp(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _ip(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _lp(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _pack(arrays, width: int):
+    """The arrays [n_i, width] of a batch one after the other: (offsets int64 [n + 1], rows [total, width] f64, C-contiguous)."""
+    arrs = [_f64(a).reshape(-1, width) for a in arrays]
+    offs = np.zeros(len(arrs) + 1, dtype=np.int64)
+    np.cumsum([len(a) for a in arrs], out=offs[1:])
+    return offs, (np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros((0, width)))
+
+
+class _RefineOut:
+    """The outputs of a refine call for n problems of n_points points in all: poisoned, padded to one element at least."""
+
+    def __init__(self, n: int, poses0, n_points: int, with_errors: bool):
+        m = max(n, 1)
+        self.poses = np.full((m, 6), np.nan)
+        self.poses[:n] = _f64(poses0).reshape(n, 6)
+        self.ints = [np.full(m, -2, dtype=np.int32) for _ in range(3)]              # status, iterations, n_used
+        self.costs = [np.full(m, np.nan), np.full(m, np.nan)]                       # cost0, cost
+        self.err = np.full(max(n_points, 1), np.nan) if with_errors else None
+
+    def args(self):
+        return (_dp(self.poses), *map(_ip, self.ints), *map(_dp, self.costs), _dp(self.err))      # the tail of the C call
+
+    def result(self, n: int, err_bounds):
+        """The returned tuple; err_bounds: per problem the (first, last) of its points in err."""
+        out = tuple(a[:n] for a in (self.poses, *self.ints, *self.costs))
+        return out + ([self.err[a:b] for a, b in err_bounds],) if self.err is not None else out
+
+
 class Context:
     """One GPU + one HIP stream (ccal_ctx)."""
 
@@ -98,10 +134,7 @@ class Context:
         each.  Returns a dict of per-problem arrays `lambda` [n], `H` [n, 3, 3], `score` [n], `best` [n] (-1: none), `n_valid` [n]
         and, with per_hypothesis, `hyp_sample` [n, n_hyp, 6], `hyp_lambda`, `hyp_H` [n, n_hyp, 9], `hyp_score` (+inf: none)."""
         n = len(pairs_list)
-        arrs = [_f64(a).reshape(-1, 4) for a in pairs_list]
-        offs = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([len(a) for a in arrs], out=offs[1:])
-        allp = np.ascontiguousarray(np.concatenate(arrs)) if n else np.zeros((0, 4))
+        offs, allp = _pack(pairs_list, 4)
         if allp.size == 0:
             allp = np.zeros((1, 4))
         sd = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
@@ -115,10 +148,9 @@ class Context:
         if per_hypothesis:
             hyp = {"hyp_sample": np.full((m, n_hyp, 6), -2, dtype=np.int32), "hyp_lambda": np.full((m, n_hyp), nan),
                    "hyp_H": np.full((m, n_hyp, 9), nan), "hyp_score": np.full((m, n_hyp), nan)}
-        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
-        rc = self.lib.ccal_rdh_batch(self.handle, n, offs.ctypes.data_as(C.POINTER(C.c_int64)), _dp(allp),
+        rc = self.lib.ccal_rdh_batch(self.handle, n, _lp(offs), _dp(allp),
                                      sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_hyp), _dp(out["lambda"]), _dp(out["H"]),
-                                     _dp(out["score"]), ip(out["best"]), ip(out["n_valid"]), ip(hyp["hyp_sample"]),
+                                     _dp(out["score"]), _ip(out["best"]), _ip(out["n_valid"]), _ip(hyp["hyp_sample"]),
                                      _dp(hyp["hyp_lambda"]), _dp(hyp["hyp_H"]), _dp(hyp["hyp_score"]))
         if rc != _ffi.OK:
             raise CcalError(rc, "ccal_rdh_batch", self.last_error())
@@ -135,19 +167,13 @@ class Context:
         n = len(xyz_list)
         if len(xn_list) != n:
             raise ValueError("pnp_batch: one array of image points per array of points")
-        X = [_f64(a).reshape(-1, 3) for a in xyz_list]
-        U = [_f64(a).reshape(-1, 2) for a in xn_list]
-        if any(len(a) != len(b) for a, b in zip(X, U)):
+        (offs, allx), (offs_u, allu) = _pack(xyz_list, 3), _pack(xn_list, 2)
+        if not np.array_equal(offs, offs_u):
             raise ValueError("pnp_batch: a problem's points and image points differ in number")
-        offs = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([len(a) for a in X], out=offs[1:])
-        allx = np.ascontiguousarray(np.concatenate(X)) if n else np.zeros((0, 3))
-        allu = np.ascontiguousarray(np.concatenate(U)) if n else np.zeros((0, 2))
         m = max(n, 1)
         poses = np.full((m, 6), np.nan); used = np.full(m, -2, dtype=np.int32)
         cost = np.full(m, np.nan) if with_cost else None
-        rc = self.lib.ccal_pnp_batch(self.handle, n, offs.ctypes.data_as(C.POINTER(C.c_int64)), _dp(allx), _dp(allu), int(min_points),
-                                     _dp(poses), used.ctypes.data_as(C.POINTER(C.c_int32)), _dp(cost))
+        rc = self.lib.ccal_pnp_batch(self.handle, n, _lp(offs), _dp(allx), _dp(allu), int(min_points), _dp(poses), _ip(used), _dp(cost))
         if rc != _ffi.OK:
             raise CcalError(rc, "ccal_pnp_batch", self.last_error())
         return poses[:n], used[:n], (cost[:n] if with_cost else None)
@@ -163,34 +189,18 @@ class Context:
         n = len(xyz_list)
         if len(uv_list) != n:
             raise ValueError("refine_poses_batch: one array of detections per array of points")
-        X = [_f64(a).reshape(-1, 3) for a in xyz_list]
-        U = [_f64(a).reshape(-1, 2) for a in uv_list]
-        if any(len(a) != len(b) for a, b in zip(X, U)):
+        (offs, allx), (offs_u, allu) = _pack(xyz_list, 3), _pack(uv_list, 2)
+        if not np.array_equal(offs, offs_u):
             raise ValueError("refine_poses_batch: a frame's points and detections differ in number")
-        m = max(n, 1)
-        poses = np.full((m, 6), np.nan)
-        poses[:n] = _f64(poses0).reshape(n, 6)
-        offs = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([len(a) for a in X], out=offs[1:])
-        allx = np.ascontiguousarray(np.concatenate(X)) if n else np.zeros((0, 3))
-        allu = np.ascontiguousarray(np.concatenate(U)) if n else np.zeros((0, 2))
+        out = _RefineOut(n, poses0, int(offs[-1]), with_errors)
         par = np.zeros(PMAX)
         p = _f64(params).ravel()
         par[:len(p)] = p
-        status = np.full(m, -2, dtype=np.int32); iters = np.full(m, -2, dtype=np.int32); used = np.full(m, -2, dtype=np.int32)
-        cost0 = np.full(m, np.nan); cost = np.full(m, np.nan)
-        err = np.full(max(int(offs[-1]), 1), np.nan) if with_errors else None
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        rc = self.lib.ccal_refine_poses_batch(self.handle, int(model), _dp(par), float(huber_delta), n,
-                                              offs.ctypes.data_as(C.POINTER(C.c_int64)), _dp(allx), _dp(allu), int(min_points),
-                                              C.byref(opts) if opts is not None else None, _dp(poses), ip(status), ip(iters),
-                                              ip(used), _dp(cost0), _dp(cost), _dp(err))
+        rc = self.lib.ccal_refine_poses_batch(self.handle, int(model), _dp(par), float(huber_delta), n, _lp(offs), _dp(allx), _dp(allu),
+                                              int(min_points), C.byref(opts) if opts is not None else None, *out.args())
         if rc != _ffi.OK:
             raise CcalError(rc, "ccal_refine_poses_batch", self.last_error())
-        out = (poses[:n], status[:n], iters[:n], used[:n], cost0[:n], cost[:n])
-        if with_errors:
-            out += ([err[int(offs[i]):int(offs[i + 1])] for i in range(n)],)
-        return out
+        return out.result(n, [(int(offs[i]), int(offs[i + 1])) for i in range(n)])
 
     # -- board poses of a rig under fixed intrinsics and extrinsics, batched (ccal_refine_rig_poses_batch, ccal_kernels_rig_refine.hip) --
     def refine_rig_poses_batch(self, models, params, extr, slots, poses0, huber_delta: float = 1.0, min_points: int = 4,
@@ -211,38 +221,20 @@ class Context:
             p = _f64(p).ravel()[:PMAX]
             par[c, :len(p)] = p
         ex = _f64(extr).reshape(n_cams, 6)
-        cams, X, U = [], [], []
+        segs = [seg for slot in slots for seg in slot]
         seg_offs = np.zeros(n + 1, dtype=np.int64)
-        for s, segs in enumerate(slots):
-            for cam, x, u in segs:
-                cams.append(int(cam)); X.append(_f64(x).reshape(-1, 3)); U.append(_f64(u).reshape(-1, 2))
-            seg_offs[s + 1] = len(cams)
-        if any(len(a) != len(b) for a, b in zip(X, U)):
+        seg_offs[1:] = np.add.accumulate([len(slot) for slot in slots], dtype=np.int64)
+        (pt_offs, allx), (offs_u, allu) = _pack([x for _, x, _ in segs], 3), _pack([u for _, _, u in segs], 2)
+        if not np.array_equal(pt_offs, offs_u):
             raise ValueError("refine_rig_poses_batch: a segment's points and detections differ in number")
-        n_seg = len(cams)
-        seg_cam = np.asarray(cams + [0], dtype=np.int32)
-        pt_offs = np.zeros(n_seg + 1, dtype=np.int64)
-        np.cumsum([len(a) for a in X], out=pt_offs[1:])
-        allx = np.ascontiguousarray(np.concatenate(X)) if n_seg else np.zeros((0, 3))
-        allu = np.ascontiguousarray(np.concatenate(U)) if n_seg else np.zeros((0, 2))
-        m = max(n, 1)
-        poses = np.full((m, 6), np.nan)
-        poses[:n] = _f64(poses0).reshape(n, 6)
-        status = np.full(m, -2, dtype=np.int32); iters = np.full(m, -2, dtype=np.int32); used = np.full(m, -2, dtype=np.int32)
-        cost0 = np.full(m, np.nan); cost = np.full(m, np.nan)
-        err = np.full(max(int(pt_offs[-1]), 1), np.nan) if with_errors else None
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        rc = self.lib.ccal_refine_rig_poses_batch(self.handle, n_cams, ip(mod), _dp(par), _dp(ex), float(huber_delta), n, lp(seg_offs),
-                                                  ip(seg_cam), lp(pt_offs), _dp(allx), _dp(allu), int(min_points),
-                                                  C.byref(opts) if opts is not None else None, _dp(poses), ip(status), ip(iters),
-                                                  ip(used), _dp(cost0), _dp(cost), _dp(err))
+        seg_cam = np.asarray([int(cam) for cam, _, _ in segs] + [0], dtype=np.int32)
+        out = _RefineOut(n, poses0, int(pt_offs[-1]), with_errors)
+        rc = self.lib.ccal_refine_rig_poses_batch(self.handle, n_cams, _ip(mod), _dp(par), _dp(ex), float(huber_delta), n, _lp(seg_offs),
+                                                  _ip(seg_cam), _lp(pt_offs), _dp(allx), _dp(allu), int(min_points),
+                                                  C.byref(opts) if opts is not None else None, *out.args())
         if rc != _ffi.OK:
             raise CcalError(rc, "ccal_refine_rig_poses_batch", self.last_error())
-        out = (poses[:n], status[:n], iters[:n], used[:n], cost0[:n], cost[:n])
-        if with_errors:
-            out += ([err[int(pt_offs[seg_offs[s]]):int(pt_offs[seg_offs[s + 1]])] for s in range(n)],)
-        return out
+        return out.result(n, [(int(pt_offs[seg_offs[s]]), int(pt_offs[seg_offs[s + 1]])) for s in range(n)])
 
     # -- applying a calibration: points, the new camera matrix, undistortion maps (ccal_kernels_undistort.hip) ---------------
     def _points(self, fn, where, model: int, params, pts, in_w: int, out_w: int):

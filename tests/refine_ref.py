@@ -10,7 +10,12 @@ counts each outlier delta sqrt(s) and is not stationary where the iteration stop
 numpy: Levenberg-Marquardt on the corrected system with central-difference Jacobians of r through synth.project (no analytic
 derivative anywhere), a step taken when objective() decreases, run until the step stalls.  solve() starts it both from the
 given pose and from the ground truth and keeps the lower objective.
+
+cost_of() ... solve_of() are that yardstick over any residual callable res(pose) -> r [n, 2] (poses [k, 6] -> [k, n, 2]); the
+functions of this module bind them to one camera's frame, those of tests/rig_refine_ref.py to a slot of a rig.
 """
+from functools import partial
+
 import numpy as np
 
 from camera_intrinsic_calibration_rs_amd import synth
@@ -41,16 +46,16 @@ def corrected(model, params, X, uv, pose, delta):
     return c.reshape(c.shape[:-2] + (-1,))
 
 
-def cost(model, params, X, uv, pose, delta):
-    r = residuals(model, params, X, uv, pose)
+def cost_of(res, pose, delta):
+    r = res(pose)
     s = (r * r).sum(axis=-1)
     c = (weights(s, delta) * s).sum(axis=-1)
     return float(c) if c.ndim == 0 else c
 
 
-def objective(model, params, X, uv, pose, delta):
+def objective_of(res, pose, delta):
     """sum rho(s): the function whose stationary point the corrected Gauss-Newton iteration finds."""
-    r = residuals(model, params, X, uv, pose)
+    r = res(pose)
     s = (r * r).sum(axis=-1)
     if delta > 0.0:
         s = np.where(s > delta * delta, 2.0 * delta * np.sqrt(s) - delta * delta, s)
@@ -63,34 +68,34 @@ def _stencil(pose, h):
     return np.concatenate([pose + h * np.eye(6), pose - h * np.eye(6)])
 
 
-def gradient(model, params, X, uv, pose, delta, h=_H):
-    """Central-difference gradient of objective() with respect to rvec | tvec."""
-    c = objective(model, params, X, uv, _stencil(pose, h), delta)
+def gradient_of(res, pose, delta, h=_H):
+    """Central-difference gradient of objective_of() with respect to rvec | tvec."""
+    c = objective_of(res, _stencil(pose, h), delta)
     return (c[:6] - c[6:]) / (2 * h)
 
 
-def _corrected_system(model, params, X, uv, pose, delta, h=_H):
+def corrected_system_of(res, pose, delta, h=_H):
     """(J, c): central-difference Jacobian of r and r itself, rows scaled by sqrt(rho')."""
-    r = residuals(model, params, X, uv, pose)
+    r = res(pose)
     sw = np.sqrt(weights((r * r).sum(axis=-1), delta))
-    rs = residuals(model, params, X, uv, _stencil(pose, h))
+    rs = res(_stencil(pose, h))
     J = (rs[:6] - rs[6:]) / (2 * h)                                   # [6, n, 2]
     return (J * sw[None, :, None]).reshape(6, -1).T, (r * sw[:, None]).ravel()
 
 
-def refine(model, params, X, uv, pose0, delta, max_iter=300):
-    """LM from pose0 until the step stalls: (pose, cost() there)."""
+def refine_of(res, pose0, delta, max_iter=300):
+    """LM from pose0 until the step stalls (the rounding of the objective): (pose, cost_of() there)."""
     x = np.asarray(pose0, dtype=np.float64).copy()
-    F = objective(model, params, X, uv, x, delta)
+    F = objective_of(res, x, delta)
     lam = 1e-4
     for _ in range(max_iter):
-        J, c = _corrected_system(model, params, X, uv, x, delta)
+        J, c = corrected_system_of(res, x, delta)
         H = J.T @ J
         g = J.T @ c
         moved = False
         while lam < 1e12:
             d = -np.linalg.solve(H + lam * np.diag(np.maximum(np.diag(H), 1e-12)), g)
-            Fn = objective(model, params, X, uv, x + d, delta)
+            Fn = objective_of(res, x + d, delta)
             if Fn < F:
                 x = x + d; F = Fn; lam = max(lam * 0.1, 1e-15); moved = True
                 break
@@ -99,11 +104,37 @@ def refine(model, params, X, uv, pose0, delta, max_iter=300):
             lam *= 10.0
         if not moved or np.abs(d).max() < 1e-14:
             break
-    return x, cost(model, params, X, uv, x, delta)
+    return x, cost_of(res, x, delta)
+
+
+def solve_of(res, pose_start, pose_gt, delta):
+    """Of the runs from pose_start and from pose_gt the one with the lower objective."""
+    a = refine_of(res, pose_start, delta)
+    b = refine_of(res, pose_gt, delta)
+    return a if objective_of(res, a[0], delta) <= objective_of(res, b[0], delta) else b
+
+
+def cost(model, params, X, uv, pose, delta):
+    return cost_of(partial(residuals, model, params, X, uv), pose, delta)
+
+
+def objective(model, params, X, uv, pose, delta):
+    return objective_of(partial(residuals, model, params, X, uv), pose, delta)
+
+
+def gradient(model, params, X, uv, pose, delta, h=_H):
+    return gradient_of(partial(residuals, model, params, X, uv), pose, delta, h)
+
+
+def _corrected_system(model, params, X, uv, pose, delta, h=_H):
+    return corrected_system_of(partial(residuals, model, params, X, uv), pose, delta, h)
+
+
+def refine(model, params, X, uv, pose0, delta, max_iter=300):
+    """LM from pose0 until the step stalls: (pose, cost() there)."""
+    return refine_of(partial(residuals, model, params, X, uv), pose0, delta, max_iter)
 
 
 def solve(model, params, X, uv, pose_start, pose_gt, delta):
     """The yardstick's answer for one frame: of the runs from pose_start and from pose_gt the one with the lower objective."""
-    a = refine(model, params, X, uv, pose_start, delta)
-    b = refine(model, params, X, uv, pose_gt, delta)
-    return a if objective(model, params, X, uv, a[0], delta) <= objective(model, params, X, uv, b[0], delta) else b
+    return solve_of(partial(residuals, model, params, X, uv), pose_start, pose_gt, delta)
