@@ -10,6 +10,19 @@
 
 namespace ccal {
 
+// Corners that do not span the board plane (one row, one column, a diagonal, one corner repeated) leave the design rank-deficient -
+// rank 6 of 8 for a line - and no pose: rotation about the line is free.  In exact arithmetic a Cholesky pivot s is then 0; computed,
+// it is a difference of at most 8 products each bounded by its diagonal entry M_jj, +-1e-16 M_jj, and its sign is rounding.  So a
+// pivot is accepted on s > kPoseInitPivotTol M_jj, not on s > 0.  The two ends the tolerance sits between (tests/pose_init_cases.py
+// prints them; s / M_jj does not change when board or image coordinates are rescaled):
+//   from below  100 x the pivot's rounding bound 10 u = 1.1e-15, i.e. 1.1e-13 (the f64 emulation of this kernel accepted collinear
+//               frames at s / M_jj = 1.7e-16; one row plus ONE corner of the next row, which exact detections leave at rank 7,
+//               comes to 1.4e-14 through the f32 rounding of its detections and is refused as well);
+//   from above  1 / 100 of the smallest s / M_jj of a well-posed frame of the test cases, 2.7e-6 / 100 = 2.7e-8 (a board whose
+//               origin is 100 m from its corners; two adjacent rows 2.6e-3, a full board 1.6e-1).
+// A frame that passes goes through exactly the arithmetic it went through under s > 0: its result keeps its bits.
+constexpr double kPoseInitPivotTol = 0x1p-36;            // 1.46e-11
+
 template <int MODEL>
 __global__ __launch_bounds__(256) void k_pose_init(const InitArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -68,9 +81,10 @@ __global__ __launch_bounds__(256) void k_pose_init(const InitArgs a) {
         int k = 0;
         for (int i = 0; i < 8; ++i) for (int j = i; j < 8; ++j) { L[j][i] = M[k]; ++k; }
         for (int j = 0; j < 8 && ok; ++j) {
-            double s = L[j][j];
+            const double mjj = L[j][j];
+            double s = mjj;
             for (int q = 0; q < j; ++q) s -= L[j][q] * L[j][q];
-            if (!(s > 0.0)) { ok = false; break; }
+            if (!(s > kPoseInitPivotTol * mjj)) { ok = false; break; }
             const double l = sqrt(s);
             L[j][j] = l;
             for (int i = j + 1; i < 8; ++i) { double t = L[i][j]; for (int q = 0; q < j; ++q) t -= L[i][q] * L[j][q]; L[i][j] = t / l; }
@@ -84,8 +98,14 @@ __global__ __launch_bounds__(256) void k_pose_init(const InitArgs a) {
         const double n1 = sqrt(c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2]);
         const double n2 = sqrt(c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]);
         const double lam = 2.0 / (n1 + n2);
-        const double t[3] = { lam * h[2], lam * h[5], lam };
+        double t[3] = { lam * h[2], lam * h[5], lam };
         for (int i = 0; i < 3; ++i) c1[i] /= n1;
+        // h33 = 1 fixes the sign of H by the depth of the board's ORIGIN; the pose is the one with the corners in front of the
+        // camera, sum_i (h31 X_i + h32 Y_i + 1) > 0 (M[2], M[9], M[15] = sum X, sum Y, n) - the rule of ccal_pnp_batch.  The
+        // origin of a board may lie behind the camera's plane while its corners are in view: then [r1 r2 t] is -H, not H.
+        if (h[6] * M[2] + h[7] * M[9] + M[15] < 0.0) {
+            for (int i = 0; i < 3; ++i) { c1[i] = -c1[i]; c2[i] = -c2[i]; t[i] = -t[i]; }
+        }
         const double d = c1[0] * c2[0] + c1[1] * c2[1] + c1[2] * c2[2];
         for (int i = 0; i < 3; ++i) c2[i] -= d * c1[i];
         const double n2b = sqrt(c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]);

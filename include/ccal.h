@@ -376,6 +376,14 @@ int ccal_multi_solve(ccal_multi_problem* mp, const ccal_solver_opts* opts,
  * homography -- same basin, the joint solve refines it).  poses_obs [n_obs][6] = T_cam_board of every
  * observation frame; n_used [n_obs] = corners that entered the estimate, 0 = no pose (the reference skips
  * frames with fewer than 10 valid unprojections: pass min_points = 10).
+ * A frame gets NO pose - six zeros, n_used 0 - when
+ *   - fewer than min_points corners unproject (outside the model's domain, or not in front of the camera),
+ *   - its valid corners do not span the board plane (one row, one column, a diagonal, one corner repeated: rotation about the
+ *     line is free): a Cholesky pivot s of the 8 x 8 normal matrix M is at or below 2^-36 (1.46e-11) x its own diagonal entry M_jj.
+ *     Well-posed frames sit above 1e-6 (two adjacent rows: 2.6e-3), rank-deficient ones at rounding, below 1e-13,
+ *   - the homography's first two columns are not two directions (a norm at or below 1e-12) or the result is not finite.
+ * Of the homography's two signs the pose is the one with the corners in front of the camera (their summed depth is positive, the
+ * rule of ccal_pnp_batch), wherever the board's origin lies.
  *
  * The homography serves frames whose corners all have z == 0 (z = -0 counts).  A frame with any z != 0 - a board whose coordinates
  * are not at z = 0, boards hinged at an angle, any 3-D target - takes a general PnP instead (ccal_pnp_batch below: the same
