@@ -428,7 +428,7 @@ hipError_t launch_gram1v_general(int model, bool one_focal, const FusedArgs& a, 
 // ccal_kernels_gram2.hip: a corner's two rows on two lanes (row-local columns), same records, same fused tail
 hipError_t launch_gram2(int model, bool one_focal, FusedArgs& a, hipStream_t s);
 // single-launch groups on the two-wavefronts-per-SIMD kernel (k_gram2i: UCM / EUCM, 2 000 .. ~10 000 frames): rows (= workgroups of eight
-// wavefronts) such a launch of this problem has, 0: the form does not apply; launch: a.it filled in as for launch_gram_iter
+// wavefronts) such a launch of this problem has, 0: the form does not apply (avg_corners: not used - the window is one of frame counts, g2_iter_applies); launch: a.it filled in as for launch_gram_iter
 int gram2_iter_rows(int model, bool one_focal, int n_obs, int avg_corners, int K);
 hipError_t launch_gram2_iter(int model, bool one_focal, FusedArgs& a, hipStream_t s);
 hipError_t launch_gram2_general(int model, bool one_focal, const FusedArgs& a, hipStream_t s);

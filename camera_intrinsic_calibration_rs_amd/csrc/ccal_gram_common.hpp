@@ -4,6 +4,7 @@
 #pragma once
 #include "ccal_device.hpp"
 #include "ccal_fused.hpp"
+#include "ccal_gram_plan.hpp"
 
 namespace ccal {
 
@@ -303,8 +304,13 @@ __device__ __forceinline__ double gen_backsub_pose(const FusedArgs& a, const int
     return mc;
 }
 
-#ifndef CCAL_GRAMV_WPB
-#define CCAL_GRAMV_WPB 2          // wavefronts per workgroup of the register Gram kernels
-#endif
+// host: the fusion plan of a plain (unbinned) launch of a register Gram kernel - the rows its wavefronts may take (what the lane mapping
+// is chosen under) and, once the mapping is chosen, what the kernel and the groups behind it read in the argument block
+inline int64_t fused_wave_cap(const FusedArgs& a, bool gen) { return (gen || !a.fuse_elim) ? kNoWaveCap : (int64_t)a.part_cap; }
+inline void set_fuse_plan(FusedArgs& a, int lpf, bool gen) {
+    const FusePlan fp = fuse_plan(lpf, a.n_obs, a.fuse_elim != 0, a.part_cap, gen);
+    a.fuse_elim = a.elim_fused = fp.fuse ? 1 : 0;
+    if (fp.fuse) a.n_part = fp.n_part;
+}
 
 }  // namespace ccal

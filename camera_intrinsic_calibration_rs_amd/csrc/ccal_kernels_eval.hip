@@ -8,6 +8,7 @@
 // 64 consecutive corners form one contiguous 64*2*D*8-byte tile of J_out, so they are transposed
 // through LDS and written with full 16-B-per-lane coalesced stores.  HBM-write-bound by design.
 #include "ccal_device.hpp"
+#include "ccal_gram_plan.hpp"
 #include "ccal_internal.hpp"
 
 #include <algorithm>
@@ -273,30 +274,18 @@ static hipError_t launch_err_t(const KArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-#define CCAL_DISPATCH(FN, model, of, other, ...)                                                     \
-    do {                                                                                             \
-        const int key_ = (model) * 4 + ((of) ? 2 : 0) + ((other) ? 1 : 0);                           \
-        switch (key_) {                                                                              \
-            case 0: return FN<kUCM, false, false>(__VA_ARGS__);   case 1: return FN<kUCM, false, true>(__VA_ARGS__);   \
-            case 2: return FN<kUCM, true, false>(__VA_ARGS__);    case 3: return FN<kUCM, true, true>(__VA_ARGS__);    \
-            case 4: return FN<kEUCM, false, false>(__VA_ARGS__);  case 5: return FN<kEUCM, false, true>(__VA_ARGS__);  \
-            case 6: return FN<kEUCM, true, false>(__VA_ARGS__);   case 7: return FN<kEUCM, true, true>(__VA_ARGS__);   \
-            case 8: return FN<kKB4, false, false>(__VA_ARGS__);   case 9: return FN<kKB4, false, true>(__VA_ARGS__);   \
-            case 10: return FN<kKB4, true, false>(__VA_ARGS__);   case 11: return FN<kKB4, true, true>(__VA_ARGS__);   \
-            case 12: return FN<kOCV5, false, false>(__VA_ARGS__); case 13: return FN<kOCV5, false, true>(__VA_ARGS__); \
-            case 14: return FN<kOCV5, true, false>(__VA_ARGS__);  case 15: return FN<kOCV5, true, true>(__VA_ARGS__);  \
-            default: return hipErrorInvalidValue;                                                    \
-        }                                                                                            \
-    } while (0)
-
 hipError_t launch_eval(const ccal_problem* p, int cam, const KArgs& a, hipStream_t s) {
     // corner rows (20 B each) of the whole problem beyond ~half the Infinity Cache: they will not survive the output
     // stream from one launch to the next (measured cliff: 46 000 -> 50 000 frames x 144 corners = 132 -> 144 MB)
     const bool big_inputs = p->n_corners * 20 > (int64_t)120 << 20;
-    CCAL_DISPATCH(launch_eval_t, p->cams[cam].model, p->one_focal, cam > 0, a, big_inputs, s);
+    return dispatch_model_focal_other(p->cams[cam].model, p->one_focal, cam > 0, hipErrorInvalidValue, [&](auto m, auto of, auto other) {
+        return launch_eval_t<decltype(m)::value, decltype(of)::value, decltype(other)::value>(a, big_inputs, s);
+    });
 }
 hipError_t launch_reproj_err(const ccal_problem* p, int cam, const KArgs& a, hipStream_t s) {
-    CCAL_DISPATCH(launch_err_t, p->cams[cam].model, p->one_focal, cam > 0, a, s);
+    return dispatch_model_focal_other(p->cams[cam].model, p->one_focal, cam > 0, hipErrorInvalidValue, [&](auto m, auto of, auto other) {
+        return launch_err_t<decltype(m)::value, decltype(of)::value, decltype(other)::value>(a, s);
+    });
 }
 
 }  // namespace ccal

@@ -254,9 +254,19 @@ struct RecMap {
 };
 template <int K, int W, bool GEN = false> __device__ const RecMap<K, W, GEN> g_recmap = RecMap<K, W, GEN>();
 
-#ifndef CCAL_GRAMV_WPB
-#define CCAL_GRAMV_WPB 2          // wavefronts per workgroup (4 frames each)
+// camera columns whose products with the pose columns k_gram1w keeps as LDS accumulators
+#ifndef CCAL_GRAMW_NLC
+#define CCAL_GRAMW_NLC 3          // measured at 10 000 frames (EUCM): 6 -> 53.2, 4 -> 51.8, 3 -> 51.0, 2 -> 56.1 us per build
 #endif
+// doubles of LDS per wavefront of k_gram1v (W = false) / k_gram1w (W = true) at lpf lanes per frame: the frames' constants | the
+// reduction buffer (k_gram1w: or its LDS accumulators).  The kernels assert their own layout against it, the launchers size by it.
+template <int MODEL, bool OF, bool W>
+constexpr int gram1_wave_lds(int lpf) {
+    constexpr int NC = block_dim(MODEL, OF, false) + 1, NE = NC * (NC + 1) / 2;
+    constexpr int NL = W ? 6 * (CCAL_GRAMW_NLC < NC - 7 ? CCAL_GRAMW_NLC : NC - 7) : 0;
+    constexpr int LS = ((NE - NL + 1) / 2) | 1;
+    return (64 / lpf) * FC_N0P + (NL * 65 > 64 * LS ? NL * 65 : 64 * LS);
+}
 // structural zeros of the block Jacobian rows (u row: no fy, cy; v row: no fx, cx); f feeds both rows
 template <bool OF> __device__ constexpr bool nz_u(int i) { return OF ? (i != 2) : (i != 1 && i != 3); }
 template <bool OF> __device__ constexpr bool nz_v(int i) { return OF ? (i != 1) : (i != 0 && i != 2); }
@@ -285,6 +295,7 @@ __device__ __forceinline__ void gram1v_body(const FusedArgs& a, const IterDyn& d
     constexpr int HALF = (NE + 1) / 2;              // entries reduced per LDS round
     constexpr int LS = HALF | 1;                    // odd row stride (doubles): conflict-free column sums
     constexpr int WSL = G * FC_N0P + 64 * LS;           // per wave: G frames' constants | reduction buffer
+    static_assert(WSL == gram1_wave_lds<MODEL, OF, false>(LPF), "the launchers size the LDS by gram1_wave_lds");
     constexpr int NQ = (G * HALF + 63) / 64;        // (frame, entry) sums per lane and round
     extern __shared__ double smem[];
 #ifdef CCAL_STAMPS          // diagnostic build (tools/stamps_g1v.py): the phases of every wavefront, 8 stamps per wavefront in the per-frame scratch
@@ -731,9 +742,6 @@ __global__ __launch_bounds__(64 * CCAL_GRAMV_WPB, 2) void k_gram1w(const FusedAr
     constexpr int K = D - 6, K1 = K + 1;
     constexpr int NC = D + 1;                       // columns of [J | r]
     constexpr int NE = NC * (NC + 1) / 2;           // upper triangle
-#ifndef CCAL_GRAMW_NLC
-#define CCAL_GRAMW_NLC 3          // measured at 10 000 frames (EUCM): 6 -> 53.2, 4 -> 51.8, 3 -> 51.0, 2 -> 56.1 us per build
-#endif
     // camera columns whose products with the pose columns are LDS accumulators: as few as keeps two wavefronts per SIMD
     constexpr int NLC = CCAL_GRAMW_NLC < K ? CCAL_GRAMW_NLC : K;
     constexpr int NL = 6 * NLC;
@@ -743,6 +751,7 @@ __global__ __launch_bounds__(64 * CCAL_GRAMV_WPB, 2) void k_gram1w(const FusedAr
     constexpr int LS = HALF | 1;                    // odd row stride (doubles): conflict-free column sums
     constexpr int RED = NL * LSA > 64 * LS ? NL * LSA : 64 * LS;
     constexpr int WSL = G * FC_N0P + RED;               // per wave: G frames' constants | accumulators / reduction buffer
+    static_assert(WSL == gram1_wave_lds<MODEL, OF, true>(LPF), "the launchers size the LDS by gram1_wave_lds");
     constexpr int NQ = (G * HALF + 63) / 64;        // (frame, entry) sums per lane and round
     constexpr int NQA = (G * NL + 63) / 64;
     extern __shared__ double smem[];
@@ -1058,15 +1067,16 @@ __global__ __launch_bounds__(64 * CCAL_GRAMV_WPB, 2) void k_gram1w(const FusedAr
 #endif
 }
 
+// the second library's developer switches compile k_gram1w and the OPENCV5 instantiations of k_gram1v's single-problem forms in
+#ifdef CCAL_DEV_SWITCHES
+constexpr bool kDevSwitches = true;
+#else
+constexpr bool kDevSwitches = false;
+#endif
 template <int MODEL, bool OF, int LPF, bool W, bool GEN>
 static hipError_t launch_gram1v_l(const FusedArgs& a, hipStream_t s) {
     constexpr int G = 64 / LPF;
-    constexpr int NC = block_dim(MODEL, OF, false) + 1;
-    constexpr int NE = NC * (NC + 1) / 2, NL = 6 * (CCAL_GRAMW_NLC < NC - 7 ? CCAL_GRAMW_NLC : NC - 7);
-    constexpr int HALF = ((W ? NE - NL : NE) + 1) / 2;
-    constexpr int RED = (W && NL * 65 > 64 * (HALF | 1)) ? NL * 65 : 64 * (HALF | 1);
-    constexpr int WSL = G * FC_N0P + RED;
-    const size_t lds = sizeof(double) * WSL * CCAL_GRAMV_WPB;
+    const size_t lds = sizeof(double) * gram1_wave_lds<MODEL, OF, W>(LPF) * CCAL_GRAMV_WPB;
     void (*kern)(const FusedArgs);
     if constexpr (W) kern = k_gram1w<MODEL, OF, LPF, GEN>; else kern = k_gram1v<MODEL, OF, LPF, GEN>;
     static DynLdsGuard lds_guard;
@@ -1076,49 +1086,11 @@ static hipError_t launch_gram1v_l(const FusedArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3((a.n_obs + fpb - 1) / fpb), dim3(64 * CCAL_GRAMV_WPB), lds, s, a);
     return hipGetLastError();
 }
-// Lanes per frame: few lanes = many corner passes per lane but fewer wavefronts, and a wavefront's prologue, reductions and
-// (fused) elimination amortised over more corners.  Cost of a launch in units of one corner pass (~1.75 us):
-//   k_gram1v (one wavefront per SIMD):   rounds x (c0 + passes),   rounds = ceil(wavefronts / 1 024)
-//   k_gram1w (two wavefronts per SIMD):  g(n) x (c0 + passes),     n = wavefronts / 1 024 SIMDs,
-//     g = 1 (n <= 1: every wavefront alone on its SIMD), 1 + 0.3 (n - 1) up to n = 2 (the younger partner runs at ~0.57 of
-//     the solo speed until it is alone), 0.65 + 0.43 n beyond (wavefronts past 2 048 wait for a slot: a step at n = 2, then
-//     pipelined) - fitted to tools/sweep_lpf.py with the fused elimination (6 / 8 / 12 / 16 / 32 / 64 lanes, 1 500-50 000 frames;
-//     EUCM us per build, best in brackets: 5 000 frames 37.4 40.2 33.7 [31.2] 37.2 50.7; 10 000: 52.9 45.8 [40.8] 45.7 58.3 82.4;
-//     20 000: 85.2 [67.6] 72.1 74.6 98.0 117; 50 000: 159 [138] 151 154 191 267;  KB4 (k_gram1v) 10 000: [54.6] 78.1 63.4 74.3
-//     88.4 138; 20 000: [99.4] 115 116 120 168 214).  c0 = 6 passes' worth of prologue + epilogue (6 lanes: 8).
-// The second library's CCAL_GRAMV_LPF overrides.  Mappings whose wavefronts would not fit the rows of the partial-sum buffer
-// (`max_waves`: the single-camera loop's fused elimination writes one row per wavefront) are left out; six lanes per frame
-// (the fewest wavefronts) always fit (fused_ws_ensure sizes the buffer for them).
-static int gram_lanes_per_frame(int n_obs, int avg_corners, int slots, int64_t max_waves = (int64_t)1 << 40, int share = 1) {
-    static const int cand[6] = { 64, 32, 16, 12, 8, 6 };
-    // developer override: only the instantiated mappings (anything else would make the launcher's wavefront count and the
-    // kernel it falls back to disagree)
-    static const int lpf_env = [] {
-        const int v = dev_env_int("CCAL_GRAMV_LPF", 0);
-        for (int c : cand) if (v == c) return v;
-        return 0;
-    }();
-    if (lpf_env) return lpf_env;
-    int best = 6;
-    double best_cost = 1e300;
-    for (int i = 0; i < 6; ++i) {
-        const int lpf = cand[i], g = 64 / lpf;
-        const int64_t waves = ((int64_t)n_obs + g - 1) / g;
-        if (((waves + CCAL_GRAMV_WPB - 1) / CCAL_GRAMV_WPB) * CCAL_GRAMV_WPB > max_waves && lpf != 6) continue;
-        const int passes = (std::max(avg_corners, 1) + lpf - 1) / lpf;
-        const double c0 = lpf == 6 ? 8.0 : 6.0;
-        double occ;
-        const int simds = std::max(1024 / std::max(share, 1), 64);      // side-by-side sessions (ccal_solve_batch) share the chip
-        if (slots > 1024) {
-            const double n = (double)waves / (double)simds;
-            occ = n <= 1.0 ? 1.0 : (n <= 2.0 ? 1.0 + 0.3 * (n - 1.0) : 0.65 + 0.43 * n);
-        } else {
-            occ = (double)((waves + simds - 1) / simds);
-        }
-        const double cost = occ * (c0 + passes);
-        if (cost < best_cost) { best_cost = cost; best = lpf; }        // ties: the wider mapping (listed first)
-    }
-    return best;
+// Lanes per frame: the cost model of ccal_gram_plan.hpp with k_gram1v's (one wavefront per SIMD) or k_gram1w's (two) constants.
+// The second library's CCAL_GRAMV_LPF overrides.
+static int gram_lanes_per_frame(int n_obs, int avg_corners, bool two_per_simd, int64_t max_waves = kNoWaveCap, int share = 1) {
+    static const int lpf_env = dev_env_int("CCAL_GRAMV_LPF", 0);
+    return lanes_per_frame(n_obs, avg_corners, gram1_lane_cost(two_per_simd), lpf_env, max_waves, share);
 }
 template <int MODEL, bool OF, bool GEN>
 static hipError_t launch_gram1v_t(FusedArgs& a, hipStream_t s) {
@@ -1132,59 +1104,33 @@ static hipError_t launch_gram1v_t(FusedArgs& a, hipStream_t s) {
     // (k_gram1w is not even instantiated for them: CCAL_GRAMV_LDSACC=1 has no effect there)
     // The PRODUCT launchers never reach k_gram1w (UCM / EUCM from 2 000 frames go to k_gram2, use_gram2) nor any OPENCV5
     // instantiation of k_gram1v (k_gram2 for every size): they are compiled into the second library only (CCAL_GRAM2=0 there)
-#ifdef CCAL_DEV_SWITCHES
-    constexpr bool W_OK = NCt * (NCt + 1) / 2 <= 91;
-#else
-    constexpr bool W_OK = false; (void)NCt;
-#endif
+    constexpr bool W_OK = kDevSwitches && NCt * (NCt + 1) / 2 <= 91;
     const bool w = W_OK && (force >= 0 ? force == 1 : a.n_obs >= 2000);
-    const int lpf = gram_lanes_per_frame(a.n_obs, a.avg_corners, w ? 2048 : 1024, (GEN || !a.fuse_elim) ? (int64_t)1 << 40 : a.part_cap, a.share);
-    // fused elimination (single-camera loop): one row of partial sums per wavefront
-    const int waves = ((a.n_obs + 64 / lpf - 1) / (64 / lpf) + CCAL_GRAMV_WPB - 1) / CCAL_GRAMV_WPB * CCAL_GRAMV_WPB;
-    // (every size: 300 / 625 / 1 000 / 1 280 frames GN 0.135-0.155 ms fused against 0.145-0.172 with a separate elimination launch and
-    // the head's own reduction of its <= 40 rows; the second library's CCAL_FUSE_ELIM=0 still takes the separate launch)
-    const bool fuse = !GEN && a.fuse_elim != 0 && waves <= a.part_cap;
-    a.fuse_elim = fuse ? 1 : 0;
-    a.elim_fused = fuse ? 1 : 0;
-    if (fuse) a.n_part = waves;
-#define CCAL_LPF_CASE(L) case L: if constexpr (W_OK) { if (w) return launch_gram1v_l<MODEL, OF, L, true, GEN>(a, s); } return launch_gram1v_l<MODEL, OF, L, false, GEN>(a, s);
-    switch (lpf) {
-        CCAL_LPF_CASE(6) CCAL_LPF_CASE(8) CCAL_LPF_CASE(12) CCAL_LPF_CASE(16) CCAL_LPF_CASE(32)
-        default: if constexpr (W_OK) { if (w) return launch_gram1v_l<MODEL, OF, 64, true, GEN>(a, s); } return launch_gram1v_l<MODEL, OF, 64, false, GEN>(a, s);
-    }
-#undef CCAL_LPF_CASE
+    const int lpf = gram_lanes_per_frame(a.n_obs, a.avg_corners, w, fused_wave_cap(a, GEN), a.share);
+    set_fuse_plan(a, lpf, GEN);
+    return dispatch_lanes(lpf, hipErrorInvalidValue, [&](auto l) {
+        constexpr int LPF = decltype(l)::value;
+        if constexpr (W_OK) { if (w) return launch_gram1v_l<MODEL, OF, LPF, true, GEN>(a, s); }
+        return launch_gram1v_l<MODEL, OF, LPF, false, GEN>(a, s);
+    });
 }
 template <bool GEN>
 static hipError_t launch_gram1v_m(int model, bool one_focal, FusedArgs& a, hipStream_t s) {
-    switch (model * 2 + (one_focal ? 1 : 0)) {
-        case 0: return launch_gram1v_t<kUCM, false, GEN>(a, s);
-        case 1: return launch_gram1v_t<kUCM, true, GEN>(a, s);
-        case 2: return launch_gram1v_t<kEUCM, false, GEN>(a, s);
-        case 3: return launch_gram1v_t<kEUCM, true, GEN>(a, s);
-        case 4: return launch_gram1v_t<kKB4, false, GEN>(a, s);
-        case 5: return launch_gram1v_t<kKB4, true, GEN>(a, s);
-#ifdef CCAL_DEV_SWITCHES
-        case 6: return launch_gram1v_t<kOCV5, false, GEN>(a, s);
-        case 7: return launch_gram1v_t<kOCV5, true, GEN>(a, s);
-#else
-        case 6: case 7: return hipErrorNotSupported;          // (OPENCV5: k_gram2 for every size)
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_model_focal(model, one_focal, hipErrorInvalidValue, [&](auto m, auto of) {
+        constexpr int MODEL = decltype(m)::value;
+        if constexpr (MODEL == kOCV5 && !kDevSwitches) return hipErrorNotSupported;          // (OPENCV5: k_gram2 for every size)
+        else return launch_gram1v_t<MODEL, decltype(of)::value, GEN>(a, s);
+    });
 }
 // ---- single-launch groups (k_gram1v<.., ITER>) ----
 constexpr int kIterWpb = 4;
 constexpr size_t kLdsPerCu = 160 * 1024;
-template <int MODEL, bool OF, int LPF>
-static size_t iter_lds_bytes() {
-    constexpr int G = 64 / LPF, NC = block_dim(MODEL, OF, false) + 1, NE = NC * (NC + 1) / 2, HALF = (NE + 1) / 2;
-    constexpr int WSL = G * FC_N0P + 64 * (HALF | 1);
-    return sizeof(double) * WSL * kIterWpb;
-}
+template <int MODEL, bool OF>
+static constexpr size_t iter_lds_bytes(int lpf) { return sizeof(double) * gram1_wave_lds<MODEL, OF, false>(lpf) * kIterWpb; }
 template <int MODEL, bool OF, int LPF>
 static hipError_t launch_gram_iter_l(FusedArgs& a, hipStream_t s) {
     constexpr int G = 64 / LPF;
-    const size_t lds = iter_lds_bytes<MODEL, OF, LPF>();
+    const size_t lds = iter_lds_bytes<MODEL, OF>(LPF);
     void (*kern)(const FusedArgs) = k_gram1v<MODEL, OF, LPF, false, true>;
     static DynLdsGuard lds_guard;
     if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds, lds_guard); e != hipSuccess) return e;
@@ -1197,64 +1143,32 @@ static hipError_t launch_gram_iter_l(FusedArgs& a, hipStream_t s) {
 // static LDS of the ITER form beside the dynamic part: HeadShared + the reduction's 4 x 64 + the four rows
 template <int MODEL, bool OF>
 static constexpr size_t iter_static_lds() { return sizeof(HeadShared) + 4 * 2 * 64 * 8 + 4 * 8 * (size_t)fused_red_size(block_dim(MODEL, OF, false) - 6) + 256; }
+// rows (= workgroups) of a single-launch group, 0 if the form does not apply; launch: the group is launched as well (*err)
 template <int MODEL, bool OF>
 static int iter_rows_t(int n_obs, int avg_corners, int share, bool launch, FusedArgs* a, hipStream_t s, hipError_t* err) {
+    // OPENCV5 in the product: only the batched form exists (k_gram1v_batch) - the row count without the single-problem launcher
+    constexpr bool LAUNCHER = MODEL != kOCV5 || kDevSwitches;
     // CCAL_ITER_ROWS: most rows (= workgroups, each of which reads every row of the launch before) for which a group is one
     // launch; 0 = never.  One wavefront per SIMD, every workgroup resident at once: <= 256 workgroups.
     static const int max_rows = std::min(dev_env_int("CCAL_ITER_ROWS", 256), 256);
-    if (n_obs <= 0 || max_rows <= 0) return 0;
-    const int lpf = gram_lanes_per_frame(n_obs, avg_corners, 1024, (int64_t)1 << 40, share);
+    if (n_obs <= 0 || max_rows <= 0 || (launch && !LAUNCHER)) return 0;
+    const int lpf = gram_lanes_per_frame(n_obs, avg_corners, false, kNoWaveCap, share);
     const int g = 64 / lpf, rows = (n_obs + g * kIterWpb - 1) / (g * kIterWpb);
-    if (rows > max_rows) return 0;
-    size_t lds = 0;
-    switch (lpf) {
-#define CCAL_IT_CASE(L) case L: lds = iter_lds_bytes<MODEL, OF, L>(); if (launch && lds + iter_static_lds<MODEL, OF>() <= kLdsPerCu) *err = launch_gram_iter_l<MODEL, OF, L>(*a, s); break;
-        CCAL_IT_CASE(6) CCAL_IT_CASE(8) CCAL_IT_CASE(12) CCAL_IT_CASE(16) CCAL_IT_CASE(32) CCAL_IT_CASE(64)
-#undef CCAL_IT_CASE
-        default: return 0;
+    if (rows > max_rows || iter_lds_bytes<MODEL, OF>(lpf) + iter_static_lds<MODEL, OF>() > kLdsPerCu) return 0;
+    if constexpr (LAUNCHER) {
+        if (launch) *err = dispatch_lanes(lpf, hipErrorInvalidValue, [&](auto l) { return launch_gram_iter_l<MODEL, OF, decltype(l)::value>(*a, s); });
     }
-    if (lds + iter_static_lds<MODEL, OF>() > kLdsPerCu) return 0;
     return rows;
 }
-// rows (= workgroups) of a single-launch group without reference to a launcher: 0 if the form does not apply
-template <int MODEL, bool OF>
-static int iter_rows_only(int n_obs, int avg_corners, int share) {
-    if (n_obs <= 0) return 0;
-    const int lpf = gram_lanes_per_frame(n_obs, avg_corners, 1024, (int64_t)1 << 40, share);
-    const int g = 64 / lpf, rows = (n_obs + g * kIterWpb - 1) / (g * kIterWpb);
-    if (rows > 256) return 0;
-    size_t lds = 0;
-    switch (lpf) {
-        case 6: lds = iter_lds_bytes<MODEL, OF, 6>(); break;   case 8: lds = iter_lds_bytes<MODEL, OF, 8>(); break;
-        case 12: lds = iter_lds_bytes<MODEL, OF, 12>(); break; case 16: lds = iter_lds_bytes<MODEL, OF, 16>(); break;
-        case 32: lds = iter_lds_bytes<MODEL, OF, 32>(); break; case 64: lds = iter_lds_bytes<MODEL, OF, 64>(); break;
-        default: return 0;
-    }
-    return lds + iter_static_lds<MODEL, OF>() <= kLdsPerCu ? rows : 0;
-}
 static int iter_rows_m(int model, bool one_focal, int n_obs, int avg_corners, int share, bool launch, FusedArgs* a, hipStream_t s, hipError_t* err) {
-    switch (model * 2 + (one_focal ? 1 : 0)) {
-        case 0: return iter_rows_t<kUCM, false>(n_obs, avg_corners, share, launch, a, s, err);
-        case 1: return iter_rows_t<kUCM, true>(n_obs, avg_corners, share, launch, a, s, err);
-        case 2: return iter_rows_t<kEUCM, false>(n_obs, avg_corners, share, launch, a, s, err);
-        case 3: return iter_rows_t<kEUCM, true>(n_obs, avg_corners, share, launch, a, s, err);
-        case 4: return iter_rows_t<kKB4, false>(n_obs, avg_corners, share, launch, a, s, err);
-        case 5: return iter_rows_t<kKB4, true>(n_obs, avg_corners, share, launch, a, s, err);
-#ifdef CCAL_DEV_SWITCHES
-        case 6: return iter_rows_t<kOCV5, false>(n_obs, avg_corners, share, launch, a, s, err);
-        case 7: return iter_rows_t<kOCV5, true>(n_obs, avg_corners, share, launch, a, s, err);
-#else
-        // OPENCV5 in the product: only the batched form exists (k_gram1v_batch) - the row count without the single-problem launcher
-        case 6: return launch ? 0 : iter_rows_only<kOCV5, false>(n_obs, avg_corners, share);
-        case 7: return launch ? 0 : iter_rows_only<kOCV5, true>(n_obs, avg_corners, share);
-#endif
-        default: return 0;
-    }
+    return dispatch_model_focal(model, one_focal, 0, [&](auto m, auto of) {
+        return iter_rows_t<decltype(m)::value, decltype(of)::value>(n_obs, avg_corners, share, launch, a, s, err);
+    });
 }
 // ---- the batched form (k_gram1v_batch) ----
 template <int MODEL, bool OF, int LPF>
 static hipError_t launch_iter_batch_l(const FusedArgs* tab, int n, int max_rows, int s_no, hipStream_t s) {
-    const size_t lds = iter_lds_bytes<MODEL, OF, LPF>();
+    const size_t lds = iter_lds_bytes<MODEL, OF>(LPF);
     if (lds + iter_static_lds<MODEL, OF>() > kLdsPerCu) return hipErrorInvalidValue;
     void (*kern)(const FusedArgs*, int) = k_gram1v_batch<MODEL, OF, LPF>;
     static DynLdsGuard lds_guard;
@@ -1262,34 +1176,16 @@ static hipError_t launch_iter_batch_l(const FusedArgs* tab, int n, int max_rows,
     hipLaunchKernelGGL(kern, dim3(max_rows, n), dim3(64 * kIterWpb), lds, s, tab, s_no);
     return hipGetLastError();
 }
-template <int MODEL, bool OF>
-static hipError_t launch_iter_batch_t(int lpf, const FusedArgs* tab, int n, int max_rows, int s_no, hipStream_t s) {
-    switch (lpf) {
-        case 6: return launch_iter_batch_l<MODEL, OF, 6>(tab, n, max_rows, s_no, s);
-        case 8: return launch_iter_batch_l<MODEL, OF, 8>(tab, n, max_rows, s_no, s);
-        case 12: return launch_iter_batch_l<MODEL, OF, 12>(tab, n, max_rows, s_no, s);
-        case 16: return launch_iter_batch_l<MODEL, OF, 16>(tab, n, max_rows, s_no, s);
-        case 32: return launch_iter_batch_l<MODEL, OF, 32>(tab, n, max_rows, s_no, s);
-        case 64: return launch_iter_batch_l<MODEL, OF, 64>(tab, n, max_rows, s_no, s);
-        default: return hipErrorInvalidValue;
-    }
-}
 // one launch for n problems of one model / focal mode / lane mapping; tab: device memory, n FusedArgs (bases, see the kernel)
 hipError_t launch_gram_iter_batch(int model, bool one_focal, int lpf, const FusedArgs* tab, int n, int max_rows, int s_no, hipStream_t s) {
-    switch (model * 2 + (one_focal ? 1 : 0)) {
-        case 0: return launch_iter_batch_t<kUCM, false>(lpf, tab, n, max_rows, s_no, s);
-        case 1: return launch_iter_batch_t<kUCM, true>(lpf, tab, n, max_rows, s_no, s);
-        case 2: return launch_iter_batch_t<kEUCM, false>(lpf, tab, n, max_rows, s_no, s);
-        case 3: return launch_iter_batch_t<kEUCM, true>(lpf, tab, n, max_rows, s_no, s);
-        case 4: return launch_iter_batch_t<kKB4, false>(lpf, tab, n, max_rows, s_no, s);
-        case 5: return launch_iter_batch_t<kKB4, true>(lpf, tab, n, max_rows, s_no, s);
-        case 6: return launch_iter_batch_t<kOCV5, false>(lpf, tab, n, max_rows, s_no, s);
-        case 7: return launch_iter_batch_t<kOCV5, true>(lpf, tab, n, max_rows, s_no, s);
-        default: return hipErrorNotSupported;
-    }
+    return dispatch_model_focal(model, one_focal, hipErrorNotSupported, [&](auto m, auto of) {
+        return dispatch_lanes(lpf, hipErrorInvalidValue, [&](auto l) {
+            return launch_iter_batch_l<decltype(m)::value, decltype(of)::value, decltype(l)::value>(tab, n, max_rows, s_no, s);
+        });
+    });
 }
 // the lane mapping a single-launch group of this problem takes (what launch_gram_iter dispatches on)
-int fused_iter_lpf(int n_obs, int avg_corners, int share) { return gram_lanes_per_frame(n_obs, avg_corners, 1024, (int64_t)1 << 40, share); }
+int fused_iter_lpf(int n_obs, int avg_corners, int share) { return gram_lanes_per_frame(n_obs, avg_corners, false, kNoWaveCap, share); }
 
 // CCAL_GRAM2_ITER=0 (second library) / -DCCAL_NO_GRAM2_ITER (A/B builds): k_gram1v's single-launch form at every size
 static bool use_gram2_iter(bool batch, int share) {
@@ -1352,17 +1248,7 @@ static hipError_t launch_gram1_t(const FusedArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 hipError_t launch_gram1(int model, bool one_focal, const FusedArgs& a, hipStream_t s) {
-    switch (model * 2 + (one_focal ? 1 : 0)) {
-        case 0: return launch_gram1_t<kUCM, false>(a, s);
-        case 1: return launch_gram1_t<kUCM, true>(a, s);
-        case 2: return launch_gram1_t<kEUCM, false>(a, s);
-        case 3: return launch_gram1_t<kEUCM, true>(a, s);
-        case 4: return launch_gram1_t<kKB4, false>(a, s);
-        case 5: return launch_gram1_t<kKB4, true>(a, s);
-        case 6: return launch_gram1_t<kOCV5, false>(a, s);
-        case 7: return launch_gram1_t<kOCV5, true>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_model_focal(model, one_focal, hipErrorInvalidValue, [&](auto m, auto of) { return launch_gram1_t<decltype(m)::value, decltype(of)::value>(a, s); });
 }
 
 #else

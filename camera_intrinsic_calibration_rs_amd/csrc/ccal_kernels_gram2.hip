@@ -204,6 +204,16 @@ template <int MODEL> __host__ __device__ constexpr int g2_slices() { return (MOD
 #define CCAL_G2_HOIST(MODEL) ((MODEL) == kUCM)
 #endif
 
+// doubles of LDS per wavefront of the k_gram2 family at lpf lanes per frame: the frames' constants (+ R, t mirrored) | the reduction buffer,
+// or the frames' records for the fused elimination | the item table.  The kernel asserts its own layout against it, the launchers size by it.
+template <int MODEL, bool OF, bool GEN>
+constexpr int gram2_wave_lds(int lpf) {
+    using Map = RowMap<MODEL, OF, GEN, g2_slices<MODEL>()>;
+    constexpr int K1 = block_dim(MODEL, OF, false) - 6 + 1, LS = Map::CH | 1, GS_ = (praw_jl_off(K1 - 1) + 9 + 6 * K1 + 1) & ~1;
+    const int G = 64 / lpf, RED = (!GEN && G * GS_ > 64 * LS) ? G * GS_ : 64 * LS;
+    return (G * (FC_N0P + 12) + RED + Map::NEF + 1) & ~1;
+}
+
 // R | t of a frame with the x and y rows exchanged: what the v lanes transform their corners with
 __device__ __forceinline__ void g2_store_mirrored(const double* fcr, double* dst) {
 #pragma unroll
@@ -251,6 +261,7 @@ __device__ __forceinline__ void gram2_body(const FusedArgs& a, double* smem, con
     constexpr int REC_ = praw_jl_off(K) + 9, GS_ = (REC_ + 6 * K1 + 1) & ~1;
     constexpr int RED = (!GEN && G * GS_ > 64 * LS) ? G * GS_ : 64 * LS;
     constexpr int WSL = (G * FCS + RED + NEF + 1) & ~1;        // per wave: G frames' constants | reduction buffer / records | item table
+    static_assert(WSL == gram2_wave_lds<MODEL, OF, GEN>(LPF), "the launchers size the LDS by gram2_wave_lds");
     static_assert(!ITER || fused_red_size(K) <= G * FCS, "a wavefront's row of partial sums is parked where its frames' constants were");
     const bool fuse = !GEN && a.fuse_elim != 0;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -900,14 +911,8 @@ template __global__ void k_gram2i<kEUCM, false, 12, true>(const FusedArgs);
 #else
 template <int MODEL, bool OF, int LPF, bool GEN>
 static hipError_t launch_gram2_l(const FusedArgs& a, hipStream_t s) {
-    constexpr int NS = g2_slices<MODEL>();
-    using Map = RowMap<MODEL, OF, GEN, NS>;
-    constexpr int G = 64 / LPF, K = block_dim(MODEL, OF, false) - 6, K1 = K + 1;
-    constexpr int LS = Map::CH | 1;
-    constexpr int GS_ = (praw_jl_off(K) + 9 + 6 * K1 + 1) & ~1;
-    constexpr int RED = (!GEN && G * GS_ > 64 * LS) ? G * GS_ : 64 * LS;
-    constexpr int WSL = (G * (FC_N0P + 12) + RED + Map::NEF + 1) & ~1;
-    const size_t lds = sizeof(double) * WSL * CCAL_GRAMV_WPB;
+    constexpr int G = 64 / LPF;
+    const size_t lds = sizeof(double) * gram2_wave_lds<MODEL, OF, GEN>(LPF) * CCAL_GRAMV_WPB;
     void (*kern)(const FusedArgs) = k_gram2<MODEL, OF, LPF, GEN>;
     static DynLdsGuard lds_guard;
     if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds, lds_guard); e != hipSuccess) return e;
@@ -917,34 +922,10 @@ static hipError_t launch_gram2_l(const FusedArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Lanes per frame (even: 64, 32, 16, 12, 8, 6): the cost model of gram_lanes_per_frame (ccal_kernels_fused.hip).
-// `force` (FusedArgs::lpf_force: a developer switch of the second library) overrides; mappings whose wavefronts would not fit
-// the rows of the partial-sum buffer (`max_waves`, single-camera loop: one row per wavefront) are left out.
+// Lanes per frame (even: 64, 32, 16, 12, 8, 6): the cost model of ccal_gram_plan.hpp with k_gram2's constants.
+// `force` (FusedArgs::lpf_force: a developer switch of the second library) overrides.
 static int gram2_lanes_per_frame(int n_obs, int avg_corners, bool two_per_simd, bool gen, int force, int64_t max_waves, int share) {
-    static const int cand[6] = { 64, 32, 16, 12, 8, 6 };
-    for (int c : cand) if (force == c) return c;
-    int best = 6;
-    double best_cost = 1e300;
-    for (int i = 0; i < 6; ++i) {
-        const int lpf = cand[i], g = 64 / lpf;
-        const int64_t waves = ((int64_t)n_obs + g - 1) / g;
-        if (((waves + CCAL_GRAMV_WPB - 1) / CCAL_GRAMV_WPB) * CCAL_GRAMV_WPB > max_waves && lpf != 6) continue;
-        const int passes = (std::max(avg_corners, 1) + lpf - 1) / lpf;
-        // prologue + reductions + elimination, in passes; the general loop's launches (GEN) have no elimination in their tail
-        // (two EUCM cameras x 10 000 frames in one launch, whole build: 6 lanes 77.0 us, 8: 81.5, 12: 83.1, 16: 85.0)
-        // - but what they measure at 20 000 frames is a larger fixed cost per wavefront (the record goes to HBM, the
-        // occupancy term below is optimistic beyond four wavefronts per SIMD)
-        // (single camera, 20 000 frames, whole build: 6 lanes 55.1 us, 8: 59.1, 12: 63.8; 50 000 frames: 133.8, 123.5, 136.8)
-        const double c0 = gen ? (lpf == 6 ? 8.0 : 7.0) : (lpf == 6 ? 7.0 : 6.0);
-        double occ;
-        const int simds = std::max(1024 / std::max(share, 1), 64);      // side-by-side sessions (ccal_solve_batch) share the chip
-        const double nw = (double)waves / (double)simds;
-        if (two_per_simd) occ = nw <= 1.0 ? 1.0 : (nw <= 2.0 ? 1.0 + 0.3 * (nw - 1.0) : 0.65 + 0.43 * nw);
-        else occ = (double)((waves + simds - 1) / simds);
-        const double cost = occ * (c0 + passes);
-        if (cost < best_cost) { best_cost = cost; best = lpf; }
-    }
-    return best;
+    return lanes_per_frame(n_obs, avg_corners, gram2_lane_cost(two_per_simd, gen), force, max_waves, share);
 }
 
 // ---- ragged frames: the bins of one launch ------------------------------------------------------------------------------------
@@ -981,7 +962,6 @@ static double g2_launch_cost(const std::vector<double>& c, int simds, bool two_p
     }
     return worst;
 }
-static int g2_iter_lpf(int n_obs, int avg_corners);
 GramBins gram2_bin_plan(const int64_t* off, int n_obs, bool two_per_simd, std::vector<int32_t>* order, bool rig_list) {
     GramBins none;
 #ifdef CCAL_G2_NO_BINS        // A/B builds (tools/build_tu_variants.sh ccal_kernels_gram2 "nobins:-DCCAL_G2_NO_BINS"): the launch without bins
@@ -1025,7 +1005,7 @@ GramBins gram2_bin_plan(const int64_t* off, int n_obs, bool two_per_simd, std::v
     double cost_plain;
     {
         const int avg = (int)(total / std::max(n_obs, 1));
-        const int lpf = gram2_lanes_per_frame(n_obs, avg, two_per_simd, false, 0, (int64_t)1 << 40, 1), g = 64 / lpf;
+        const int lpf = gram2_lanes_per_frame(n_obs, avg, two_per_simd, false, 0, kNoWaveCap, 1), g = 64 / lpf;
         std::vector<double> c;
         for (int o = 0; o < n_obs; o += g) {
             int64_t mx = 0;
@@ -1077,7 +1057,7 @@ GramBins gram2_bin_plan(const int64_t* off, int n_obs, bool two_per_simd, std::v
         // two sizes ranges where the table's shape is not the model's to choose: the single-launch groups' 12 lanes, and 3 500 .. 8 192 frames
         // of clearly ragged sets, where the 16-lane fold was the best of every plan tried at 4 000, 5 000, 6 000, 7 000 and 8 000 frames
         // (20.8 / 23.0 / 24.5 / 25.8 / 26.7 us; the plain launch at 4 000 / 5 000: 22.5 / 25.3) and the model sees it only from 5 000
-        const bool iter12 = !rig_list && g2_iter_lpf(n_obs, (int)(total / std::max(n_obs, 1))) == 12;       // (a rig's Gram lists: the model's choice only)
+        const bool iter12 = !rig_list && g2_iter_applies(n_obs);       // (a rig's Gram lists: the model's choice only)
         const bool mid16 = !rig_list && !iter12 && n_obs > 3500 && n_obs <= 8192 && nmax <= 16 * 64 && (double)total <= 0.8 * (double)nmax * (double)n_obs;
         const int force_lpf = iter12 ? 12 : (mid16 ? 16 : 0);
         for (int b = 0; b < kGramMaxBins; ++b) {
@@ -1126,18 +1106,8 @@ GramBins gram2_bin_plan(const int64_t* off, int n_obs, bool two_per_simd, std::v
 // the binned launch: a.n_bins / a.bin_* filled in by the caller (single camera: make_fused_args, + a.bin_tab; rigs: launch_gram_dev, a.list sorted)
 template <int MODEL, bool OF, bool GEN>
 static hipError_t launch_gram2_binned(FusedArgs& a, hipStream_t s) {
-    constexpr int NS = g2_slices<MODEL>();
-    using Map = RowMap<MODEL, OF, GEN, NS>;
-    constexpr int K = block_dim(MODEL, OF, false) - 6, K1 = K + 1;
-    constexpr int LS = Map::CH | 1;
-    constexpr int GS_ = (praw_jl_off(K) + 9 + 6 * K1 + 1) & ~1;
     size_t lds = 0;
-    for (int b = 0; b < a.n_bins; ++b) {
-        const int G = 64 / a.bin_lpf[b];
-        const int RED = (!GEN && G * GS_ > 64 * LS) ? G * GS_ : 64 * LS;
-        const int WSL = (G * (FC_N0P + 12) + RED + Map::NEF + 1) & ~1;
-        lds = std::max(lds, sizeof(double) * WSL * CCAL_GRAMV_WPB);
-    }
+    for (int b = 0; b < a.n_bins; ++b) lds = std::max(lds, sizeof(double) * gram2_wave_lds<MODEL, OF, GEN>(a.bin_lpf[b]) * CCAL_GRAMV_WPB);
     void (*kern)(const FusedArgs) = GEN ? k_gram2g<MODEL, OF> : k_gram2b<MODEL, OF>;
     static DynLdsGuard lds_guard;
     if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds, lds_guard); e != hipSuccess) return e;
@@ -1156,64 +1126,28 @@ static hipError_t launch_gram2_t(FusedArgs& a, hipStream_t s) {
     } else {
         if (a.n_bins > 0 && !a.lpf_force) return launch_gram2_binned<MODEL, OF, true>(a, s);      // rigs: the list came sorted, with its bins
     }
-    const int lpf = gram2_lanes_per_frame(a.n_obs, a.avg_corners, CCAL_G2_MINW(MODEL) >= 2, GEN, a.lpf_force, (GEN || !a.fuse_elim) ? (int64_t)1 << 40 : a.part_cap, a.share);
-    const int waves = ((a.n_obs + 64 / lpf - 1) / (64 / lpf) + CCAL_GRAMV_WPB - 1) / CCAL_GRAMV_WPB * CCAL_GRAMV_WPB;
-    const bool fuse = !GEN && a.fuse_elim != 0 && waves <= a.part_cap;
-    a.fuse_elim = fuse ? 1 : 0;
-    a.elim_fused = fuse ? 1 : 0;
-    if (fuse) a.n_part = waves;
-    switch (lpf) {
-        case 6: return launch_gram2_l<MODEL, OF, 6, GEN>(a, s);
-        case 8: return launch_gram2_l<MODEL, OF, 8, GEN>(a, s);
-        case 12: return launch_gram2_l<MODEL, OF, 12, GEN>(a, s);
-        case 16: return launch_gram2_l<MODEL, OF, 16, GEN>(a, s);
-        case 32: return launch_gram2_l<MODEL, OF, 32, GEN>(a, s);
-        default: return launch_gram2_l<MODEL, OF, 64, GEN>(a, s);
-    }
+    const int lpf = gram2_lanes_per_frame(a.n_obs, a.avg_corners, CCAL_G2_MINW(MODEL) >= 2, GEN, a.lpf_force, fused_wave_cap(a, GEN), a.share);
+    set_fuse_plan(a, lpf, GEN);
+    return dispatch_lanes(lpf, hipErrorInvalidValue, [&](auto l) { return launch_gram2_l<MODEL, OF, decltype(l)::value, GEN>(a, s); });
 }
 // ---- single-launch groups on k_gram2i ------------------------------------------------------------------------------------------
 // Where it applies: UCM / EUCM (two wavefronts of 256 registers per SIMD), all wavefronts resident at once (<= 2 048) in <= 256
 // workgroups of eight 12-lane wavefronts - and at least 224 of them: a workgroup of eight wavefronts takes a whole compute unit, so
 // the form only pays where the launch fills the chip (profiles/r06/ab_g2_single_launch_groups.txt, GN with host pointers against
 // k_gram1v's single-launch form: 10 000 frames 0.237 against 0.253 ms, 8 000 - 16 lanes - 0.212 = 0.211, 5 000: 0.188 against 0.180,
-// 2 500: 0.168 against 0.147).  10 000 frames: 250 workgroups; the window is 8 960 .. 10 240 frames.
-constexpr int kG2IterWpb = 8;
-template <int MODEL, bool OF, int LPF>
-static constexpr size_t g2_iter_lds() {
-    constexpr int NS = g2_slices<MODEL>();
-    using Map = RowMap<MODEL, OF, false, NS>;
-    constexpr int G = 64 / LPF, K = block_dim(MODEL, OF, false) - 6, K1 = K + 1;
-    constexpr int LS = Map::CH | 1, GS_ = (praw_jl_off(K) + 9 + 6 * K1 + 1) & ~1;
-    constexpr int RED = (G * GS_ > 64 * LS) ? G * GS_ : 64 * LS;
-    constexpr int WSL = (G * (FC_N0P + 12) + RED + Map::NEF + 1) & ~1;
-    return sizeof(double) * WSL * kG2IterWpb;
-}
+// 2 500: 0.168 against 0.147).  10 000 frames: 250 workgroups; the window is g2_iter_applies (ccal_gram_plan.hpp): 8 921 .. 10 240 frames.
 template <int MODEL, bool OF>
 static constexpr size_t g2_iter_static_lds() { return sizeof(HeadShared) + 4 * 2 * 64 * 8 + 512; }      // decision + the row sum's 4 x 2 x 64 + alignment
-static int g2_iter_lpf(int n_obs, int avg_corners) {
-    int best = 0;
-    double best_cost = 1e300;
-    for (int lpf : { 12 }) {
-        const int g = 64 / lpf;
-        const int64_t waves = ((int64_t)n_obs + g - 1) / g, wgs = (waves + kG2IterWpb - 1) / kG2IterWpb;
-        if (waves > 2048 || wgs > 256 || wgs < 224) continue;
-        const double nw = (double)waves / 1024.0;
-        const double occ = nw <= 1.0 ? 1.0 : 1.0 + 0.3 * (nw - 1.0);
-        const double cost = occ * (6.0 + (std::max(avg_corners, 1) + lpf - 1) / lpf);
-        if (cost < best_cost) { best_cost = cost; best = lpf; }
-    }
-    return best;
-}
 template <int MODEL, bool OF>
-static int g2_iter_rows_t(int n_obs, int avg_corners, FusedArgs* a, hipStream_t s, hipError_t* err) {
-    const int lpf = g2_iter_lpf(n_obs, avg_corners);
-    if (!lpf) return 0;
-    const int g = 64 / lpf, rows = (int)((((int64_t)n_obs + g - 1) / g + kG2IterWpb - 1) / kG2IterWpb);
-    const size_t lds = g2_iter_lds<MODEL, OF, 12>();
-    if (lpf != 12 || lds + g2_iter_static_lds<MODEL, OF>() > 160 * 1024) return 0;
+static int g2_iter_rows_t(int n_obs, FusedArgs* a, hipStream_t s, hipError_t* err) {
+    if (!g2_iter_applies(n_obs)) return 0;
+    constexpr int LPF = kG2IterLpf, G = 64 / LPF;
+    const int rows = (int)((((int64_t)n_obs + G - 1) / G + kG2IterWpb - 1) / kG2IterWpb);
+    constexpr size_t lds = sizeof(double) * gram2_wave_lds<MODEL, OF, false>(LPF) * kG2IterWpb;
+    if (lds + g2_iter_static_lds<MODEL, OF>() > 160 * 1024) return 0;
     if (a) {
         const bool sorted = a->n_bins > 0 && a->bin_tab != nullptr;      // ragged frames: the sorted table of ccal_problem_create
-        void (*kern)(const FusedArgs) = sorted ? k_gram2i<MODEL, OF, 12, true> : k_gram2i<MODEL, OF, 12, false>;
+        void (*kern)(const FusedArgs) = sorted ? k_gram2i<MODEL, OF, LPF, true> : k_gram2i<MODEL, OF, LPF, false>;
         static DynLdsGuard guard_plain, guard_sorted;
         if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds, sorted ? guard_sorted : guard_plain); e != hipSuccess) { *err = e; return rows; }
         a->fuse_elim = 1; a->elim_fused = 1; a->n_part = rows;
@@ -1222,36 +1156,24 @@ static int g2_iter_rows_t(int n_obs, int avg_corners, FusedArgs* a, hipStream_t 
     }
     return rows;
 }
-static int g2_iter_rows_m(int model, bool one_focal, int n_obs, int avg_corners, int K, FusedArgs* a, hipStream_t s, hipError_t* err) {
+static int g2_iter_rows_m(int model, bool one_focal, int n_obs, int K, FusedArgs* a, hipStream_t s, hipError_t* err) {
     if (n_obs < 2000 || K != block_dim(model, one_focal, false) - 6) return 0;
-    switch (model * 2 + (one_focal ? 1 : 0)) {
-        case 0: return g2_iter_rows_t<kUCM, false>(n_obs, avg_corners, a, s, err);
-        case 1: return g2_iter_rows_t<kUCM, true>(n_obs, avg_corners, a, s, err);
-        case 2: return g2_iter_rows_t<kEUCM, false>(n_obs, avg_corners, a, s, err);
-        case 3: return g2_iter_rows_t<kEUCM, true>(n_obs, avg_corners, a, s, err);
-        default: return 0;                                 // KB4 / OPENCV5: one wavefront per SIMD - k_gram1v's single-launch form
-    }
+    return dispatch_model_focal(model, one_focal, 0, [&](auto m, auto of) {
+        constexpr int MODEL = decltype(m)::value;
+        if constexpr (MODEL == kKB4 || MODEL == kOCV5) return 0;       // one wavefront per SIMD - k_gram1v's single-launch form
+        else return g2_iter_rows_t<MODEL, decltype(of)::value>(n_obs, a, s, err);
+    });
 }
-int gram2_iter_rows(int model, bool one_focal, int n_obs, int avg_corners, int K) { return g2_iter_rows_m(model, one_focal, n_obs, avg_corners, K, nullptr, nullptr, nullptr); }
+int gram2_iter_rows(int model, bool one_focal, int n_obs, int /*avg_corners*/, int K) { return g2_iter_rows_m(model, one_focal, n_obs, K, nullptr, nullptr, nullptr); }
 hipError_t launch_gram2_iter(int model, bool one_focal, FusedArgs& a, hipStream_t s) {
     hipError_t err = hipErrorInvalidValue;
-    const int rows = g2_iter_rows_m(model, one_focal, a.n_obs, a.avg_corners, a.K, &a, s, &err);
+    const int rows = g2_iter_rows_m(model, one_focal, a.n_obs, a.K, &a, s, &err);
     return rows > 0 ? err : hipErrorInvalidValue;
 }
 
 template <bool GEN>
 static hipError_t launch_gram2_m(int model, bool one_focal, FusedArgs& a, hipStream_t s) {
-    switch (model * 2 + (one_focal ? 1 : 0)) {
-        case 0: return launch_gram2_t<kUCM, false, GEN>(a, s);
-        case 1: return launch_gram2_t<kUCM, true, GEN>(a, s);
-        case 2: return launch_gram2_t<kEUCM, false, GEN>(a, s);
-        case 3: return launch_gram2_t<kEUCM, true, GEN>(a, s);
-        case 4: return launch_gram2_t<kKB4, false, GEN>(a, s);
-        case 5: return launch_gram2_t<kKB4, true, GEN>(a, s);
-        case 6: return launch_gram2_t<kOCV5, false, GEN>(a, s);
-        case 7: return launch_gram2_t<kOCV5, true, GEN>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_model_focal(model, one_focal, hipErrorInvalidValue, [&](auto m, auto of) { return launch_gram2_t<decltype(m)::value, decltype(of)::value, GEN>(a, s); });
 }
 // single-camera loop; a.fuse_elim in: fusion allowed, out: fusion done (then a.n_part = rows of partial sums, a.elim_fused = 1)
 hipError_t launch_gram2(int model, bool one_focal, FusedArgs& a, hipStream_t s) { return launch_gram2_m<false>(model, one_focal, a, s); }

@@ -6,6 +6,7 @@
 
 #include "ccal_device.hpp"
 #include "ccal_fused.hpp"
+#include "ccal_gram_plan.hpp"
 
 namespace ccal {
 
@@ -225,22 +226,6 @@ static hipError_t launch_gram_t(const GramArgs& ga, hipStream_t s) {
 
 #endif  // CCAL_LEGACY_KERNELS
 
-#define CCAL_DISPATCH(FN, model, of, other, ...)                                                     \
-    do {                                                                                             \
-        const int key_ = (model) * 4 + ((of) ? 2 : 0) + ((other) ? 1 : 0);                           \
-        switch (key_) {                                                                              \
-            case 0: return FN<kUCM, false, false>(__VA_ARGS__);   case 1: return FN<kUCM, false, true>(__VA_ARGS__);   \
-            case 2: return FN<kUCM, true, false>(__VA_ARGS__);    case 3: return FN<kUCM, true, true>(__VA_ARGS__);    \
-            case 4: return FN<kEUCM, false, false>(__VA_ARGS__);  case 5: return FN<kEUCM, false, true>(__VA_ARGS__);  \
-            case 6: return FN<kEUCM, true, false>(__VA_ARGS__);   case 7: return FN<kEUCM, true, true>(__VA_ARGS__);   \
-            case 8: return FN<kKB4, false, false>(__VA_ARGS__);   case 9: return FN<kKB4, false, true>(__VA_ARGS__);   \
-            case 10: return FN<kKB4, true, false>(__VA_ARGS__);   case 11: return FN<kKB4, true, true>(__VA_ARGS__);   \
-            case 12: return FN<kOCV5, false, false>(__VA_ARGS__); case 13: return FN<kOCV5, false, true>(__VA_ARGS__); \
-            case 14: return FN<kOCV5, true, false>(__VA_ARGS__);  case 15: return FN<kOCV5, true, true>(__VA_ARGS__);  \
-            default: return hipErrorInvalidValue;                                                    \
-        }                                                                                            \
-    } while (0)
-
 hipError_t launch_gram(const ccal_problem* p, int cam, bool cand, int gbuf, hipStream_t s) {
 #ifndef CCAL_LEGACY_KERNELS
     (void)p; (void)cam; (void)cand; (void)gbuf; (void)s;
@@ -255,7 +240,9 @@ hipError_t launch_gram(const ccal_problem* p, int cam, bool cand, int gbuf, hipS
     a.intr = cand ? p->d_intr_c : p->d_intr; a.poses = cand ? p->d_poses_c : p->d_poses; a.extr = cand ? p->d_extr_c : p->d_extr;
     a.huber_delta = p->huber_delta; a.rt = model_rt(p->ctx);
     ga.goff = w->d_goff; ga.G = w->G[gbuf]; ga.cost_o = w->cost_o[gbuf];
-    CCAL_DISPATCH(launch_gram_t, p->cams[cam].model, p->one_focal, cam > 0, ga, s);
+    return dispatch_model_focal_other(p->cams[cam].model, p->one_focal, cam > 0, hipErrorInvalidValue, [&](auto m, auto of, auto other) {
+        return launch_gram_t<decltype(m)::value, decltype(of)::value, decltype(other)::value>(ga, s);
+    });
 #endif
 }
 // device-resident loop: set 0 = (p->d_*, G[w->cur]), set 1 = (p->d_*_c, G[w->cur ^ 1])
@@ -276,27 +263,33 @@ static void set_gen_bins(FusedArgs& fa, const NormalWs* w, int slot) {
     for (int b = 0; b < kGramMaxBins; ++b) { fa.bin_lpf[b] = gb.lpf[b]; fa.bin_first[b] = gb.first[b]; fa.bin_count[b] = gb.count[b]; fa.bin_wg0[b] = gb.wg0[b]; }
     fa.bin_wg0[kGramMaxBins] = gb.wg0[kGramMaxBins];
 }
+// what the register Gram launches of the general loop share; cam: the camera whose intrinsics and block size the launch starts from
+static FusedArgs gen_fused_args(const ccal_problem* p, int cam, const DevState* st) {
+    const NormalWs* w = p->nws;
+    FusedArgs fa = {};
+    fa.x = p->d_x; fa.y = p->d_y; fa.z = p->d_z; fa.u = p->d_u; fa.v = p->d_v;
+    fa.obs_off = p->d_obs_off; fa.obs_slot = p->d_obs_slot; fa.rec_off = w->d_goff;
+    fa.K = p->cams[cam].Peff; fa.huber_delta = p->huber_delta; fa.rt = model_rt(p->ctx);
+    fa.intr[0] = p->d_intr + cam * CCAL_PMAX; fa.intr[1] = p->d_intr_c + cam * CCAL_PMAX;
+    fa.poses[0] = p->d_poses; fa.poses[1] = p->d_poses_c;
+    fa.extr[0] = p->d_extr; fa.extr[1] = p->d_extr_c; fa.cam = cam;
+    fa.praw[0] = w->G[w->cur]; fa.praw[1] = w->G[w->cur ^ 1];
+    fa.st = st;
+    if (st && w->gen_backsub) {          // device-resident loop: the candidate poses are formed in the kernel's prologue
+        fa.gen_backsub = 1; fa.g_K = w->K; fa.g_PF = w->PF; fa.g_pf = w->pf; fa.g_dc = w->dc; fa.g_mc_slot = w->mc_slot;
+        fa.g_owner = w->d_obs_owner; fa.min_diag = w->lm_min_diag; fa.max_diag = w->lm_max_diag;
+    }
+    fa.avg_corners = (int32_t)(p->n_corners / std::max(p->n_obs, 1));
+    return fa;
+}
 // cam < 0: the merged launch (w->merged_gram)
 hipError_t launch_gram_dev(const ccal_problem* p, int cam, const DevState* st, hipStream_t s) {
     const NormalWs* w = p->nws;
     if (w->register_gram && cam < 0) {
         // Two launches of 2 000 wavefronts each leave the FP64 pipes half empty twice (the second wavefront of every SIMD
         // runs alone for its last ~9 us); one launch refills the slot of a finished wavefront at once
-        FusedArgs fa = {};
-        fa.x = p->d_x; fa.y = p->d_y; fa.z = p->d_z; fa.u = p->d_u; fa.v = p->d_v;
-        fa.obs_off = p->d_obs_off; fa.obs_slot = p->d_obs_slot;
-        fa.list = w->d_all_obs; fa.n_obs = p->n_obs; fa.rec_off = w->d_goff; fa.obs_cam = w->d_obs_cam;
-        fa.K = p->cams[0].Peff; fa.huber_delta = p->huber_delta; fa.rt = model_rt(p->ctx);
-        fa.intr[0] = p->d_intr; fa.intr[1] = p->d_intr_c;
-        fa.poses[0] = p->d_poses; fa.poses[1] = p->d_poses_c;
-        fa.extr[0] = p->d_extr; fa.extr[1] = p->d_extr_c; fa.cam = 0;
-        fa.praw[0] = w->G[w->cur]; fa.praw[1] = w->G[w->cur ^ 1];
-        fa.st = st;
-        if (st && w->gen_backsub) {          // device-resident loop: the candidate poses are formed in the kernel's prologue
-            fa.gen_backsub = 1; fa.g_K = w->K; fa.g_PF = w->PF; fa.g_pf = w->pf; fa.g_dc = w->dc; fa.g_mc_slot = w->mc_slot;
-            fa.g_owner = w->d_obs_owner; fa.min_diag = w->lm_min_diag; fa.max_diag = w->lm_max_diag;
-        }
-        fa.avg_corners = (int32_t)(p->n_corners / std::max(p->n_obs, 1));
+        FusedArgs fa = gen_fused_args(p, 0, st);
+        fa.list = w->d_all_obs; fa.n_obs = p->n_obs; fa.obs_cam = w->d_obs_cam;
         set_gen_bins(fa, w, 0);
         return launch_gram1v_general(p->cams[0].model, p->one_focal, fa, s);
     }
@@ -304,21 +297,8 @@ hipError_t launch_gram_dev(const ccal_problem* p, int cam, const DevState* st, h
         // every camera's blocks (6 + P_eff + 1 columns at the composed pose: a triangle of <= 136 entries) through the
         // register Gram kernels of the single-camera loop, record format; k_schur expands the records (caminfo NCP = 0).
         // Two EUCM cameras x 10 000 frames: 32 + 60 us (matrix-core kernel for camera 1, 19 columns) -> 2 x ~32 us
-        FusedArgs fa = {};
-        fa.x = p->d_x; fa.y = p->d_y; fa.z = p->d_z; fa.u = p->d_u; fa.v = p->d_v;
-        fa.obs_off = p->d_obs_off; fa.obs_slot = p->d_obs_slot;
-        fa.list = p->cams[cam].d_obs; fa.n_obs = (int32_t)p->cams[cam].obs.size(); fa.rec_off = w->d_goff;
-        fa.K = p->cams[cam].Peff; fa.huber_delta = p->huber_delta; fa.rt = model_rt(p->ctx);
-        fa.intr[0] = p->d_intr + cam * CCAL_PMAX; fa.intr[1] = p->d_intr_c + cam * CCAL_PMAX;
-        fa.poses[0] = p->d_poses; fa.poses[1] = p->d_poses_c;
-        fa.extr[0] = p->d_extr; fa.extr[1] = p->d_extr_c; fa.cam = cam;
-        fa.praw[0] = w->G[w->cur]; fa.praw[1] = w->G[w->cur ^ 1];
-        fa.st = st;
-        if (st && w->gen_backsub) {          // device-resident loop: the candidate poses are formed in the kernel's prologue
-            fa.gen_backsub = 1; fa.g_K = w->K; fa.g_PF = w->PF; fa.g_pf = w->pf; fa.g_dc = w->dc; fa.g_mc_slot = w->mc_slot;
-            fa.g_owner = w->d_obs_owner; fa.min_diag = w->lm_min_diag; fa.max_diag = w->lm_max_diag;
-        }
-        fa.avg_corners = (int32_t)(p->n_corners / std::max(p->n_obs, 1));
+        FusedArgs fa = gen_fused_args(p, cam, st);
+        fa.list = p->cams[cam].d_obs; fa.n_obs = (int32_t)p->cams[cam].obs.size();
         set_gen_bins(fa, w, 1 + cam);
         return launch_gram1v_general(p->cams[cam].model, p->one_focal, fa, s);
     }
@@ -335,7 +315,9 @@ hipError_t launch_gram_dev(const ccal_problem* p, int cam, const DevState* st, h
     a.huber_delta = p->huber_delta; a.rt = model_rt(p->ctx);
     ga.goff = w->d_goff; ga.G = w->G[w->cur]; ga.cost_o = w->cost_o[w->cur]; ga.G2 = w->G[w->cur ^ 1]; ga.cost_o2 = w->cost_o[w->cur ^ 1];
     ga.st = st;
-    CCAL_DISPATCH(launch_gram_t, p->cams[cam].model, p->one_focal, cam > 0, ga, s);
+    return dispatch_model_focal_other(p->cams[cam].model, p->one_focal, cam > 0, hipErrorInvalidValue, [&](auto m, auto of, auto other) {
+        return launch_gram_t<decltype(m)::value, decltype(of)::value, decltype(other)::value>(ga, s);
+    });
 #endif
 }
 

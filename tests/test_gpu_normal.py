@@ -391,9 +391,10 @@ sys.path.insert(0, {root!r})
 from camera_intrinsic_calibration_rs_amd import _ffi, synth
 from camera_intrinsic_calibration_rs_amd.engine import Context, Problem, default_opts
 from oracle import binding as ob
-ctx = Context(0, lib=_ffi.load_for_switches())          # CCAL_GRAMV_LPF: a switch of the second library
-for n_frames, model in ((300, "eucm"), (2600, "eucm"), (2600, "ucm"), (700, "kb4")):
-    sp = synth.make_problem(n_frames, model, ragged=True, outlier_frac=0.01)
+ctx = Context(0, lib=_ffi.load_for_switches())          # CCAL_GRAMV_LPF / CCAL_GRAM2_LPF: switches of the second library
+for n_frames, model, one_focal in ((300, "eucm", False), (2600, "eucm", False), (2600, "ucm", False), (700, "kb4", False),
+                                   (300, "kb4", True), (2600, "eucm", True)):
+    sp = synth.make_problem(n_frames, model, ragged=True, outlier_frac=0.01, xy_same_focal=one_focal)
     gp = Problem.from_synth(ctx, sp); op = ob.OracleProblem.from_synth(sp)
     S, b, c = gp.build_normal(sp.intr0, sp.poses0, lam=1e-3); So, bo, co = op.build_normal(sp.intr0, sp.poses0, lam=1e-3)
     assert abs(c - co) <= 1e-12 * co and np.abs(S - So).max() <= 1e-9 * np.abs(So).max() and np.abs(b - bo).max() <= 1e-9 * np.abs(bo).max()
@@ -410,11 +411,12 @@ print("LPF-OK")
 @pytest.mark.parametrize("lpf", [6, 8, 12, 16, 32, 64])
 def test_gram_lanes_per_frame_every_mapping(lpf):
     """Every lanes-per-frame mapping of the register Gram kernels (6 and 12 - ten / five frames per wavefront, four lanes
-    idle -, 8, 16, 32, 64) forced through CCAL_GRAMV_LPF (read once per process, hence the subprocess), ragged frames, with damping
+    idle -, 8, 16, 32, 64) forced through CCAL_GRAMV_LPF (k_gram1v: the cases below 2 000 frames) and CCAL_GRAM2_LPF (k_gram2's plain
+    launch: the 2 600-frame cases) - both read once per process, hence the subprocess -, both focal modes, ragged frames, with damping
     (the per-frame phi -> rvec map only shows under damping: the undamped Schur complement is basis invariant)."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, CCAL_GRAMV_LPF=str(lpf))
+    env = dict(os.environ, CCAL_GRAMV_LPF=str(lpf), CCAL_GRAM2_LPF=str(lpf))
     out = subprocess.run([sys.executable, "-c", _LPF_SCRIPT.format(root=root)], env=env, capture_output=True, text=True, timeout=600)
     assert "LPF-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
 
