@@ -175,7 +175,7 @@ def test_validation_statistics_are_order_statistics(gpu_ctx, oracle):
             assert abs(res[0][0] - ao) < 1e-11 and abs(res[0][1] - mo) < 1e-11
         gp.close()
     assert res[0] == res[1] == res[2]                                           # bit for bit, whatever the order of the frames
-    # above 2^17 values the selection is the multi-launch form (one histogram launch per digit): same definition, same checks
+    # above 2^13 values (kSelOneMax) the selection is the multi-launch form (one histogram launch per digit): same definition, same checks
     big = synth.make_problem(1000, "kb4", outlier_frac=0.01, seed=78)
     gp = Problem.from_synth(gpu_ctx, big)
     a, m = gp.validation(0, big.intr0, big.poses0)
