@@ -7,40 +7,16 @@
 #include <memory>
 #include <new>
 
-#include "ccal_internal.hpp"
+#include "ccal_call.hpp"
 #include "ccal_normal.hpp"
 
 using namespace ccal;
-
-#define HIP_TRY(ctx, expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
-            return CCAL_ERR_HIP;                                                                   \
-        }                                                                                          \
-    } while (0)
 
 // the context stream has just been synchronised: whatever early-exit groups a finished solve left in it are gone
 static void stream_synced(ccal_problem* p) {
     if (!p->nws) return;
     p->nws->tail_pending = false;
     if (p->nws->fws) p->nws->fws->tail_pending = false;
-}
-
-static int fail(ccal_ctx* ctx, int code, const char* msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
-
-// One element of slack behind every array: the Gram / eval kernels request a frame's first corner row before they look at
-// its corner count (software prefetch), which for an EMPTY last frame is index n - one past the data, inside the allocation.
-template <class T>
-static int upload(ccal_ctx* ctx, T** dst, const T* src, size_t n) {
-    HIP_TRY(ctx, hipMalloc((void**)dst, (n + 1) * sizeof(T)));
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(*dst + n, 0, sizeof(T), ctx->stream));
-    return CCAL_OK;
 }
 
 static void default_conventions(ccal_model_conventions* cv) {
@@ -239,13 +215,6 @@ int ccal_problem_create(ccal_ctx* ctx, const ccal_problem_desc* d, ccal_problem*
         for (size_t i = 0; i < nc; ++i) { uint32_t b; std::memcpy(&b, d->p3d_z + i, sizeof b); any |= b & 0x7fffffffu; }
         p->has_nonplanar = any != 0;
     }
-    // ONE device allocation, cleared once, sliced (a calibration session creates its problem once: sixteen hipMalloc + memset pairs
-    // were a third of ccal_problem_create's 0.25 ms at 600 frames).  One element of slack behind every uploaded array, as upload().
-    const size_t ni = (size_t)d->n_cams * CCAL_PMAX, np6 = (size_t)std::max(d->n_slots, 1) * 6, ne = (size_t)d->n_cams * 6;
-    auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t total = 5 * up256((nc + 1) * sizeof(float)) + 2 * up256((p->h_obs_off.size() + 1) * sizeof(int64_t)) +
-                   2 * up256((p->h_obs_cam.size() + 1) * sizeof(int32_t)) + 2 * (up256(ni * 8) + up256(np6 * 8) + up256(ne * 8));
-    for (int c = 0; c < d->n_cams; ++c) total += up256((p->cams[c].obs.size() + 1) * sizeof(int32_t));
     // single camera, ragged frames (real sessions: 24 .. 144 corners per frame, src/data_loader.rs:15): the Gram launch works on bins of
     // frames sorted by corner count, each bin with the lanes per frame its frames need (ccal_kernels_gram2.hip); the sorted table -
     // { frame, first corner, corners, slot } per position - is made once, here
@@ -261,9 +230,14 @@ int ccal_problem_create(ccal_ctx* ctx, const ccal_problem_desc* d, ccal_problem*
                 bin_tab[4 * (size_t)i] = o; bin_tab[4 * (size_t)i + 1] = (int32_t)p->h_obs_off[o];
                 bin_tab[4 * (size_t)i + 2] = (int32_t)(p->h_obs_off[o + 1] - p->h_obs_off[o]); bin_tab[4 * (size_t)i + 3] = p->h_obs_slot[o];
             }
-            total += up256((bin_tab.size() + 1) * sizeof(int32_t));
         }
     }
+    // ONE device allocation, sliced (a calibration session creates its problem once: sixteen hipMalloc + memset pairs were a third of
+    // ccal_problem_create's 0.25 ms at 600 frames): ProblemLayout, ccal_internal.hpp
+    size_t cam_obs[CCAL_MAX_CAMS];
+    for (int c = 0; c < d->n_cams; ++c) cam_obs[c] = p->cams[c].obs.size();
+    const ProblemLayout l((size_t)p->n_corners, (size_t)d->n_obs, (size_t)d->n_slots, d->n_cams, cam_obs, bin_tab.size());
+    const size_t total = l.plan.total;
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_block, total));
     // Session-sized problems (up to 8 MB of inputs) are packed into ONE pinned staging block laid out like the device block and
     // uploaded with ONE copy: ten hipMemcpyAsync calls from pageable memory - each staged by the runtime on its own - were
@@ -274,40 +248,31 @@ int ccal_problem_create(ccal_ctx* ctx, const ccal_problem_desc* d, ccal_problem*
     if (total <= ((size_t)8 << 20)) HIP_TRY(ctx, ctx_host_alloc(ctx, (void**)&h_pack, total));
     if (!h_pack) HIP_TRY(ctx, hipMemsetAsync(p->d_block, 0, total, ctx->stream));
     {
-        char* q = p->d_block;
-        auto put = [&](auto** dst, const auto* src, size_t n) -> hipError_t {
-            using T = std::remove_pointer_t<std::remove_pointer_t<decltype(dst)>>;
-            *dst = reinterpret_cast<T*>(q);
-            const size_t room = up256((n + 1) * sizeof(T));
-            if (h_pack) {                 // (the slack behind the data must be zeros: the kernels load - and mask - one element past an empty last frame)
-                char* h = h_pack + (q - p->d_block);
-                const size_t nb = (n && src) ? n * sizeof(T) : 0;
-                if (nb) std::memcpy(h, src, nb);
-                std::memset(h + nb, 0, room - nb);
-                q += room;
-                return hipSuccess;
-            }
-            q += room;
-            return (n && src) ? hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+        const Bound dev{ p->d_block }, img{ h_pack };
+        auto put = [&](auto** dst, auto slice, const auto* src, size_t n) -> hipError_t {
+            *dst = dev.at(slice);
+            const size_t nb = src ? n * sizeof(*src) : 0;
+            if (!h_pack) return nb ? hipMemcpyAsync(*dst, src, nb, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+            if (nb) std::memcpy(img.at(slice), src, nb);       // (the slack behind the data must be zeros: the kernels load - and mask - one element past an empty last frame)
+            if (slice.bytes) std::memset((char*)img.at(slice) + nb, 0, slice.bytes - nb);
+            return hipSuccess;
         };
-        HIP_TRY(ctx, put(&p->d_x, d->p3d_x, nc)); HIP_TRY(ctx, put(&p->d_y, d->p3d_y, nc)); HIP_TRY(ctx, put(&p->d_z, d->p3d_z, nc));
-        HIP_TRY(ctx, put(&p->d_u, d->p2d_u, nc)); HIP_TRY(ctx, put(&p->d_v, d->p2d_v, nc));
-        HIP_TRY(ctx, put(&p->d_obs_off, (const int64_t*)p->h_obs_off.data(), p->h_obs_off.size()));
-        HIP_TRY(ctx, put(&p->d_joff, (const int64_t*)p->h_joff.data(), p->h_joff.size()));
-        HIP_TRY(ctx, put(&p->d_obs_cam, (const int32_t*)p->h_obs_cam.data(), p->h_obs_cam.size()));
-        HIP_TRY(ctx, put(&p->d_obs_slot, (const int32_t*)p->h_obs_slot.data(), p->h_obs_slot.size()));
-        for (int c = 0; c < d->n_cams; ++c) HIP_TRY(ctx, put(&p->cams[c].d_obs, (const int32_t*)p->cams[c].obs.data(), p->cams[c].obs.size()));
-        if (!bin_tab.empty()) HIP_TRY(ctx, put(&p->d_bin_tab, (const int32_t*)bin_tab.data(), bin_tab.size()));
-        double** bufs[6] = { &p->d_intr, &p->d_poses, &p->d_extr, &p->d_intr_c, &p->d_poses_c, &p->d_extr_c };
-        const size_t sz[6] = { ni, np6, ne, ni, np6, ne };
-        const size_t packed = (size_t)(q - p->d_block);                     // the uploaded arrays; the parameter sets behind them start as zeros
-        for (int i = 0; i < 6; ++i) { *bufs[i] = reinterpret_cast<double*>(q); q += up256(sz[i] * 8); }
-        if ((size_t)(q - p->d_block) > total) return fail(ctx, CCAL_ERR_HIP, "problem block layout");
+        HIP_TRY(ctx, put(&p->d_x, l.x, d->p3d_x, nc)); HIP_TRY(ctx, put(&p->d_y, l.y, d->p3d_y, nc)); HIP_TRY(ctx, put(&p->d_z, l.z, d->p3d_z, nc));
+        HIP_TRY(ctx, put(&p->d_u, l.u, d->p2d_u, nc)); HIP_TRY(ctx, put(&p->d_v, l.v, d->p2d_v, nc));
+        HIP_TRY(ctx, put(&p->d_obs_off, l.obs_off, p->h_obs_off.data(), p->h_obs_off.size()));
+        HIP_TRY(ctx, put(&p->d_joff, l.joff, p->h_joff.data(), p->h_joff.size()));
+        HIP_TRY(ctx, put(&p->d_obs_cam, l.obs_cam, p->h_obs_cam.data(), p->h_obs_cam.size()));
+        HIP_TRY(ctx, put(&p->d_obs_slot, l.obs_slot, p->h_obs_slot.data(), p->h_obs_slot.size()));
+        for (int c = 0; c < d->n_cams; ++c) HIP_TRY(ctx, put(&p->cams[c].d_obs, l.cam_obs[c], p->cams[c].obs.data(), p->cams[c].obs.size()));
+        HIP_TRY(ctx, put(&p->d_bin_tab, l.bin_tab, bin_tab.data(), bin_tab.size()));
+        p->d_intr = dev.at(l.intr); p->d_poses = dev.at(l.poses); p->d_extr = dev.at(l.extr);      // the parameter sets behind the uploaded arrays start as zeros
+        p->d_intr_c = dev.at(l.intr_c); p->d_poses_c = dev.at(l.poses_c); p->d_extr_c = dev.at(l.extr_c);
         if (h_pack) {
-            HIP_TRY(ctx, hipMemcpyAsync(p->d_block, h_pack, packed, hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(p->d_block + packed, 0, total - packed, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(p->d_block, h_pack, l.uploaded, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(p->d_block + l.uploaded, 0, total - l.uploaded, ctx->stream));
         }
     }
+    const size_t ni = (size_t)d->n_cams * CCAL_PMAX;
     p->lo.assign(ni, 0.0); p->hi.assign(ni, 0.0); p->has_bound.assign(ni, 0); p->fixed.assign(ni, 0);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, CCAL_ERR_HIP, "upload failed");
     p->counted = true;
@@ -465,14 +430,8 @@ int ccal_eval(ccal_problem* p, const double* intr, const double* poses, const do
     ccal_ctx* ctx = p->ctx;
     int rc = ccal_upload_params(p, intr, poses, extr);
     if (rc != CCAL_OK) return rc;
-    if (!p->d_r) {
-        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_r, sizeof(double) * std::max<int64_t>(2 * p->n_corners, 2)));
-        HIP_TRY(ctx, test_poison_f64(ctx, p->d_r, sizeof(double) * std::max<int64_t>(2 * p->n_corners, 2), false, ctx->stream));
-    }
-    if (!p->d_J) {
-        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_J, sizeof(double) * std::max<int64_t>(p->j_len, 2)));
-        HIP_TRY(ctx, test_poison_f64(ctx, p->d_J, sizeof(double) * std::max<int64_t>(p->j_len, 2), false, ctx->stream));
-    }
+    HIP_TRY(ctx, ctx_doubles(ctx, &p->d_r, (size_t)std::max<int64_t>(2 * p->n_corners, 2)));
+    HIP_TRY(ctx, ctx_doubles(ctx, &p->d_J, (size_t)std::max<int64_t>(p->j_len, 2)));
     rc = ccal_eval_dev(p, apply_loss, p->d_r, p->d_J);
     if (rc != CCAL_OK) return rc;
     if (p->n_corners) {
@@ -485,15 +444,13 @@ int ccal_eval(ccal_problem* p, const double* intr, const double* poses, const do
 
 }  // extern "C"
 namespace ccal {
-int reprojection_errors_dev(ccal_problem* p, const double* intr, const double* poses, const double* extr) {
+int reprojection_errors_dev(ccal_problem* p, const double* intr, const double* poses, const double* extr, int only_cam) {
     ccal_ctx* ctx = p->ctx;
     int rc = ccal_upload_params(p, intr, poses, extr);
     if (rc != CCAL_OK) return rc;
-    if (!p->d_err) {
-        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1)));
-        HIP_TRY(ctx, test_poison_f64(ctx, p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1), false, ctx->stream));
-    }
+    HIP_TRY(ctx, ctx_doubles(ctx, &p->d_err, (size_t)std::max<int64_t>(p->n_corners, 1)));
     for (int c = 0; c < p->n_cams; ++c) {
+        if (only_cam >= 0 && c != only_cam) continue;
         KArgs a = make_args(p, c);
         a.err_out = p->d_err;
         HIP_TRY(ctx, launch_reproj_err(p, c, a, ctx->stream));
@@ -521,16 +478,10 @@ int ccal_init_poses(ccal_problem* p, const double* intr, int min_points, double*
     if (rc != CCAL_OK) return rc;
     const size_t no = (size_t)std::max(p->n_obs, 1);
     // the two temporaries are slices of the problem's scratch block (kept for the next call: no hipMalloc / hipFree pair per call)
-    const size_t b_po = (no * 6 * sizeof(double) + 255) & ~(size_t)255, b_va = (no * sizeof(int32_t) + 255) & ~(size_t)255;
-    if (p->scratch_bytes < b_po + b_va) {
-        if (p->d_scratch) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); ctx_release(ctx, p->d_scratch, false); p->d_scratch = nullptr; p->scratch_bytes = 0; }
-        const size_t want = std::max(b_po + b_va, problem_scratch_hint(p));       // (room for validation()'s temporaries too: growing the block later costs a free)
-        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_scratch, want));
-        p->scratch_bytes = want;
-        HIP_TRY(ctx, test_poison_f64(ctx, p->d_scratch, b_po, false, ctx->stream));      // (the poses slice; not the counts behind it)
-    }
-    double* d_po = reinterpret_cast<double*>(p->d_scratch);
-    int32_t* d_va = reinterpret_cast<int32_t*>(p->d_scratch + b_po);
+    const PoseScratch l((size_t)p->n_obs);
+    HIP_TRY(ctx, ensure_scratch(p, l.plan));
+    double* d_po = Bound{ p->d_scratch }.at(l.poses);
+    int32_t* d_va = Bound{ p->d_scratch }.at(l.counts);
     hipError_t e = hipMemsetAsync(d_va, 0, no * sizeof(int32_t), ctx->stream);
     for (int c = 0; c < p->n_cams && e == hipSuccess; ++c) e = launch_pose_init(p, c, p->d_intr, d_po, d_va, min_points, ctx->stream);
     if (e == hipSuccess && p->n_obs) {
@@ -549,15 +500,8 @@ int ccal_validation(ccal_problem* p, int cam, const double* intr, const double* 
     if (!p || cam < 0 || cam >= p->n_cams || !avg_99 || !median || !intr || (!poses && p->n_slots) || (!extr && p->n_cams > 1)) return CCAL_ERR_INVALID_ARG;
     ccal_ctx* ctx = p->ctx;
     if (p->cams[cam].obs.empty()) return fail(ctx, CCAL_ERR_INVALID_ARG, "camera has no observations");
-    int rc = ccal_upload_params(p, intr, poses, extr);
+    int rc = reprojection_errors_dev(p, intr, poses, extr, cam);
     if (rc != CCAL_OK) return rc;
-    if (!p->d_err) {
-        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1)));
-        HIP_TRY(ctx, test_poison_f64(ctx, p->d_err, sizeof(double) * std::max<int64_t>(p->n_corners, 1), false, ctx->stream));
-    }
-    KArgs a = make_args(p, cam);
-    a.err_out = p->d_err;
-    HIP_TRY(ctx, launch_reproj_err(p, cam, a, ctx->stream));
     HIP_TRY(ctx, validation_stats_device(p, cam, p->d_err, avg_99, median, ctx->stream));     // gather + radix sort + sums on the device
     return CCAL_OK;
 }

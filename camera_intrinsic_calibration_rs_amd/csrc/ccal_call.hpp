@@ -1,6 +1,6 @@
 // One-shot batch calls (host arrays in, host arrays out): ONE device block of the context's allocator, cut into slices that each
 // start on a 256-byte boundary; uploads, the launch, downloads and one synchronise, all on the context's stream.
-//   CallPlan   the slices in order and the total - plain arithmetic, no context and no HIP call (tests/test_call_block_cpu.py)
+//   CallPlan   the slices in order and the total - plain arithmetic, no context and no HIP call (ccal_plan.hpp)
 //   CallBlock  the plan, the block and a sticky hipError_t: after the first failure every step is a no-op and finish() reports it;
 //              the destructor drains the stream before the block goes back to the context's cache, on every way out
 //   check_offsets  the argument check of a batched call's CSR offsets, with the call's name in the message
@@ -8,6 +8,7 @@
 #pragma once
 #include <cstdio>
 #include "ccal_internal.hpp"
+#include "ccal_plan.hpp"
 
 namespace ccal {
 
@@ -30,18 +31,6 @@ inline int check_offsets(ccal_ctx* ctx, const char* where, const char* name, con
     snprintf(msg, sizeof msg, bad, where, name);
     return fail(ctx, CCAL_ERR_INVALID_ARG, msg);
 }
-
-template <class T> struct Slice { size_t off = 0, bytes = 0; };        // bytes: rounded up; 0 = absent (an optional output not asked for)
-
-struct CallPlan {
-    size_t total = 0;
-    static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-    template <class T> Slice<T> add(size_t count) {
-        const Slice<T> s{ total, up256(count * sizeof(T)) };
-        total += s.bytes;
-        return s;
-    }
-};
 
 class CallBlock : public CallPlan {
     ccal_ctx* ctx;

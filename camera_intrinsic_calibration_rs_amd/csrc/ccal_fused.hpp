@@ -17,39 +17,6 @@
 
 namespace ccal {
 
-struct DevState {                 // lives in device memory; updated by the decision kernels only (sizeof % 8 == 0)
-    double lambda;                // damping of the system to solve next (0 for GN)
-    double lambda_spec;           // LM: damping of the speculative elimination at the candidate
-    double lambda_solve;          // damping that produced the current dc (model decrease of the pose blocks)
-    double radius, dec;
-    double cur_cost, last_cost, initial_cost;
-    double mc_cam;                // model decrease of the camera block for the current dc
-    double min_error, min_abs, min_rel;
-    int32_t cur;                  // parameter set (0/1) holding the accepted point
-    int32_t first;                // 1 until the starting point has been evaluated
-    int32_t redo;                 // 1: the next group re-eliminates the accepted set with `lambda` (no evaluation, no decision)
-    int32_t done;                 // 0 = running, else ccal_status + 1
-    int32_t iter, max_iter, method;
-    int32_t lm_accepted, lm_rejected;
-    int32_t sys_failed;           // a pose block of the system that produced the candidate was not positive definite (any rank)
-    int32_t cam_failed;           // the camera system that produced the candidate was not positive definite
-    int32_t done_seq;             // sequence number of the step that set `done` (0 while running)
-    int32_t spec_hits, spec_misses;   // LM: accepted steps whose speculative elimination was / was not the next system
-    int32_t error_metric;         // ccal_solver_opts::error_metric: what the stop rules compare (0: cost, 1: its square root)
-    int32_t pad_;
-};
-static_assert(sizeof(DevState) % 8 == 0, "DevState is staged as doubles");
-
-struct HostStatus {               // pinned, host-coherent; written at the end of a decision kernel
-    // what the polling host needs after EVERY group, in one 8-byte store (no fence, no second word to order against):
-    // bits 0-23 sequence number of the group, 24-31 `done` (0 = running, else ccal_status + 1), 32-55 the sequence number
-    // of the step that set `done` - the host acts on `done` only once it has waited for that step
-    volatile uint64_t word;
-    // the rest is published (behind a system-scope fence, before `word`) only by the group that finishes the solve
-    volatile int32_t iter, cur, lm_accepted, lm_rejected;
-    volatile int32_t spec_hits, spec_misses;
-    volatile double cur_cost, initial_cost, radius;
-};
 constexpr int kMaxGroups = (1 << 23);             // sequence numbers fit the 24-bit fields of HostStatus::word
 __host__ __device__ inline uint64_t status_word(int seq, int done, int done_seq) {
     return (uint64_t)(uint32_t)seq | ((uint64_t)(uint32_t)(done & 0xff) << 24) | ((uint64_t)(uint32_t)done_seq << 32);

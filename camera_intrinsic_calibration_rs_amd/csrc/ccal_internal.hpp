@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstring>
 #include <exception>
 #include <functional>
 #include <mutex>
@@ -13,6 +14,7 @@
 
 #include "../../include/ccal.h"
 #include "ccal_models.hpp"
+#include "ccal_plan.hpp"
 
 namespace ccal {
 
@@ -139,6 +141,21 @@ inline void ctx_stream_put(ccal_ctx* ctx, hipStream_t s) {
 // wrote turns into NaN (tests/test_gpu_poison.py).  Never called on indices, offsets, counters, flags or DevState.  Defined out of
 // line in ccal_solver.hip, which each library compiles itself; hidden, so that each library calls its own.  The product's is empty.
 __attribute__((visibility("hidden"))) hipError_t test_poison_f64(ccal_ctx* ctx, void* p, size_t bytes, bool host, hipStream_t s);
+// A persistent block as its plan describes it: from the context's allocator, the test hook's NaN over its slices of doubles, then ONE
+// clear of the slices that must start as zeros - on the context's stream (it does not synchronise with the null stream), in front of every use
+inline hipError_t ctx_block_alloc(ccal_ctx* ctx, const CallPlan& pl, char** out, bool host) {
+    hipError_t e = host ? ctx_host_alloc(ctx, (void**)out, pl.total) : ctx_dev_alloc(ctx, (void**)out, pl.total);
+    for (int i = 0; i < pl.n_poison && e == hipSuccess; ++i) e = test_poison_f64(ctx, *out + pl.poison[i].off, pl.poison[i].bytes, host, ctx->stream);
+    if (e != hipSuccess || !pl.zero_bytes) return e;
+    if (host) { std::memset(*out, 0, pl.zero_bytes); return hipSuccess; }
+    return hipMemsetAsync(*out, 0, pl.zero_bytes, ctx->stream);
+}
+// a buffer of n doubles made on first use, which the library writes before it reads (*out != NULL: there already)
+inline hipError_t ctx_doubles(ccal_ctx* ctx, double** out, size_t n) {
+    if (*out) return hipSuccess;
+    const hipError_t e = ctx_dev_alloc(ctx, (void**)out, n * sizeof(double));
+    return e != hipSuccess ? e : test_poison_f64(ctx, *out, n * sizeof(double), false, ctx->stream);
+}
 inline void ctx_cache_clear(ccal_ctx* ctx) {
     for (auto& b : ctx->cache_dev) (void)hipFree(b.p);
     for (auto& b : ctx->cache_host) (void)hipHostFree(b.p);
@@ -189,6 +206,28 @@ struct GramBins {
 // The plan for corner counts n[0 .. n_obs) (host): which frames go together and with how many lanes each; order = the sorted table
 // (frame indices, bins in launch order).  n_bins == 0: binning does not pay (uniform frames, too few of them).
 GramBins gram2_bin_plan(const int64_t* obs_off, int n_obs, bool two_per_simd, std::vector<int32_t>* order, bool rig_list = false);
+
+// ccal_problem::d_block: the corner arrays, the frame tables and each camera's list of frames (one element of slack behind each: the
+// Gram / eval kernels request a frame's first corner row before they look at its corner count - for an EMPTY last frame one past the
+// data), the sorted table of ragged single-camera problems, then the two parameter sets, which start as zeros behind [0, uploaded)
+struct ProblemLayout {
+    CallPlan plan;
+    Slice<float> x, y, z, u, v; Slice<int64_t> obs_off, joff;
+    Slice<int32_t> obs_cam, obs_slot, cam_obs[CCAL_MAX_CAMS], bin_tab;
+    size_t uploaded = 0;
+    Slice<double> intr, poses, extr, intr_c, poses_c, extr_c;
+    ProblemLayout(size_t n_corners, size_t n_obs, size_t n_slots, int n_cams, const size_t* n_cam_obs, size_t n_bin_tab) {
+        for (Slice<float>* s : { &x, &y, &z, &u, &v }) *s = plan.add<float>(n_corners + 1);
+        obs_off = plan.add<int64_t>(n_obs + 2); joff = plan.add<int64_t>(n_obs + 2);
+        obs_cam = plan.add<int32_t>(n_obs + 1); obs_slot = plan.add<int32_t>(n_obs + 1);
+        for (int c = 0; c < n_cams; ++c) cam_obs[c] = plan.add<int32_t>(n_cam_obs[c] + 1);
+        bin_tab = plan.add<int32_t>(n_bin_tab ? n_bin_tab + 1 : 0);
+        uploaded = plan.total;
+        const size_t ni = (size_t)n_cams * CCAL_PMAX, np6 = std::max<size_t>(n_slots, 1) * 6, ne = (size_t)n_cams * 6;
+        intr = plan.add<double>(ni); poses = plan.add<double>(np6); extr = plan.add<double>(ne);
+        intr_c = plan.add<double>(ni); poses_c = plan.add<double>(np6); extr_c = plan.add<double>(ne);
+    }
+};
 
 }  // namespace ccal
 
@@ -294,16 +333,32 @@ int rccl_allreduce_sum(ccal_ctx* ctx, void* comm, double* buf, size_t count, hip
 // ccal_solver.hip: wait for the early-exit groups a finished solve left in the stream (no-op if there are none)
 int drain_pending_groups(ccal_problem* p);
 // ccal_kernels_stats.hip
+// ccal_problem::d_scratch, grown on demand and kept between calls, as its two users cut it:
+//   ccal_init_poses       poses [n_obs][6] | counts [n_obs]
+//   validation()          offsets [frames of the camera + 1] | values [n] | the selection's work area
+// (the multi-GPU form's block - order_stats_block, ccal_multi.hip - is the second without offsets: the values in front)
+constexpr size_t kSelWorkBytes = 103680;           // sizeof(SelWork) rounded up (ccal_kernels_stats.hip asserts it)
+struct PoseScratch {
+    CallPlan plan; Slice<double> poses; Slice<int32_t> counts;
+    explicit PoseScratch(size_t n_obs) { poses = plan.add<double, kDoubles>(std::max<size_t>(n_obs, 1) * 6); counts = plan.add<int32_t>(std::max<size_t>(n_obs, 1)); }
+};
+struct StatsScratch {
+    CallPlan plan; Slice<int64_t> offsets; Slice<double> values; Slice<char> work;
+    StatsScratch(size_t n_offsets, int64_t n) { offsets = plan.add<int64_t>(n_offsets); values = plan.add<double, kDoubles>((size_t)n); work = plan.add<char>(kSelWorkBytes); }
+};
 // first size of ccal_problem::d_scratch: what ccal_init_poses and validation() of every camera need (gathered values + the selection's work area)
 inline size_t problem_scratch_hint(const ccal_problem* p) {
     return (size_t)std::max<int64_t>(p->n_corners, 1) * 32 + (size_t)(std::max(p->n_obs, 1) + 1) * 64 + (size_t)384 * 1024;
 }
+// the scratch holds at least pl.total bytes; a new block gets the test hook's poison over the plan's slices of doubles
+hipError_t ensure_scratch(ccal_problem* p, const CallPlan& pl);
 hipError_t validation_stats_device(ccal_problem* p, int cam, const double* d_err, double* avg_99, double* median, hipStream_t s);
 hipError_t camera_errors_device(ccal_problem* p, int cam, const double* d_err, double** d_out, int64_t* n_out, hipStream_t s);     // *d_out: a slice of p->d_scratch
-size_t order_stats_block_bytes(int64_t n, hipStream_t s);      // block size order_stats_block needs for n values (0: sizing failed)
+inline size_t order_stats_block_bytes(int64_t n, hipStream_t = nullptr) { return n <= 0 ? 0 : StatsScratch(0, n).plan.total; }     // block size order_stats_block needs for n values
 hipError_t order_stats_block(char* block /* values in front */, size_t block_bytes, int64_t n, double* avg_99, double* median, hipStream_t s);
-// ccal_api.hip: reprojection errors of every corner at the given parameters into p->d_err (device); ccal_multi.hip uses it per shard
-int reprojection_errors_dev(ccal_problem* p, const double* intr, const double* poses, const double* extr);
+// ccal_api.hip: reprojection errors of every corner (only_cam >= 0: of that camera's) at the given parameters into p->d_err (device);
+// ccal_multi.hip uses it per shard
+int reprojection_errors_dev(ccal_problem* p, const double* intr, const double* poses, const double* extr, int only_cam = -1);
 // ccal_kernels_init.hip
 hipError_t launch_pose_init(const ccal_problem* p, int cam, const double* d_intr, double* d_poses_obs, int32_t* d_valid,
                             int min_points, hipStream_t s);

@@ -47,7 +47,7 @@ __device__ __forceinline__ double from_fixed(const u128 f) {
     const double hi = (double)(unsigned long long)(f >> 64), lo = (double)(unsigned long long)f;
     return (hi * 18446744073709551616.0 + lo) * 8.271806125530277e-25;          // x 2^-80
 }
-size_t order_stats_work_bytes() { return CallPlan::up256(sizeof(SelWork)); }
+static_assert(kSelWorkBytes == ((sizeof(SelWork) + 255) & ~(size_t)255), "the work area's room in the scratch layouts (ccal_internal.hpp)");
 
 // What the histogram of pass p - 1 says about both targets: every workgroup derives it for itself (the same counts: the same
 // answer), workgroup 0 leaves it for the next launch.  state[p] = state at the ENTRY of pass p.  Wavefront t of the workgroup takes
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(1024) void k_sel_one(const double* __restrict__ val
     }
 }
 
-// median and 99 % mean of n non-negative values on the device; `work`: order_stats_work_bytes() of device memory
+// median and 99 % mean of n non-negative values on the device; `work`: kSelWorkBytes of device memory
 hipError_t order_stats_device(const double* d_vals, int64_t n, char* work, double* avg_99, double* median, hipStream_t s) {
     if (n <= 0 || !work) return hipErrorInvalidValue;
     SelWork* w = reinterpret_cast<SelWork*>(work);
@@ -272,14 +272,13 @@ hipError_t order_stats_device(const double* d_vals, int64_t n, char* work, doubl
     return hipSuccess;
 }
 
-// (f64_off, f64_bytes: the slice of doubles the caller puts there - the test hook's poison on a new block)
-static hipError_t ensure_scratch(ccal_problem* p, size_t total, size_t f64_off, size_t f64_bytes) {
-    if (p->scratch_bytes >= total) return hipSuccess;
+hipError_t ensure_scratch(ccal_problem* p, const CallPlan& pl) {
+    if (p->scratch_bytes >= pl.total) return hipSuccess;
     if (p->d_scratch) { (void)hipStreamSynchronize(p->ctx->stream); ctx_release(p->ctx, p->d_scratch, false); p->d_scratch = nullptr; p->scratch_bytes = 0; }
-    const size_t want = std::max(total, problem_scratch_hint(p));
-    const hipError_t e = ctx_dev_alloc(p->ctx, (void**)&p->d_scratch, want);
-    if (e == hipSuccess) p->scratch_bytes = want;
-    if (e == hipSuccess) return test_poison_f64(p->ctx, p->d_scratch + f64_off, f64_bytes, false, p->ctx->stream);
+    CallPlan want = pl;
+    want.total = std::max(pl.total, problem_scratch_hint(p));       // (room for the other user too: growing the block later costs a free)
+    const hipError_t e = ctx_block_alloc(p->ctx, want, &p->d_scratch, false);
+    if (e == hipSuccess) p->scratch_bytes = want.total;
     return e;
 }
 
@@ -295,11 +294,11 @@ static hipError_t gather_camera_errors(ccal_problem* p, int cam, const double* d
     for (int i = 0; i < n_list; ++i) dst[i + 1] = dst[i] + (p->h_obs_off[cl.obs[i] + 1] - p->h_obs_off[cl.obs[i]]);
     const int64_t n = dst[n_list];
     if (n <= 0) return hipSuccess;
-    const size_t b_off = CallPlan::up256((size_t)(n_list + 1) * sizeof(int64_t)), b_val = CallPlan::up256((size_t)n * sizeof(double));
-    hipError_t e = ensure_scratch(p, b_off + b_val + order_stats_work_bytes(), b_off, b_val);
+    const StatsScratch l((size_t)n_list + 1, n);
+    hipError_t e = ensure_scratch(p, l.plan);
     if (e != hipSuccess) return e;
-    int64_t* d_dst = reinterpret_cast<int64_t*>(p->d_scratch);
-    double* d_a = reinterpret_cast<double*>(p->d_scratch + b_off);
+    int64_t* d_dst = Bound{ p->d_scratch }.at(l.offsets);
+    double* d_a = Bound{ p->d_scratch }.at(l.values);
     e = hipMemcpyAsync(d_dst, dst.data(), (size_t)(n_list + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) { hipLaunchKernelGGL(k_gather_err, dim3(n_list), dim3(256), 0, s, d_err, p->d_obs_off, cl.d_obs, n_list, d_dst, d_a); e = hipGetLastError(); }
     if (e == hipSuccess && sync) e = hipStreamSynchronize(s);       // (the multi-GPU form copies d_a across devices next; else the caller's own
@@ -323,15 +322,14 @@ hipError_t validation_stats_device(ccal_problem* p, int cam, const double* d_err
     hipError_t e = gather_camera_errors(p, cam, d_err, &d_a, &n, s, dst, false);
     if (e != hipSuccess) return e;
     if (n <= 0) return hipErrorInvalidValue;
-    char* work = reinterpret_cast<char*>(d_a) + CallPlan::up256((size_t)n * sizeof(double));
-    return order_stats_device(d_a, n, work, avg_99, median, s);
+    return order_stats_device(d_a, n, p->d_scratch + StatsScratch(dst.size(), n).work.off, avg_99, median, s);
 }
 
 // the multi-GPU form: block = [values (n) | work area], sized by order_stats_block_bytes and kept by the caller between calls
-size_t order_stats_block_bytes(int64_t n, hipStream_t) { return n <= 0 ? 0 : CallPlan::up256((size_t)n * sizeof(double)) + order_stats_work_bytes(); }
 hipError_t order_stats_block(char* block, size_t block_bytes, int64_t n, double* avg_99, double* median, hipStream_t s) {
-    if (n <= 0 || !block || order_stats_block_bytes(n, s) > block_bytes) return hipErrorInvalidValue;
-    return order_stats_device(reinterpret_cast<const double*>(block), n, block + CallPlan::up256((size_t)n * sizeof(double)), avg_99, median, s);
+    if (n <= 0 || !block || order_stats_block_bytes(n) > block_bytes) return hipErrorInvalidValue;
+    const StatsScratch l(0, n);
+    return order_stats_device(Bound{ block }.at(l.values), n, block + l.work.off, avg_99, median, s);
 }
 
 }  // namespace ccal

@@ -34,15 +34,6 @@ using namespace ccal;
         }                                                                                          \
     } while (0)
 
-#define HIP_TRY(ctx, expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
-            return CCAL_ERR_HIP;                                                                   \
-        }                                                                                          \
-    } while (0)
-
 namespace ccal {
 
 hipError_t test_poison_f64(ccal_ctx* ctx, void* p, size_t bytes, bool host, hipStream_t s) {
@@ -69,21 +60,14 @@ void normal_ws_destroy(ccal_problem* p) {
         (void)hipSetDevice(p->ctx->device);
         (void)hipDeviceSynchronize();
     }
-    void* ptrs[] = { w->G[0], w->G[1], w->cost_o[0], w->cost_o[1], w->d_goff, w->d_slot_off, w->d_slot_obs, w->d_obs_cam,
-                     w->d_caminfo, w->partial, w->red, w->pf, w->dc, w->mc_slot, w->scal, w->flags, w->cols, w->d_slot_desc, w->d_slot_rec, w->d_all_obs, w->d_obs_owner };
     // (the blocks go back to the context's cache - ccal_internal.hpp - for its next problem; ccal_problem_destroy has drained the stream)
     ccal_ctx* ctx = p->ctx;
-    for (void* q : ptrs) if (q) ctx_release(ctx, q, false);
-    for (int32_t* q : w->d_gen_sorted) if (q) ctx_release(ctx, q, false);
-    if (w->h_pinned) (void)hipHostFree(w->h_pinned);
-    if (w->d_gstate) ctx_release(ctx, w->d_gstate, false);
     if (w->side) { (void)hipStreamSynchronize(w->side); ctx_stream_put(ctx, w->side); }
-    if (w->h_gstatus) ctx_release(ctx, w->h_gstatus, true);
-    if (w->h_gstate) (void)hipHostFree(w->h_gstate);
+    ctx_release(ctx, w->d_base, false); ctx_release(ctx, w->d_block, false); ctx_release(ctx, w->h_block, true);
     if (FusedWs* f = w->fws) {
         if (f->side) { (void)hipStreamSynchronize(f->side); ctx_stream_put(ctx, f->side); }      // (the result's download ran there)
-        if (f->d_block) ctx_release(ctx, f->d_block, false);          // every device buffer of the workspace is a slice of it
-        if (f->h_block) ctx_release(ctx, f->h_block, true);           // h_status | h_result | h_stage
+        ctx_release(ctx, f->d_block, false);          // every device buffer of the workspace is a slice of it
+        ctx_release(ctx, f->h_block, true);           // h_status | h_result | h_stage
         if (f->fcbuf) (void)hipFree(f->fcbuf);
         delete f;
     }
@@ -107,16 +91,6 @@ int drain_pending_groups(ccal_problem* p) {
 // problems stage through device copies (a kernel reading / writing half a megabyte across the bus one wavefront wide would
 // cost more than the DMA it saves).
 constexpr size_t kZeroCopyBytes = 96 * 1024;
-// poses a finishing single-launch group writes to the host with ALL its workgroups: up to 5 461 frames.  Stores of a shader cross the bus in
-// 64-byte packets, the DMA engine's in 256+: 2 500 frames GN 0.150 -> 0.136 ms, 5 000: 0.184 -> 0.178, but 10 000: 0.238 -> 0.255 and, from a
-// table sorted by corner count, scattered pose READS over the bus on top (0.219 -> 0.256): profiles/r06/ab_result_spread.txt
-constexpr size_t kSpreadBytes = 256 * 1024;
-
-// rows of the single-camera loop's partial-sum buffer (fused_ws_ensure)
-static int fused_partial_rows(int n_obs) {
-    const int n_pw = std::max(std::min(std::max(n_obs, 1), 16384), (std::max(n_obs, 1) + 9) / 10 + 8);
-    return (n_pw + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK * WAVES_PER_BLOCK;
-}
 static int fused_ws_ensure(ccal_problem* p) {
     NormalWs* w = p->nws;
     if (w->fws) return CCAL_OK;
@@ -129,70 +103,28 @@ static int fused_ws_ensure(ccal_problem* p) {
     { const char* e = dev_env("CCAL_FUSE_ELIM"); f->fuse_elim = !(e && e[0] == '0'); }      // second library: the separate elimination launch (k_schur1m)
 #endif
     f->RB1 = fused_red_size(p->K);
-    // rows of the partial-sum buffer = most wavefronts a Gram launch of this problem may have: one row per wavefront (fused
-    // elimination).  Up to 16 384 frames any lanes-per-frame mapping fits; beyond, the launchers keep to mappings that do - six
-    // lanes per frame (ten frames per wavefront) always does
     f->n_pw = fused_partial_rows(p->n_obs);
-    const size_t ns = (size_t)std::max(p->n_slots, 1), no = (size_t)std::max(p->n_obs, 1);
     // ONE device allocation and ONE pinned allocation, sliced (a calibration session creates a problem and solves it once or
     // twice: fifteen hipMalloc / hipHostMalloc calls and five memsets were 0.46 ms of the first solve's 0.58 at 600 frames)
-    const size_t stage_bytes = std::max((ns * 6 + CCAL_PMAX) * sizeof(double) + 64, (size_t)(f->RB1 + 8) * sizeof(double));      // (ccal_build_normal stages the reduced sums here)
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_pf = up(ns * w->PF * sizeof(double)), b_praw = up(no * f->PRAW * sizeof(double)), b_no = up(no * sizeof(double));
-    const size_t b_part = up((size_t)f->RB1 * f->n_pw * sizeof(double)), b_red = up((size_t)(f->RB1 + 7) * sizeof(double));
-    const size_t b_state = up(3 * sizeof(DevState)), b_stage = up(stage_bytes);
-    const size_t b_cnt = 256;
-    const size_t zeroed = 2 * b_pf + 2 * b_praw + b_part + 2 * b_red + b_cnt;              // the slices that must start as zeros come first (red: two buffers,
-                                                                                  // the in-process transport alternates between them)
-    const size_t d_total = zeroed + 2 * b_no + b_state + b_stage;
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&f->d_block, d_total));
-    // (test hook: the double slices - pf, praw, partial, red | mc_f, cost_f | d_stage; not done_cnt, d_state)
-    HIP_TRY(ctx, test_poison_f64(ctx, f->d_block, zeroed - b_cnt, false, ctx->stream));
-    HIP_TRY(ctx, test_poison_f64(ctx, f->d_block + zeroed, 2 * b_no, false, ctx->stream));
-    HIP_TRY(ctx, test_poison_f64(ctx, f->d_block + zeroed + 2 * b_no + b_state, b_stage, false, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(f->d_block, 0, zeroed, ctx->stream));             // (stream-ordered in front of everything that uses the workspace)
-    {
-        char* q = f->d_block;
-        for (int i = 0; i < 2; ++i) { f->pf[i] = reinterpret_cast<double*>(q); q += b_pf; }
-        for (int i = 0; i < 2; ++i) { f->praw[i] = reinterpret_cast<double*>(q); q += b_praw; }
-        f->partial = reinterpret_cast<double*>(q); q += b_part;
-        f->red = reinterpret_cast<double*>(q); q += 2 * b_red; f->red_stride = b_red / sizeof(double);
-        f->done_cnt = reinterpret_cast<int32_t*>(q); q += b_cnt;
-        f->mc_f = reinterpret_cast<double*>(q); q += b_no;
-        f->cost_f = reinterpret_cast<double*>(q); q += b_no;
-        f->d_state = reinterpret_cast<DevState*>(q); q += b_state;      // [0] the loops' state; [1], [2]: single-launch groups alternate
-        f->d_stage = reinterpret_cast<double*>(q); q += b_stage;
-    }
+    const FusedLayout l((size_t)p->n_slots, (size_t)p->n_obs, (size_t)w->PF, (size_t)f->PRAW, (size_t)f->RB1, (size_t)f->n_pw);
+    HIP_TRY(ctx, ctx_block_alloc(ctx, l.dev, &f->d_block, false));
+    HIP_TRY(ctx, ctx_block_alloc(ctx, l.host, &f->h_block, true));
+    const Bound d{ f->d_block }, h{ f->h_block };
+    for (int i = 0; i < 2; ++i) { f->pf[i] = d.at(l.pf[i]); f->praw[i] = d.at(l.praw[i]); }
+    f->partial = d.at(l.partial); f->red = d.at(l.red); f->red_stride = l.red_stride; f->done_cnt = d.at(l.done_cnt);
+    f->mc_f = d.at(l.mc_f); f->cost_f = d.at(l.cost_f); f->d_state = d.at(l.state); f->d_stage = d.at(l.d_stage);
+    f->h_status = h.at(l.h_status); f->h_result = h.at(l.h_result); f->h_stage = h.at(l.h_stage);
     // per-frame scratch of diagnostic builds (-DCCAL_STAMPS: in-kernel timestamps, tools/stamps_*.py); the product allocates nothing
 #ifdef CCAL_STAMPS
-    HIP_TRY(ctx, hipMalloc((void**)&f->fcbuf, std::max<size_t>(no * 40, 32768) * sizeof(double)));
+    HIP_TRY(ctx, hipMalloc((void**)&f->fcbuf, std::max<size_t>((size_t)std::max(p->n_obs, 1) * 40, 32768) * sizeof(double)));
 #endif
-    {
-        const bool zc = ns * 6 * sizeof(double) <= kSpreadBytes;         // (beyond kZeroCopyBytes: single-launch groups only, FusedJob::begin)
-        const size_t b_hs = up(sizeof(HostStatus)), b_res = zc ? up((ns * 6 + CCAL_PMAX) * sizeof(double)) : 0;
-        HIP_TRY(ctx, ctx_host_alloc(ctx, (void**)&f->h_block, b_hs + b_res + b_stage));
-        HIP_TRY(ctx, test_poison_f64(ctx, f->h_block + b_hs, b_res + b_stage, true, nullptr));      // h_result, h_stage (not h_status)
-        char* q = f->h_block;
-        f->h_status = reinterpret_cast<HostStatus*>(q); q += b_hs;
-        f->h_result = zc ? reinterpret_cast<double*>(q) : nullptr; q += b_res;
-        f->h_stage = reinterpret_cast<double*>(q);
-    }
     HIP_TRY(ctx, ctx_stream_get(ctx, &f->side));
-    std::memset((void*)f->h_status, 0, sizeof(HostStatus));
-    return CCAL_OK;
-}
-
-template <class T>
-static int dev_upload(ccal_ctx* ctx, T** dst, const std::vector<T>& src) {
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)dst, std::max<size_t>(src.size(), 1) * sizeof(T)));
-    if (!src.empty()) HIP_TRY(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return CCAL_OK;
 }
 
 // The part every loop needs: sizes, the column table and the camera step.  The single-camera loop (FusedWs) needs nothing else of
-// NormalWs; the general loop's buffers - per-frame record sets, slot tables, partial sums, a second status block and stream:
-// ~25 allocations, seven synchronous uploads - are made when a general-loop entry first asks (normal_ws_ensure_general): they
-// were 0.4 ms of a single-camera session's first solve.
+// NormalWs; the general loop's buffers - per-frame record sets, slot tables, partial sums, a second status block and stream - are
+// made when a general-loop entry first asks (normal_ws_ensure_general): one device block, one pinned block, one upload.
 int normal_ws_ensure(ccal_problem* p) {
     if (p->nws) return CCAL_OK;
     ccal_ctx* ctx = p->ctx;
@@ -200,9 +132,9 @@ int normal_ws_ensure(ccal_problem* p) {
     NormalWs* w = new NormalWs();
     p->nws = w;
     w->K = p->K; w->RB = red_size(p->K); w->PF = pf_size(p->K);
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->dc, CCAL_KMAX * sizeof(double)));
-    HIP_TRY(ctx, test_poison_f64(ctx, w->dc, CCAL_KMAX * sizeof(double), false, ctx->stream));
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->cols, CCAL_KMAX * sizeof(ColInfo)));
+    const NormalBaseLayout l;
+    HIP_TRY(ctx, ctx_block_alloc(ctx, l.plan, &w->d_base, false));
+    w->dc = Bound{ w->d_base }.at(l.dc); w->cols = Bound{ w->d_base }.at(l.cols);
     return CCAL_OK;
 }
 int normal_ws_ensure_general(ccal_problem* p) {
@@ -212,7 +144,6 @@ int normal_ws_ensure_general(ccal_problem* p) {
     if (w->general_ready) return CCAL_OK;
     ccal_ctx* ctx = p->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // persistent Schur waves: at most 2 workgroups per CU worth, never more than slots
     // persistent wavefronts of k_schur: 4 per SIMD (measured at 10 000 slots x 2 cameras: 2048 -> 165.7, 4096 -> 158.5, 8192 -> 173 us per build)
     int n_pw = std::min(std::max(p->n_slots, 1), std::max(4, dev_env_int("CCAL_SCHUR_WAVES", 4096)));
     n_pw = (n_pw + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK * WAVES_PER_BLOCK;
@@ -286,92 +217,61 @@ int normal_ws_ensure_general(ccal_problem* p) {
       for (int o = 0; o < p->n_obs; ++o) slot_obs[cur[p->h_obs_slot[o]]++] = o; }
     std::vector<int64_t> slot_desc(p->n_obs);
     for (int i = 0; i < p->n_obs; ++i) slot_desc[i] = goff[slot_obs[i]] * 8 + p->h_obs_cam[slot_obs[i]];
-    int rc;
-    if ((rc = dev_upload(ctx, &w->d_slot_desc, slot_desc))) return rc;
-    {
-        std::vector<int8_t> owner(std::max(p->n_obs, 1), 0);
-        w->all_slots_observed = true;
-        for (int sl = 0; sl < p->n_slots; ++sl) {
-            if (slot_off[sl + 1] > slot_off[sl]) owner[slot_obs[slot_off[sl]]] = 1;
-            else w->all_slots_observed = false;
-        }
-        if ((rc = dev_upload(ctx, &w->d_obs_owner, owner))) return rc;
+    std::vector<int8_t> owner(p->n_obs, 0);
+    w->all_slots_observed = true;
+    for (int sl = 0; sl < p->n_slots; ++sl) {
+        if (slot_off[sl + 1] > slot_off[sl]) owner[slot_obs[slot_off[sl]]] = 1;
+        else w->all_slots_observed = false;
     }
-    if (w->merged_gram) {
-        std::vector<int32_t> all;
-        all.reserve(p->n_obs);
-        for (int c = 0; c < p->n_cams; ++c) all.insert(all.end(), p->cams[c].obs.begin(), p->cams[c].obs.end());
-        if ((rc = dev_upload(ctx, &w->d_all_obs, all))) return rc;
-    }
+    std::vector<int32_t> all, sorted[1 + CCAL_MAX_CAMS];
+    if (w->merged_gram) for (int c = 0; c < p->n_cams; ++c) all.insert(all.end(), p->cams[c].obs.begin(), p->cams[c].obs.end());
     if (w->register_gram) {
         // ragged frames: every Gram launch's list sorted by corner count, with the bins of the launch (the single-camera loop's plan,
         // ccal_kernels_gram2.hip: gram2_bin_plan - uniform frames and short lists get none)
-        auto plan_list = [&](const std::vector<int32_t>& list, int slot, int model) -> int {
-            if (list.size() < 2000) return CCAL_OK;
+        auto plan_list = [&](const std::vector<int32_t>& list, int slot, int model) {
+            if (list.size() < 2000) return;
             std::vector<int64_t> off(list.size() + 1, 0);
             for (size_t i = 0; i < list.size(); ++i) off[i + 1] = off[i] + (p->h_obs_off[list[i] + 1] - p->h_obs_off[list[i]]);
             std::vector<int32_t> order;
             const GramBins gb = gram2_bin_plan(off.data(), (int)list.size(), model == kUCM || model == kEUCM, &order, true);
-            if (gb.n_bins <= 0) return CCAL_OK;
-            std::vector<int32_t> sorted(list.size());
-            for (size_t i = 0; i < list.size(); ++i) sorted[i] = list[(size_t)order[i]];
-            if (int r = dev_upload(ctx, &w->d_gen_sorted[slot], sorted)) return r;
+            if (gb.n_bins <= 0) return;
+            sorted[slot].resize(list.size());
+            for (size_t i = 0; i < list.size(); ++i) sorted[slot][i] = list[(size_t)order[i]];
             w->gen_bins[slot] = gb;
-            return CCAL_OK;
         };
-        if (w->merged_gram) {
-            std::vector<int32_t> all;
-            for (int c = 0; c < p->n_cams; ++c) all.insert(all.end(), p->cams[c].obs.begin(), p->cams[c].obs.end());
-            if ((rc = plan_list(all, 0, p->cams[0].model))) return rc;
-        } else {
-            for (int c = 0; c < p->n_cams; ++c) if ((rc = plan_list(p->cams[c].obs, 1 + c, p->cams[c].model))) return rc;
-        }
+        if (w->merged_gram) plan_list(all, 0, p->cams[0].model);
+        else for (int c = 0; c < p->n_cams; ++c) plan_list(p->cams[c].obs, 1 + c, p->cams[c].model);
     }
+    std::vector<int64_t> slot_rec;
     if (w->schurq) {
-        std::vector<int64_t> slot_rec((size_t)std::max(p->n_slots, 1) * 2, -1);
+        slot_rec.assign((size_t)std::max(p->n_slots, 1) * 2, -1);
         for (int o = 0; o < p->n_obs; ++o) slot_rec[(size_t)p->h_obs_slot[o] * 2 + p->h_obs_cam[o]] = goff[o];
-        if ((rc = dev_upload(ctx, &w->d_slot_rec, slot_rec))) return rc;
     }
-    if ((rc = dev_upload(ctx, &w->d_goff, goff)) || (rc = dev_upload(ctx, &w->d_slot_off, slot_off)) ||
-        (rc = dev_upload(ctx, &w->d_slot_obs, slot_obs)) || (rc = dev_upload(ctx, &w->d_obs_cam, p->h_obs_cam)) ||
-        (rc = dev_upload(ctx, &w->d_caminfo, caminfo)))
-        return rc;
-    const size_t gbytes = std::max<int64_t>(gl, 1) * sizeof(double);
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->G[i], gbytes));
-        HIP_TRY(ctx, test_poison_f64(ctx, w->G[i], gbytes, false, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(w->G[i], 0, gbytes, ctx->stream));     // tile (1,0) of two-tile blocks is never written
-        HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->cost_o[i], std::max(p->n_obs, 1) * sizeof(double)));
-        HIP_TRY(ctx, test_poison_f64(ctx, w->cost_o[i], std::max(p->n_obs, 1) * sizeof(double), false, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(w->cost_o[i], 0, std::max(p->n_obs, 1) * sizeof(double), ctx->stream));
-    }
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->partial, (size_t)w->RB * std::max(n_pw, w->n_rows) * sizeof(double)));
-    HIP_TRY(ctx, test_poison_f64(ctx, w->partial, (size_t)w->RB * std::max(n_pw, w->n_rows) * sizeof(double), false, ctx->stream));
-    // (every clear of this function is ordered on the context's stream: it does not synchronise with the null stream, and the
-    // kernels rely on what is never written staying zero - holes in the record buffers, upper-triangle rows of `partial`)
-    // k_schurq writes the lower triangle and the extras only: the rows of the upper triangle stay zero.  On the context's
-    // stream: it does not synchronise with the null stream, a plain hipMemset could still be running when the first
-    // elimination writes the buffer
-    HIP_TRY(ctx, hipMemsetAsync(w->partial, 0, (size_t)w->RB * std::max(n_pw, w->n_rows) * sizeof(double), ctx->stream));
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->red, 2 * (size_t)(w->RB + 8) * sizeof(double)));      // two buffers: the in-process transport alternates
-    HIP_TRY(ctx, test_poison_f64(ctx, w->red, 2 * (size_t)(w->RB + 8) * sizeof(double), false, ctx->stream));
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->pf, (size_t)std::max(p->n_slots, 1) * w->PF * sizeof(double)));
-    HIP_TRY(ctx, test_poison_f64(ctx, w->pf, (size_t)std::max(p->n_slots, 1) * w->PF * sizeof(double), false, ctx->stream));
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->mc_slot, (size_t)std::max(p->n_slots, 1) * sizeof(double)));
-    HIP_TRY(ctx, test_poison_f64(ctx, w->mc_slot, (size_t)std::max(p->n_slots, 1) * sizeof(double), false, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(w->mc_slot, 0, (size_t)std::max(p->n_slots, 1) * sizeof(double), ctx->stream));
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->scal, 8 * sizeof(double)));
-    HIP_TRY(ctx, test_poison_f64(ctx, w->scal, 8 * sizeof(double), false, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(w->scal, 0, 8 * sizeof(double), ctx->stream));
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->flags, 4 * sizeof(int32_t)));
-    HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&w->d_gstate, sizeof(DevState)));
+    // ONE device block and ONE pinned block (GeneralLayout, ccal_normal.hpp); the index tables go up as one image with one copy.  The
+    // block's clear is ordered on the context's stream (ctx_block_alloc): the kernels rely on what is never written staying zero - holes in the
+    // record buffers (tile (1,0) of two-tile blocks, k_schurq's missing records), the upper-triangle rows of `partial` (k_schurq writes the rest)
+    size_t n_sorted[1 + CCAL_MAX_CAMS];
+    for (int i = 0; i <= CCAL_MAX_CAMS; ++i) n_sorted[i] = sorted[i].size();
+    const GeneralLayout l(p->n_cams, (size_t)p->n_obs, (size_t)p->n_slots, (size_t)w->RB, (size_t)w->PF, (size_t)gl, (size_t)std::max(n_pw, w->n_rows),
+                          w->merged_gram, w->schurq, n_sorted);
+    HIP_TRY(ctx, ctx_block_alloc(ctx, l.dev, &w->d_block, false));
+    HIP_TRY(ctx, ctx_block_alloc(ctx, l.host, &w->h_block, true));
+    const Bound d{ w->d_block }, h{ w->h_block };
+    for (int i = 0; i < 2; ++i) { w->G[i] = d.at(l.G[i]); w->cost_o[i] = d.at(l.cost_o[i]); }
+    w->partial = d.at(l.partial); w->mc_slot = d.at(l.mc_slot); w->scal = d.at(l.scal); w->flags = d.at(l.flags);
+    w->red = d.at(l.red); w->pf = d.at(l.pf); w->d_gstate = d.at(l.gstate);
+    w->h_gstatus = h.at(l.h_gstatus); w->h_gstate = h.at(l.h_gstate); w->h_pinned = h.at(l.h_pinned);
     HIP_TRY(ctx, ctx_stream_get(ctx, &w->side));
-    HIP_TRY(ctx, ctx_host_alloc(ctx, (void**)&w->h_gstatus, sizeof(HostStatus)));
-    HIP_TRY(ctx, hipHostMalloc((void**)&w->h_gstate, sizeof(DevState), hipHostMallocDefault));
-    std::memset((void*)w->h_gstatus, 0, sizeof(HostStatus));
-    HIP_TRY(ctx, hipMemsetAsync(w->flags, 0, 4 * sizeof(int32_t), ctx->stream));
-    HIP_TRY(ctx, hipHostMalloc((void**)&w->h_pinned, (size_t)(w->RB + 16) * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(ctx, test_poison_f64(ctx, w->h_pinned, (size_t)(w->RB + 16) * sizeof(double), true, nullptr));
+    std::vector<char> image(l.dev.total - l.goff.off);          // (read by an asynchronous copy: alive until normal_upload_cols has synchronised)
+    auto tab = [&](auto*& ptr, auto slice, const auto& v) {       // a table's address (an optional one that is absent: NULL) and its part of the image
+        ptr = d.at(slice);
+        if (!v.empty()) std::memcpy(image.data() + (slice.off - l.goff.off), v.data(), v.size() * sizeof(v[0]));
+    };
+    tab(w->d_goff, l.goff, goff); tab(w->d_slot_off, l.slot_off, slot_off); tab(w->d_slot_obs, l.slot_obs, slot_obs); tab(w->d_obs_cam, l.obs_cam, p->h_obs_cam);
+    tab(w->d_caminfo, l.caminfo, caminfo); tab(w->d_slot_desc, l.slot_desc, slot_desc); tab(w->d_obs_owner, l.obs_owner, owner);
+    tab(w->d_all_obs, l.all_obs, all); tab(w->d_slot_rec, l.slot_rec, slot_rec);
+    for (int i = 0; i <= CCAL_MAX_CAMS; ++i) tab(w->d_gen_sorted[i], l.sorted[i], sorted[i]);
+    HIP_TRY(ctx, hipMemcpyAsync(d.at(l.goff), image.data(), image.size(), hipMemcpyHostToDevice, ctx->stream));
     w->general_ready = true;
     return normal_upload_cols(p);
 }

@@ -468,3 +468,26 @@ def test_product_blocks_reused_across_problems():
             _bits_equal(reused, fresh, where=f"{sp.n_slots} frames: ")
     finally:
         shared.close()
+
+
+def test_dirty_general_block_serves_next_rig():
+    """A rig's general workspace is ONE device block (csrc/ccal_normal.hpp: GeneralLayout), so a destroyed rig leaves the context's
+    cache one large dirty block - record buffers, partial sums, index tables, optimizer state - that the next rig of a similar size
+    gets whole.  On one product context the rig_schurq case (two EUCM cameras over 1 200 slots, drop_frac 0.15: k_schurq, whose
+    record buffers have holes that must read as zeros) is solved and destroyed; then a rig of 1 100 slots with another seed, whose
+    holes fall elsewhere, runs mode E, ccal_build_normal, GN, LM, errors and validation - bit-identical to itself on a fresh context.
+
+    The second rig receives the first one's block: ctx_alloc hands a cached block of B bytes to a request of R bytes when
+    R <= B <= R + R / 4 + 4096.  tests/cpp/test_ws_layouts.cpp (`general 1200 2041`, `general 1100 1865`: slots and observation
+    frames of the two rigs) gives B = 10 847 232 (10 855 424 with the sorted list of the first rig's 2 041 merged frames) and
+    R = 9 945 600; the window ends at 12 436 096.  No other request of the second rig fits that block (its inputs are 3 MB, its
+    mode-E outputs 2.5 and 37 MB)."""
+    ext = np.array([[0.0] * 6, [0.3, -0.25, 0.2, -0.1, 0.02, 0.01]])
+    second = synth.make_rig(1100, ["eucm", "eucm"], ext, seed=0x5C5, drop_frac=0.15)
+    shared, fresh_ctx = Context(0), Context(0)
+    try:
+        _run_solve(shared, _case("rig_schurq"), (GN,))
+        _bits_equal(_product_run(shared, second), _product_run(fresh_ctx, second), where="1 100 slots after 1 200: ")
+    finally:
+        fresh_ctx.close()
+        shared.close()
