@@ -167,6 +167,11 @@ SYMBOLS = [
     ("ccal_undistort_map_destroy", None, [_vp]),
     ("ccal_remap", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     ("ccal_remap_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    # from pixels to detections: sub-pixel refinement of coarse corners
+    ("ccal_refine_corners_batch", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_int, C.c_int, C.c_double,
+                                            _ip, _ip, _dp]),
+    ("ccal_refine_corners_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_int, C.c_int, C.c_double,
+                                          _ip, _ip, _dp]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

@@ -20,6 +20,8 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   GenericModel::project / unproject, estimate_new_camera_matrix_for_undistort, init_undistort_map
                                     (examples/convert_model.rs:27-29)   GenericModel methods of the same names
   remap                             (examples/test_pnp.rs:80)           remap (+ engine.UndistortMap for batches)
+  the sub-pixel step that ends image_to_option_feature_frame
+                                    (src/data_loader.rs:36-70)          refine_corners, redetect_corners (no tag detector here)
   (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
    not here yet - see README, "From detections alone")
 
@@ -685,6 +687,95 @@ def validation_holdout_rig(cameras: Sequence[GenericModel], t_cam_i_0: Sequence[
     t_0_b = refine_rig_poses(cams_detected_feature_frames, cameras, t_cam_i_0, ctx=ctx, opts=opts)
     return [validation(c, cameras[c], {k: t_cam_i_0[c].compose(t) for k, t in t_0_b.items() if k < len(cams_detected_feature_frames[c])},
                        cams_detected_feature_frames[c], ctx=ctx) for c in range(len(cameras))]
+
+
+# ----------------------------------------------------------------------------- from pixels to detections
+def _corner_args(where: str, images, live: Sequence[int], half_win, max_iterations, eps, min_lambda) -> Optional[np.ndarray]:
+    """The argument checks of refine_corners / redetect_corners that need no device, and the images of the frames `live`
+    stacked [n][H][W] (None when there is none); images of other frames are not read."""
+    if not 1 <= int(half_win) <= 15:
+        raise ValueError(f"{where}: half_win 1 .. 15")
+    if int(max_iterations) < 1:
+        raise ValueError(f"{where}: max_iterations >= 1")
+    if not (np.isfinite(eps) and float(eps) >= 0.0):
+        raise ValueError(f"{where}: eps >= 0 and finite")
+    if np.isnan(min_lambda):
+        raise ValueError(f"{where}: min_lambda is NaN")
+    if not live:
+        return None
+    imgs = [np.asarray(images[i]) for i in live]
+    if any(im.ndim != 2 or im.shape != imgs[0].shape or im.dtype != imgs[0].dtype for im in imgs):
+        raise ValueError(f"{where}: single-channel images [H][W] of one size and type")
+    stack, _, _ = check_images(np.stack(imgs), True)
+    return stack
+
+
+def _kept_frames(n_frames: int, live, ids, p3ds, img_w_h, times, xy, status, lam, min_lambda) -> List[Optional[FrameFeature]]:
+    out: List[Optional[FrameFeature]] = [None] * n_frames
+    for k, fi in enumerate(live):
+        keep = (status[k] == _ffi.OK) & (lam[k] >= min_lambda)
+        feats = {ids[k][j]: FeaturePoint((float(np.float32(xy[k][j, 0])), float(np.float32(xy[k][j, 1]))), p3ds[k][j])
+                 for j in np.flatnonzero(keep)}
+        if feats:
+            out[fi] = FrameFeature(times[k], img_w_h, feats)
+    return out
+
+
+def refine_corners(images, frame_feature_list: Sequence[Optional[FrameFeature]], half_win: int = 5, max_iterations: int = 30,
+                   eps: float = 1e-3, min_lambda: float = 0.0, ctx: Optional[Context] = None) -> List[Optional[FrameFeature]]:
+    """The sub-pixel step at the end of a target detector: every corner of every frame moved onto the grey-level saddle of its
+    image (ccal_refine_corners_batch: one wavefront per corner, all frames in one launch).  images: one grey image [H][W] (uint8 or
+    uint16, all of one size) per entry of frame_feature_list; the image of a frame that is None is not read.  Returns a new list:
+    kept corners carry the refined p2d, stored as the f32 the reference's FeaturePoint holds; corners whose status is not CCAL_OK
+    (no convergence, a flat patch or a single edge, a window that leaves the image or slides off its start by more than half_win)
+    or whose lambda_min is below min_lambda are dropped; a frame left without a corner becomes None.
+    min_lambda screens by corner strength (the smaller eigenvalue of the weighted gradient matrix).  It scales with the square of
+    the image contrast; no useful value has been measured here, so the default 0 screens nothing."""
+    if len(images) != len(frame_feature_list):
+        raise ValueError("refine_corners: one image per frame")
+    live = [i for i, f in enumerate(frame_feature_list) if f is not None and f.features]
+    stack = _corner_args("refine_corners", images, live, half_win, max_iterations, eps, min_lambda)
+    if stack is None:
+        return [None] * len(frame_feature_list)
+    ids, _, starts = zip(*(_points_f32(frame_feature_list[i]) for i in live))
+    p3ds = [[frame_feature_list[i].features[k].p3d for k in ids_k] for i, ids_k in zip(live, ids)]
+    xy, status, _, lam = _ctx(ctx).refine_corners_batch(stack, starts, half_win, max_iterations, eps)
+    return _kept_frames(len(frame_feature_list), live, ids, p3ds, (stack.shape[2], stack.shape[1]),
+                        [frame_feature_list[i].time_ns for i in live], xy, status, lam, min_lambda)
+
+
+def redetect_corners(images, model: GenericModel, rtvec_map: Dict[int, RvecTvec], board_points: Dict[int, Tuple[float, float, float]],
+                     half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3, min_lambda: float = 0.0,
+                     ctx: Optional[Context] = None) -> List[Optional[FrameFeature]]:
+    """Guided re-detection after a first calibration: for every frame in rtvec_map (frame index -> board pose) every board point
+    (board_points: id -> p3d) is taken into the camera frame, projected through `model`, and - where the projection is valid and its
+    window lies in the image - refined onto the grey-level saddle of that frame's image (refine_corners' rule and parameters).
+    Returns one entry per image: a FrameFeature (time_ns 0) of the corners that end CCAL_OK with lambda_min >= min_lambda, None for
+    a frame without a pose or without such a corner.  This finds corners the detector missed, at the image edge above all.
+    min_lambda: as in refine_corners - no useful value has been measured, 0 screens nothing."""
+    model._usable("redetect_corners")
+    if any(not 0 <= int(fi) < len(images) for fi in rtvec_map):
+        raise ValueError("redetect_corners: a pose for a frame that has no image")
+    live = sorted(int(fi) for fi in rtvec_map) if board_points else []
+    stack = _corner_args("redetect_corners", images, live, half_win, max_iterations, eps, min_lambda)
+    if stack is None:
+        return [None] * len(images)
+    H, W = stack.shape[1:]
+    all_ids = sorted(board_points.keys())
+    X = np.asarray([board_points[k] for k in all_ids], dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    cam = []
+    for fi in live:
+        R, t = rtvec_map[fi].matrix()
+        cam.append(X @ R.T + t)
+    uv, valid = model.project(np.concatenate(cam), ctx=ctx)
+    m = int(half_win) + 1
+    with np.errstate(invalid="ignore"):
+        valid = valid & (uv[:, 0] >= m) & (uv[:, 0] <= W - 1 - m) & (uv[:, 1] >= m) & (uv[:, 1] <= H - 1 - m)
+    uv, valid = uv.reshape(len(live), -1, 2), valid.reshape(len(live), -1)
+    ids = [[all_ids[j] for j in np.flatnonzero(v)] for v in valid]
+    p3ds = [[tuple(board_points[k]) for k in ids_k] for ids_k in ids]
+    xy, status, _, lam = _ctx(ctx).refine_corners_batch(stack, [u[v] for u, v in zip(uv, valid)], half_win, max_iterations, eps)
+    return _kept_frames(len(images), live, ids, p3ds, (W, H), [0] * len(live), xy, status, lam, min_lambda)
 
 
 class ReprojectionFactor:

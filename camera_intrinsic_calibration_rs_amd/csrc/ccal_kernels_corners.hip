@@ -1,0 +1,217 @@
+// Sub-pixel corner refinement (ccal_refine_corners_batch / _dev): every coarse corner of a batch of grey images moved onto the
+// grey-level saddle by the gradient-orthogonality fit stated at the entry points in include/ccal.h.  All corners of all images in
+// ONE launch, one wavefront per corner, four per workgroup, the whole iteration of a corner inside the launch:
+//   patch    lanes stride the (2h+3)^2 positions around the iterate: four pixel loads and the f64 bilinear blend each, into the
+//            wavefront's own LDS patch (row stride 2h+3: odd, so a lane group's f64 rows do not pile on one bank pair)
+//   sums     lanes stride the (2h+1)^2 window: central differences out of the patch, the separable weight out of a 2h+1 table the
+//            wavefront filled once, five lane-private f64 sums; one xor-shuffle butterfly leaves the same totals on all 64 lanes
+//   decide   every lane: the 2 x 2 solve, the inside / degenerate / stop / drift rules - wave-uniform, so no lane leaves a loop
+//            another lane still exchanges data in.  The wavefronts of a workgroup never meet: there is no workgroup barrier.
+// The lane-to-pixel mapping is fixed by h alone (position p = lane + 64 k), nothing is accumulated across lanes but by the
+// butterfly, nothing is atomic: a corner's outputs are a pure function of its image, start and (h, max_iterations, eps).
+// Every pixel index is clamped to the image; the inside test makes the clamp a no-op, the clamp stays as the guard.
+#include <cmath>
+#include "ccal_call.hpp"
+
+namespace ccal {
+
+constexpr int kCornerWaves = 4;              // wavefronts (= corners in flight) per workgroup
+constexpr int kCornerMaxHalf = 15;           // half_win 1 .. 15: a patch of at most 33 x 33 doubles per wavefront
+constexpr int kCornerWTab = 2 * kCornerMaxHalf + 2;      // the weight table's room per wavefront (31 used)
+
+struct CornerArgs {
+    const void* img;                    // [n_img][H][W] of T
+    const int64_t* off;                 // [n_img + 1]
+    double* xy;                         // [n][2] in: start, out: result
+    int32_t* status; int32_t* iters;    // [n]
+    double* lam;                        // [n]
+    int64_t n;                          // corners in all
+    int32_t W, H, n_img;
+    int32_t h, max_it;
+    double eps;
+};
+
+// producer and consumer are lanes of the same wavefront: LDS operations of one wave execute in order, this only keeps the compiler
+// from moving accesses across the hand-off
+__device__ __forceinline__ void corner_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// floor and fraction of one coordinate, the two neighbour indices clamped to [0, n - 1]
+__device__ __forceinline__ void corner_tap(double x, int32_t n, int32_t& i0, int32_t& i1, double& ax) {
+    const double f = floor(x);
+    ax = x - f;
+    const double hi = (double)(n - 1);
+    i0 = (int32_t)fmin(fmax(f, 0.0), hi);            // NaN: fmax gives 0
+    i1 = min(i0 + 1, n - 1);
+}
+
+template <class T>
+__global__ __launch_bounds__(64 * kCornerWaves) void k_corner_refine(const CornerArgs a) {
+    extern __shared__ double corner_lds[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * kCornerWaves + wave;
+    if (g >= a.n) return;
+    const int h = a.h, side = 2 * h + 1, ps = 2 * h + 3;
+    double* P = corner_lds + (size_t)wave * (size_t)(ps * ps + kCornerWTab);
+    double* w1 = P + ps * ps;
+
+    // the image of corner g: the last k with off[k] <= g (images without corners are stepped over)
+    int lo = 0, hi = a.n_img;
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a.off[mid] <= g) lo = mid; else hi = mid;
+    }
+    const T* img = static_cast<const T*>(a.img) + (int64_t)lo * a.W * a.H;
+    const int32_t W = a.W, H = a.H;
+
+    if (lane < side) { const double t = (double)(lane - h) / (double)h; w1[lane] = exp(-(t * t)); }
+    corner_lds_sync();
+    double sw = 0.0;
+    for (int i = 0; i < side; ++i) sw += w1[i];
+    const double sum_w = sw * sw;
+
+    const double c0x = a.xy[2 * g], c0y = a.xy[2 * g + 1];
+    double cx = c0x, cy = c0y;
+    double lam = __builtin_nan("");
+    int it = 0, status;
+    const double lo_x = (double)(h + 1), hi_x = (double)(W - 2 - h), hi_y = (double)(H - 2 - h);
+    for (;;) {
+        // false for NaN; +-inf fail one of the two sides
+        const bool inside = cx >= lo_x && cx <= hi_x && cy >= lo_x && cy <= hi_y;
+        if (!inside) { status = CCAL_NO_RESULT; break; }
+        for (int p = lane; p < ps * ps; p += 64) {
+            const int pj = p / ps, pi = p - pj * ps;
+            int32_t x0, x1, y0, y1;
+            double ax, ay;
+            corner_tap(cx + (double)(pi - h - 1), W, x0, x1, ax);
+            corner_tap(cy + (double)(pj - h - 1), H, y0, y1, ay);
+            const T* r0 = img + (int64_t)y0 * W;
+            const T* r1 = img + (int64_t)y1 * W;
+            const double p00 = (double)r0[x0], p01 = (double)r0[x1], p10 = (double)r1[x0], p11 = (double)r1[x1];
+            // the difference form: a constant neighbourhood samples to exactly its value, whatever the fractions
+            const double top = p00 + ax * (p01 - p00), bot = p10 + ax * (p11 - p10);
+            P[p] = top + ay * (bot - top);
+        }
+        corner_lds_sync();
+        double sa = 0.0, sb = 0.0, sd = 0.0, su = 0.0, sv = 0.0;
+        for (int p = lane; p < side * side; p += 64) {
+            const int wj = p / side, wi = p - wj * side;
+            const double* q = P + (wj + 1) * ps + (wi + 1);
+            const double gx = q[1] - q[-1], gy = q[ps] - q[-ps];
+            const double w = w1[wi] * w1[wj];
+            const double di = (double)(wi - h), dj = (double)(wj - h);
+            const double xx = gx * gx, xy = gx * gy, yy = gy * gy;
+            sa += w * xx; sb += w * xy; sd += w * yy;
+            su += w * (xx * di + xy * dj);
+            sv += w * (xy * di + yy * dj);
+        }
+        corner_lds_sync();                 // the next iterate's patch is written after every lane has read this one
+        for (int off = 32; off > 0; off >>= 1) {
+            sa += __shfl_xor(sa, off, 64); sb += __shfl_xor(sb, off, 64); sd += __shfl_xor(sd, off, 64);
+            su += __shfl_xor(su, off, 64); sv += __shfl_xor(sv, off, 64);
+        }
+        const double tr = sa + sd, det = sa * sd - sb * sb;
+        lam = (tr - sqrt((sa - sd) * (sa - sd) + 4.0 * sb * sb)) / (2.0 * sum_w);
+        if (!(det > 1e-12 * (tr * tr))) { status = CCAL_ERR_NOT_PD; break; }
+        const double dx = (sd * su - sb * sv) / det, dy = (sa * sv - sb * su) / det;
+        cx += dx; cy += dy;
+        ++it;
+        const double e = sqrt(dx * dx + dy * dy);
+        if (e <= a.eps) { status = CCAL_OK; break; }
+        if (it >= a.max_it) { status = CCAL_ERR_NO_CONVERGENCE; break; }
+    }
+    if ((status == CCAL_OK || status == CCAL_ERR_NO_CONVERGENCE) && (fabs(cx - c0x) > (double)h || fabs(cy - c0y) > (double)h))
+        status = CCAL_NO_RESULT;           // the window slid off the corner it was given
+    if (status == CCAL_NO_RESULT || status == CCAL_ERR_NOT_PD) { cx = c0x; cy = c0y; }
+    if (lane == 0) {
+        a.xy[2 * g] = cx; a.xy[2 * g + 1] = cy;
+        a.status[g] = status; a.iters[g] = it; a.lam[g] = lam;
+    }
+}
+
+namespace {
+
+int corners_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
+                 const int64_t* offsets, double* xy_io, int half_win, int max_iterations, double eps, int32_t* status_out,
+                 int32_t* iters_out, double* lambda_min_out) {
+    char msg[160];
+    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    if (half_win < 1 || half_win > kCornerMaxHalf) return bad("half_win outside 1 .. 15");
+    if (max_iterations < 1) return bad("max_iterations < 1");
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return bad("eps negative or not finite");
+    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
+    if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
+    if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
+    if (n_img == 0) return CCAL_OK;
+    if (!images || !offsets || !status_out) return bad("NULL argument");
+    if (check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
+    const int64_t n64 = offsets[n_img];
+    if (n64 > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 corners");
+    if (n64 == 0) return CCAL_OK;
+    if (!xy_io) return bad("NULL argument");
+    const size_t n = (size_t)n64, ni = (size_t)n_img;
+    const size_t b_img = images_on_device ? 0 : (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height * ni;
+
+    // one block: offsets | images (host call) | corners, lambda_min | status, iterations
+    CallBlock blk(ctx);
+    const auto s_off = blk.add<int64_t>(ni + 1);
+    const auto s_img = blk.add<char>(b_img);
+    const auto s_xy = blk.add<double>(2 * n);
+    const auto s_lam = blk.add<double>(n);
+    const auto s_status = blk.add<int32_t>(n);
+    const auto s_iters = blk.add<int32_t>(n);
+    if (!blk.alloc()) return blk.finish(where);
+    blk.poison(s_xy, s_lam);
+    CornerArgs a = {};
+    a.img = images_on_device ? images : (const void*)blk.at(s_img);
+    a.off = blk.at(s_off); a.xy = blk.at(s_xy); a.lam = blk.at(s_lam); a.status = blk.at(s_status); a.iters = blk.at(s_iters);
+    a.n = n64; a.W = width; a.H = height; a.n_img = n_img; a.h = half_win; a.max_it = max_iterations; a.eps = eps;
+    blk.upload(s_off, offsets, ni + 1);
+    if (!images_on_device) blk.upload(s_img, images, b_img);
+    blk.upload(s_xy, xy_io, 2 * n);
+    if (blk.ok()) {
+        const int ps = 2 * half_win + 3;
+        const size_t lds = sizeof(double) * (size_t)kCornerWaves * (size_t)(ps * ps + kCornerWTab);
+        const dim3 grid((unsigned)((n + kCornerWaves - 1) / kCornerWaves));
+        if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_corner_refine<uint16_t>, grid, dim3(64 * kCornerWaves), lds, ctx->stream, a);
+        else hipLaunchKernelGGL(k_corner_refine<uint8_t>, grid, dim3(64 * kCornerWaves), lds, ctx->stream, a);
+        blk.launched();
+    }
+    blk.download(xy_io, a.xy, 2 * n);
+    blk.download(status_out, a.status, n);
+    blk.download(iters_out, a.iters, n);
+    blk.download(lambda_min_out, a.lam, n);
+    return blk.finish(where);
+}
+
+}  // namespace
+}  // namespace ccal
+
+using namespace ccal;
+
+extern "C" {
+
+int ccal_refine_corners_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images, const int64_t* offsets,
+                              double* xy_io, int half_win, int max_iterations, double eps, int32_t* status_out, int32_t* iters_out,
+                              double* lambda_min_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    return corners_call(ctx, "ccal_refine_corners_batch", false, dtype, width, height, n_img, images, offsets, xy_io, half_win,
+                        max_iterations, eps, status_out, iters_out, lambda_min_out);
+    CCAL_API_CATCH(ctx)
+}
+
+int ccal_refine_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev, const int64_t* offsets,
+                            double* xy_io, int half_win, int max_iterations, double eps, int32_t* status_out, int32_t* iters_out,
+                            double* lambda_min_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    return corners_call(ctx, "ccal_refine_corners_dev", true, dtype, width, height, n_img, images_dev, offsets, xy_io, half_win,
+                        max_iterations, eps, status_out, iters_out, lambda_min_out);
+    CCAL_API_CATCH(ctx)
+}
+
+}  // extern "C"

@@ -292,6 +292,43 @@ class Context:
             raise CcalError(rc, "ccal_undistort_map_from_host", self.last_error())
         return UndistortMap(self, h, xmap.shape[1], xmap.shape[0])
 
+    # -- from pixels to detections: sub-pixel corner refinement, batched (ccal_refine_corners_batch, ccal_kernels_corners.hip) --------
+    def _corners(self, fn, where, ptr, dtype, width, height, n_img, xy_list, half_win, max_iterations, eps):
+        if len(xy_list) != n_img:
+            raise ValueError(f"{where}: one array of corners per image")
+        offs, xy = _pack(xy_list, 2)
+        n = int(offs[-1])
+        m = max(n, 1)
+        out_xy = np.full((m, 2), np.nan)
+        out_xy[:n] = xy
+        status = np.full(m, -2, dtype=np.int32); iters = np.full(m, -2, dtype=np.int32)
+        lam = np.full(m, np.nan)
+        rc = fn(self.handle, int(dtype), int(width), int(height), int(n_img), C.c_void_p(ptr), _lp(offs), _dp(out_xy), int(half_win),
+                int(max_iterations), float(eps), _ip(status), _ip(iters), _dp(lam))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        cut = [(int(offs[k]), int(offs[k + 1])) for k in range(n_img)]
+        return tuple([arr[a:b] for a, b in cut] for arr in (out_xy, status, iters, lam))
+
+    def refine_corners_batch(self, images, xy_list, half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3):
+        """Every coarse corner of a batch of grey images moved onto the grey-level saddle, all in one launch.  images: [n][H][W],
+        uint8 or uint16; xy_list: one array [n_i, 2] of (x, y) starts per image.  Returns (xy_list, status_list, iters_list,
+        lambda_min_list), per image: positions [n_i, 2], status [n_i] int32 - _ffi.OK, ERR_NO_CONVERGENCE (the last iterate),
+        ERR_NOT_PD or NO_RESULT (the position as given) -, updates made [n_i], corner strength [n_i] (NaN: nothing evaluated)."""
+        images, dtype, channels = check_images(images, True)
+        if channels != 1:
+            raise ValueError("refine_corners_batch: single-channel images [n][H][W]")
+        n_img, H, W = images.shape[:3]
+        return self._corners(self.lib.ccal_refine_corners_batch, "ccal_refine_corners_batch", images.ctypes.data, dtype, W, H, n_img,
+                             xy_list, half_win, max_iterations, eps)
+
+    def refine_corners_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, xy_list, half_win: int = 5,
+                           max_iterations: int = 30, eps: float = 1e-3):
+        """refine_corners_batch over an image block that is already on the device (a device pointer to [n_img][height][width] of
+        dtype _ffi.PIX_U8 / PIX_U16, its writes complete or enqueued on the context's stream); corners and results are host arrays."""
+        return self._corners(self.lib.ccal_refine_corners_dev, "ccal_refine_corners_dev", images_ptr, dtype, width, height, n_img,
+                             xy_list, half_win, max_iterations, eps)
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first

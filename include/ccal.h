@@ -35,6 +35,8 @@
  *   ccal_refine_poses_batch  ReprojectionFactor + HuberLoss over the pose alone, intrinsics fixed, batched
  *   ccal_refine_rig_poses_batch
  *                            OtherCamReprojectionFactor + HuberLoss over T_0_b alone, intrinsics and extrinsics fixed, batched
+ *   ccal_refine_corners_batch / _dev
+ *                            the sub-pixel step at the end of image_to_option_feature_frame  src/data_loader.rs:36-70 (not the detector)
  *
  * Parameter layout.
  *   intr   [n_cams][CCAL_PMAX]  FULL model parameters [fx,fy,cx,cy,dist...] per camera, like
@@ -608,6 +610,54 @@ int ccal_undistort_map_download(ccal_undistort_map* map, float* xmap_out, float*
 void ccal_undistort_map_destroy(ccal_undistort_map* map);
 int ccal_remap(ccal_undistort_map* map, int dtype, int channels, int src_w, int src_h, int n_img, const void* src, void* dst);
 int ccal_remap_dev(ccal_undistort_map* map, int dtype, int channels, int src_w, int src_h, int n_img, const void* src_dev, void* dst_dev);
+
+/* ---- from pixels to detections: sub-pixel refinement of coarse corners ------------------------------
+ * The last step of every target detector (what load_feature_data's image_to_option_feature_frame ends with, src/data_loader.rs:36-70;
+ * the detector itself lives in the absent aprilgrid crate and is NOT here): each coarse corner is moved onto the grey-level saddle
+ * by the gradient-orthogonality fit below.  The rule is this project's; tests/corner_ref.py is its f64 yardstick.
+ *
+ * Images: n_img single-channel images of one size, [n_img][height][width] of CCAL_PIX_U8 or CCAL_PIX_U16; a pixel's centre is at
+ * integer coordinates, as in ccal_remap.  Image k owns the corners [offsets[k], offsets[k + 1]) of xy_io [.][2] = (x, y).
+ * I(x, y) is ccal_remap's bilinear sample, in f64 (no f32 anywhere): x0 = floor(x), ax = x - x0, x1 = min(x0 + 1, width - 1), y alike,
+ *     top = p00 + ax (p01 - p00), bot = p10 + ax (p11 - p10), I = top + ay (bot - top)
+ * - the same interpolant written in differences, so that a constant neighbourhood samples to EXACTLY its value and two equal rows
+ * to exactly equal values whatever the fractions are: a flat patch has all sums 0 and an axis-parallel edge b = 0 and a or d = 0, not
+ * rounding noise that the relative degenerate test below would have to judge.
+ * For a corner with start c0, h = half_win and c = c0, repeat:
+ *   inside      c.x >= h + 1, c.x <= width - 2 - h, c.y >= h + 1, c.y <= height - 2 - h (the patch lies in the image; the four
+ *               comparisons are exact, their right sides are integers) and both finite; else the corner ends CCAL_NO_RESULT, position c0.
+ *   patch       P(i, j) = I(c.x + i, c.y + j), i, j in [-h-1, h+1]; gx(i, j) = P(i+1, j) - P(i-1, j), gy(i, j) = P(i, j+1) - P(i, j-1)
+ *               for i, j in [-h, h] (no factor 1/2: it cancels).
+ *   weights     w(i, j) = w1(i) w1(j), w1(i) = exp(-(i / h)^2).
+ *   sums        over the window: a = sum w gx^2, b = sum w gx gy, d = sum w gy^2, u = sum w (gx^2 i + gx gy j),
+ *               v = sum w (gx gy i + gy^2 j); det = a d - b^2.
+ *   degenerate  !(det > 1e-12 (a + d)^2) - a flat patch, a single edge, sums that are not finite: CCAL_ERR_NOT_PD, position c0.
+ *   update      delta = ((d u - b v) / det, (a v - b u) / det); c += delta; iterations += 1; e = sqrt(delta.x^2 + delta.y^2).
+ *   stop        e <= eps: CCAL_OK.  Else iterations >= max_iterations: CCAL_ERR_NO_CONVERGENCE, the position is the last iterate.
+ * After a stop by either rule, the drift test: |c.x - c0.x| > h or |c.y - c0.y| > h (the window slid off the corner it was
+ * given): CCAL_NO_RESULT, position c0.
+ * Per corner: xy_io (the position), status_out, iters_out (updates made; NULL: not wanted), lambda_min_out (NULL: not wanted) = the
+ * smaller eigenvalue ((a + d) - sqrt((a - d)^2 + 4 b^2)) / 2 of [[a, b], [b, d]] divided by (sum_i w1(i))^2, at the LAST EVALUATED
+ * iterate - NaN when none was evaluated (the start was not inside).  It is a corner-strength figure a caller can threshold; it
+ * scales with the square of the image contrast.
+ * A corner's outputs are a pure function of its image, its start and (half_win, max_iterations, eps): they do not depend on its
+ * place in the batch or on what else is in it, and they are bit-identical from run to run (a fixed lane-to-pixel mapping,
+ * lane-private sums, one xor butterfly, no atomics).
+ * ccal_refine_corners_batch: host pointers.  ccal_refine_corners_dev: `images_dev` is a device pointer (the output of
+ * ccal_remap_dev on this context's stream, or a block whose writes are complete); corners and outputs stay host arrays.  Both
+ * return when the outputs are written.
+ * CCAL_ERR_INVALID_ARG, nothing launched or written: half_win outside 1 .. 15, max_iterations < 1, eps < 0 or not finite, a dtype
+ * other than the two, width, height <= 0 or n_img < 0, more than 2^31 - 1 pixels in an image or corners in the call, offsets that
+ * do not start at 0 or decrease, a NULL required pointer (with n_img > 0: images, offsets, status_out; xy_io when there are
+ * corners).  n_img == 0 and an image without corners are valid. */
+int ccal_refine_corners_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images,
+                              const int64_t* offsets /* [n_img + 1] */, double* xy_io /* [.][2] in: start, out: result */,
+                              int half_win, int max_iterations, double eps,
+                              int32_t* status_out, int32_t* iters_out /* or NULL */, double* lambda_min_out /* or NULL */);
+int ccal_refine_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev,
+                            const int64_t* offsets /* [n_img + 1] */, double* xy_io /* [.][2] */,
+                            int half_win, int max_iterations, double eps,
+                            int32_t* status_out, int32_t* iters_out /* or NULL */, double* lambda_min_out /* or NULL */);
 
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
