@@ -10,6 +10,10 @@ of the path independently of both the oracle's C++ and the HIP kernels:
                        numerical differentiation at 50 digits (good to ~1e-25), for UCM / EUCM / KB4 /
                        OPENCV5, with and without xy_same_focal.  Rotation uses the matrix Rodrigues
                        formula (NOT the quaternion path the oracle restates).
+  factor_wide_golden.json the same, at the geometry the synthetic problems never reach: rotation angles past pi
+                       and around 2 pi, view angles up to 3 rad (z < 0, the octant seams of the device atan2, the optical
+                       axis), large extrinsic angles; kept where the oracle is within half of the tolerance of mpmath
+                       (`python oracle/gen_golden.py wide` writes this file alone).
   reference_tests.json the known answers of the reference's own tests on this path.
   converged_golden.json an independent converged optimum: scipy.optimize.least_squares (TRF, linear
                        loss, analytic-free 2-point Jacobian replaced by mp-free numpy model) on a small
@@ -191,8 +195,222 @@ def gen_converged():
     print("converged intr", sol.x[:6], "cost", data["cost"], "nfev", sol.nfev)
 
 
+# ---- factor_wide_golden.json: the geometry make_problem / gen_factor_golden never visit ------------------------------------
+WIDE_R_ATOL, WIDE_J_RTOL = 1e-10, 1e-11          # tests/test_gpu_eval.py's R_ATOL / J_RTOL
+WIDE_DROP_CAP = 0.10
+WIDE_ANGLES = (0.3, 1.0, np.pi / 2, 2.0, np.pi - 1e-6, np.pi + 1e-6, 3.5, 4.0, 5.5, 2 * np.pi - 1e-3, 2 * np.pi + 1e-3,
+               2 * np.pi - 1e-9, 2 * np.pi + 1e-9, 7.0, 9.0, 4 * np.pi - 0.01, 12.9, 40.0)
+WIDE_EXTR_ANGLES = (1e-4, 1.5, 3.3)
+TAN_PI_8 = 0.41421356237309503
+WIDE_PARAMS = {
+    UCM: [190.89618687183938, 190.87022285882367, 254.9375370481962, 256.86414483060787, 0.6283550447635853],
+    EUCM: [190.89618687183938, 190.87022285882367, 254.9375370481962, 256.86414483060787, 0.6283550447635853, 1.0458678747533083],
+    KB4: [190.9, 190.9, 255.0, 257.0, 0.003, 0.0007, -0.002, 0.0002],
+    OCV5: [380.0, 380.0, 255.0, 257.0, -0.28, 0.07, 0.0002, 0.00002, 0.001],
+}
+
+
+def project_wide(model, p, pt):
+    """project() with KB4's limit on the optical axis (r = 0: theta_d / r -> 1 / z times x = y = 0)"""
+    if model == KB4 and pt[0] == 0 and pt[1] == 0:
+        return p[2], p[3]
+    return project(model, p, pt)
+
+
+def _np_rot(w):
+    return np.array(rodrigues([mp.mpf(float(a)) for a in w]).tolist(), dtype=float)
+
+
+def _step(x, k):
+    for _ in range(abs(k)):
+        x = float(np.nextafter(x, np.inf if k > 0 else -np.inf))
+    return x
+
+
+def _unit(rng):
+    a = rng.normal(0, 1, 3)
+    return a / np.linalg.norm(a)
+
+
+def _spin(pt, rng):
+    """the point turned about the optical axis by a seeded azimuth: off the image plane's coordinate axes.  Where the camera-frame
+    point is the rounded result of a chain of transforms, a coordinate that should be 0 is 1e-17 with an absolute error of 1e-16,
+    and KB4's d v / d k4 = fy theta^9 y / r (4e5 at theta = 3 pi/4) turns that into 4e-11 against a Jacobian entry of ~0: not
+    something any double-precision evaluation can meet, so such points are only used where they are exact."""
+    a = rng.uniform(0.3, 1.2) + (np.pi / 2) * int(rng.integers(4))
+    return [pt[0] * np.cos(a) - pt[1] * np.sin(a), pt[0] * np.sin(a) + pt[1] * np.cos(a), pt[2]]
+
+
+def ucm_theta_limit(alpha, beta):
+    """polar angle at which z = -w rho, rho = sqrt(beta r^2 + z^2), w = alpha / (1 - alpha) (alpha <= 1/2) else (1 - alpha) / alpha"""
+    w = alpha / (1 - alpha) if alpha <= 0.5 else (1 - alpha) / alpha
+    return np.pi / 2 + np.arctan(w * np.sqrt(beta) / np.sqrt(1 - w * w))
+
+
+def _wide_view_points(model, rng):
+    """regime B: (params override, camera-frame point, exact) per candidate; exact points need the board point X = 0"""
+    out = []
+    az = iter(np.tile([0.6, 2.3, 3.9, 5.5], 200) + rng.uniform(-0.3, 0.3, 800))          # all four quadrants in turn
+
+    def at(theta, rad=1.0):
+        a = next(az)
+        return [rad * np.sin(theta) * np.cos(a), rad * np.sin(theta) * np.sin(a), rad * np.cos(theta)]
+
+    if model == KB4:
+        out.append(({}, [0.0, 0.0, 1.0], True))                                            # theta = 0 exactly
+        for r in (5e-9, 2e-8):                                                             # either side of kb4_small_radius
+            a = next(az)
+            out.append(({}, [r * np.cos(a), r * np.sin(a), 1.0], True))
+        for th in (1e-6, 1e-3, 0.3, 1.5, 1.7, 5 * np.pi / 8, 3 * np.pi / 4, 7 * np.pi / 8, 2.6, 3.0):
+            out.append(({}, at(th, rng.uniform(0.6, 1.4)), False))
+        a = next(az)
+        out.append(({}, [0.8 * np.cos(a), 0.8 * np.sin(a), 0.0], True))                    # theta = pi/2: z = 0 exactly
+        # the octant seams of fast_atan2_pos, r exact (the point on a coordinate axis of the image plane), +- 2 ulp, both signs of z
+        for i, (seam, vary_r) in enumerate(((TAN_PI_8, True), (1.0, True), (TAN_PI_8, False))):
+            for sz in (1.0, -1.0):
+                for k in (-2, 2):
+                    base = (0.9, 1.1, 0.7)[i]
+                    r, z = (_step(seam * base, k), base) if vary_r else (base, _step(seam * base, k))
+                    x, y = [(r, 0.0), (0.0, r), (-r, 0.0), (0.0, -r)][(i + (k > 0) + 2 * (sz < 0)) % 4]
+                    out.append(({}, [x, y, sz * z], True))
+    elif model in (UCM, EUCM):
+        for alpha in (0.3, 0.6, 0.9):
+            for beta in ((0.7, 1.3) if model == EUCM else (1.0,)):
+                lim = ucm_theta_limit(alpha, beta)
+                for frac in ((0.35, 0.65, 0.9) if model == UCM else (0.5, 0.9)):
+                    ov = {4: alpha, 5: beta} if model == EUCM else {4: alpha}
+                    out.append((ov, at(frac * lim, rng.uniform(0.6, 1.4)), False))
+    else:
+        for th in (0.05, 0.3, 0.6, 0.9, 1.0, 1.1, 1.2, 1.2):
+            out.append(({}, at(th, rng.uniform(0.6, 1.4)), False))
+    return out
+
+
+def _wide_case(model, one_focal, other, th_full, w0, cam_pt, X, w1, rng):
+    """vec, p3d, p2d of one single-corner case whose camera-frame point is cam_pt (exactly when X = 0 and not other)"""
+    th = list(th_full)
+    if one_focal:
+        th = [th[0]] + th[2:]
+    p = np.array(cam_pt, dtype=float)
+    RX = _np_rot(w0) @ np.array(X, dtype=float)
+    vec = th + [float(a) for a in w0]
+    if other:
+        t1 = np.array([-0.101, 0.002, 0.001]) + rng.uniform(-0.01, 0.01, 3)
+        t0 = _np_rot(w1).T @ (p - t1) - RX
+        vec += [float(a) for a in t0] + [float(a) for a in w1] + [float(a) for a in t1]
+    else:
+        vec += [float(a) for a in (p - RX)]
+    mvec, mX = [mp.mpf(a) for a in vec], [mp.mpf(a) for a in X]
+    u, v = residual_wide(model, one_focal, other, mvec, mX, (mp.mpf(0), mp.mpf(0)))
+    obs = [f32(float(u) + rng.normal(0, 0.3)), f32(float(v) + rng.normal(0, 0.3))]
+    return vec, X, obs
+
+
+def residual_wide(model, one_focal, other, vec, X, obs):
+    P = NP[model]
+    pe = P - (1 if one_focal else 0)
+    th = list(vec[:pe])
+    if one_focal:
+        th = [th[0], th[0]] + th[1:]
+    p = rodrigues(vec[pe:pe + 3]) * mp.matrix(X) + mp.matrix(vec[pe + 3:pe + 6])
+    if other:
+        p = rodrigues(vec[pe + 6:pe + 9]) * p + mp.matrix(vec[pe + 9:pe + 12])
+    u, v = project_wide(model, th, (p[0], p[1], p[2]))
+    return u - obs[0], v - obs[1]
+
+
+def jacobian_wide(model, one_focal, other, vec, X, obs):
+    n = len(vec)
+    J = [[None] * n for _ in range(2)]
+    for k in range(n):
+        for row in range(2):
+            def f(t, k=k, row=row):
+                vv = list(vec)
+                vv[k] = t
+                return residual_wide(model, one_focal, other, vv, X, obs)[row]
+            J[row][k] = mp.diff(f, vec[k])
+    return J
+
+
+def gen_factor_wide_golden():
+    """Single-corner cases in the same schema as factor_golden.json at the rotation angles (regime A), view angles (regime B) and
+    both (regime C) that the synthetic problems never reach.  A case is kept only where double precision can meet the project's
+    tolerance at all: where the oracle (dual numbers in doubles, oracle/binding.py) is within HALF of R_ATOL / J_RTOL of mpmath.
+    At most 10 % of the candidates of any (model, regime) may go that way; the counts are printed and recorded in the note."""
+    from oracle import binding as ob
+    rng = np.random.default_rng(20261019)
+    cand = []                                              # (model, regime, one_focal, other, th_full, w0, cam_pt, X, w1)
+    combo = 0
+
+    def flags():
+        nonlocal combo
+        combo += 1
+        return bool(combo & 1), bool(combo & 2), np.array(WIDE_EXTR_ANGLES[(combo // 4) % 3] * _unit(rng))
+
+    def generic_X():
+        return [f32(rng.uniform(0, 0.66)), f32(rng.uniform(-0.66, 0)), f32(rng.uniform(-0.02, 0.02))]
+
+    def front(rad=1.0):
+        return [rng.uniform(-0.35, 0.35) * rad, rng.uniform(-0.35, 0.35) * rad, rng.uniform(0.7, 1.1) * rad]
+
+    for model in (UCM, EUCM, KB4, OCV5):
+        base = [t * (1 + 0.02 * rng.uniform(-1, 1)) for t in WIDE_PARAMS[model]]
+        for ang in WIDE_ANGLES:                            # A: rotation angle, the point in front of the camera
+            of, ot, w1 = flags()
+            cand.append((model, "A", of, ot, base, ang * _unit(rng), front(), generic_X(), w1))
+        for ov, pt, exact in _wide_view_points(model, rng):    # B: view angle, moderate rotation
+            th = list(base)
+            for i, val in ov.items():
+                th[i] = val
+            of, ot, w1 = flags()
+            X = [0.0, 0.0, 0.0] if exact else generic_X()
+            cand.append((model, "B", of, ot and not exact, th, rng.uniform(-0.5, 0.5, 3), pt, X, w1))
+            if exact:                                      # and the same point through the other-camera chain, as close as doubles get
+                cand.append((model, "B", of, True, th, rng.uniform(-0.5, 0.5, 3), _spin(pt, rng), X, w1))
+        views = _wide_view_points(model, rng)
+        for i in range(8):                                 # C: both
+            ov, pt, exact = views[int(rng.integers(len(views)))]
+            th = list(base)
+            for j, val in ov.items():
+                th[j] = val
+            of, ot, w1 = flags()
+            ang = WIDE_ANGLES[int(rng.integers(len(WIDE_ANGLES)))]
+            cand.append((model, "C", of, ot, th, ang * _unit(rng), _spin(pt, rng) if exact else pt, generic_X(), w1))
+
+    cases, counts = [], {}
+    for model, regime, of, ot, th, w0, pt, X, w1 in cand:
+        vec, X, obs = _wide_case(model, of, ot, th, w0, pt, X, w1, rng)
+        mvec, mX, mobs = [mp.mpf(a) for a in vec], [mp.mpf(a) for a in X], [mp.mpf(a) for a in obs]
+        r = [float(a) for a in residual_wide(model, of, ot, mvec, mX, mobs)]
+        J = [[float(a) for a in row] for row in jacobian_wide(model, of, ot, mvec, mX, mobs)]
+        pe = NP[model] - (1 if of else 0)
+        ro, Jo = ob.factor(model, of, vec[:pe], vec[pe:pe + 6], X, obs, pose1=vec[pe + 6:pe + 12] if ot else None)
+        dr = float(np.abs(ro - r).max())
+        dJ = float((np.abs(Jo - np.array(J)) / np.maximum(1.0, np.abs(J))).max())
+        keep = np.isfinite(ro).all() and np.isfinite(Jo).all() and dr <= 0.5 * WIDE_R_ATOL and dJ <= 0.5 * WIDE_J_RTOL
+        c = counts.setdefault(f"{model}{regime}", [0, 0])
+        c[0] += 1
+        c[1] += 0 if keep else 1
+        print(f"model {model} regime {regime} of {int(of)} other {int(ot)} |w0| {np.linalg.norm(w0):.9g} point {pt}: "
+              f"oracle dr {dr:.2e} dJ {dJ:.2e} {'kept' if keep else 'DROPPED'}")
+        if keep:
+            cases.append(dict(model=model, regime=regime, one_focal=of, other=ot, vec=vec, p3d=X, p2d=obs, r=r, J=J))
+    summary = ", ".join(f"{k}: {n - d} of {n}" for k, (n, d) in sorted(counts.items()))
+    print("kept per (model, regime):", summary)
+    over = {k: v for k, v in counts.items() if v[1] > WIDE_DROP_CAP * v[0]}
+    assert not over, f"more than {WIDE_DROP_CAP:.0%} of the candidates dropped: {over}"
+    with open(os.path.join(OUT, "factor_wide_golden.json"), "w") as f:
+        json.dump(dict(note="mpmath 50-digit r and J, schema of factor_golden.json; regime A rotation angle, B view angle, C both; "
+                            "kept where the oracle is within half of R_ATOL / J_RTOL of mpmath, kept per (model, regime): " + summary,
+                       cases=cases), f, indent=1)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["wide"]:                    # only the file that needs no scipy and no reference tree
+        gen_factor_wide_golden()
+        sys.exit(0)
     gen_reference_tests()
     gen_converged()
     gen_factor_golden()
+    gen_factor_wide_golden()

@@ -62,6 +62,40 @@ def test_eval_golden_mpmath(gpu_ctx, golden_dir):
         gp.close()
 
 
+def test_eval_wide_golden_mpmath(gpu_ctx, golden_dir):
+    """factor_wide_golden.json - rotation angles past pi and around 2 pi, view angles up to 3 rad (z < 0, every octant seam of
+    fast_atan2_pos, the optical axis and either side of the KB4 threshold), extrinsic angles 1e-4 .. 3.3 - as 1-frame / 1-corner
+    problems through ccal_eval, and through ccal_reprojection_errors (project_uv: a separate code path, IEEE sqrt and division)
+    against the mpmath residual's norm at test_reprojection_errors_and_validation's tolerance."""
+    cases = json.load(open(os.path.join(golden_dir, "factor_wide_golden.json")))["cases"]
+    assert len(cases) >= 150
+    worst = [0.0, 0.0, 0.0]
+    for c in cases:
+        m = c["model"]; P = synth.MODEL_NPARAMS[m]; pe = P - (1 if c["one_focal"] else 0)
+        vec = c["vec"]
+        th = vec[:pe]
+        full = ([th[0], th[0]] + th[1:]) if c["one_focal"] else th
+        n_cams = 2 if c["other"] else 1
+        intr = np.zeros((n_cams, synth.PMAX)); intr[:, :P] = full
+        extr = np.zeros((n_cams, 6))
+        if c["other"]:
+            extr[1] = vec[pe + 6:pe + 12]
+        d, keep = make_desc(n_cams, [m] * n_cams, [512.0] * n_cams, [512.0] * n_cams, c["one_focal"], 1,
+                            [n_cams - 1], [0], [0, 1], [c["p3d"][0]], [c["p3d"][1]], [c["p3d"][2]],
+                            [c["p2d"][0]], [c["p2d"][1]], 1.0)
+        gp = Problem(gpu_ctx, d, keep)
+        pose = np.array([vec[pe:pe + 6]])
+        r, J = gp.eval(intr, pose, extr)
+        e = gp.reprojection_errors(intr, pose, extr)
+        gp.close()
+        Jg = np.array(c["J"]).ravel()
+        assert np.isfinite(r).all() and np.isfinite(J).all() and e.shape == (1,)
+        err = (np.abs(r[0] - c["r"]).max(), (np.abs(J - Jg) / np.maximum(1.0, np.abs(Jg))).max(), abs(e[0] - np.hypot(*c["r"])))
+        worst = [max(a, b) for a, b in zip(worst, err)]
+        assert err[0] <= R_ATOL and err[1] <= J_RTOL and err[2] <= 1e-10, (c["model"], c["regime"], c["one_focal"], c["other"], vec, err)
+    print(f"wide golden: {len(cases)} cases, worst |dr| {worst[0]:.2e} rel |dJ| {worst[1]:.2e} |d norm| {worst[2]:.2e}")
+
+
 def test_reference_known_answer(gpu_ctx, golden_dir):
     """tests/optimization_test.rs:36-80 through the C ABI: zero residual at GT, non-zero after tvec += 0.1."""
     t = json.load(open(os.path.join(golden_dir, "reference_tests.json")))["test_reprojection_factor"]

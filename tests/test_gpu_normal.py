@@ -421,6 +421,70 @@ def test_gram_lanes_per_frame_every_mapping(lpf):
     assert "LPF-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
 
 
+def _wide_check(gp, op, sp, lam):
+    S, b, cost = gp.build_normal(sp.intr0, sp.poses0, sp.extr0, lam=lam)
+    So, bo, costo = op.build_normal(sp.intr0, sp.poses0, sp.extr0, lam=lam)
+    assert np.isfinite(S).all() and np.isfinite(b).all()
+    assert abs(cost - costo) <= 1e-12 * costo
+    assert np.abs(S - So).max() <= 1e-9 * np.abs(So).max()
+    assert np.abs(b - bo).max() <= 1e-9 * np.abs(bo).max()
+    assert np.abs(S - S.T).max() <= 1e-12 * np.abs(S).max()
+    return np.abs(S - So).max() / np.abs(So).max(), np.abs(b - bo).max() / np.abs(bo).max()
+
+
+@pytest.mark.parametrize("model", ["ucm", "eucm", "kb4", "opencv5"])
+@pytest.mark.parametrize("one_focal", [False, True])
+def test_build_normal_wide_geometry(gpu_ctx, oracle, model, one_focal):
+    """Mode N on frames made only of the corners make_problem never generates (tests/wide_geometry_cases.py: rotation angles 0.3 ..
+    12.9 about seeded axes, view angles up to 3 rad for KB4 and 0.9 of the validity limit for UCM / EUCM, z < 0, Huber on with
+    outliers) at test_build_normal_matches_oracle's tolerances: the plain single-camera problem (k_gram1v; OPENCV5: k_gram2) and
+    a two-camera rig of the same model at an extrinsic angle of 1.5 rad (the general loop)."""
+    import wide_geometry_cases as wg
+    for n_cams in (1, 2):
+        sp = wg.make_wide_problem(model, n_cams, one_focal)
+        gp, op = _pair(gpu_ctx, oracle, sp)
+        for lam in (0.0, 1e-3):
+            dS, db = _wide_check(gp, op, sp, lam)
+            print(f"wide {model} one_focal {one_focal} cams {n_cams} lam {lam}: rel dS {dS:.2e} db {db:.2e}")
+        gp.close()
+
+
+_WIDE_LPF_SCRIPT = """
+import numpy as np, sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {root!r} + "/tests")
+import test_gpu_normal as T, wide_geometry_cases as wg
+from camera_intrinsic_calibration_rs_amd import _ffi
+from camera_intrinsic_calibration_rs_amd.engine import Context, Problem
+from oracle import binding as ob
+ctx = Context(0, lib=_ffi.load_for_switches())
+for model, n_cams, one_focal in {cases!r}:
+    sp = wg.make_wide_problem(model, n_cams, one_focal)
+    gp = Problem.from_synth(ctx, sp); op = ob.OracleProblem.from_synth(sp)
+    for lam in (0.0, 1e-3):
+        print(model, n_cams, one_focal, lam, *T._wide_check(gp, op, sp, lam))
+print("WIDE-LPF-OK")
+"""
+
+
+@pytest.mark.parametrize("lpf", [6, 8, 12, 16, 32, 64])
+def test_build_normal_wide_geometry_every_mapping(lpf):
+    """The same problems through every lanes-per-frame mapping of both copies of the projection formulas, forced as in
+    test_gram_lanes_per_frame_every_mapping (switches of the second library, read once per process, hence the subprocesses):
+    k_gram1v (CCAL_GRAM2=0, CCAL_GRAMV_LPF) for a single KB4 and EUCM camera, and k_gram2 - the folded and mirrored copy of
+    ccal_kernels_gram2.hip, whose odd lanes take the v row with u and v exchanged - (CCAL_GRAM2=1, CCAL_GRAM2_LPF) for the same
+    two and for two-camera rigs of every model (the general loop's k_gram2g): every octant of fast_atan2_pos and z < 0 on both."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    single = [("kb4", 1, False), ("eucm", 1, False), ("kb4", 1, True), ("eucm", 1, True)]
+    rigs = [("ucm", 2, False), ("eucm", 2, False), ("kb4", 2, False), ("opencv5", 2, False)]
+    for gram2, cases in (("0", single), ("1", single + rigs)):
+        env = dict(os.environ, CCAL_GRAMV_LPF=str(lpf), CCAL_GRAM2_LPF=str(lpf), CCAL_GRAM2=gram2)
+        out = subprocess.run([sys.executable, "-c", _WIDE_LPF_SCRIPT.format(root=root, cases=cases)], env=env, capture_output=True,
+                             text=True, timeout=300)
+        print(out.stdout)
+        assert "WIDE-LPF-OK" in out.stdout, (gram2, out.stdout[-2000:] + out.stderr[-4000:])
+
+
 def _tile(sp, rep):
     """`rep` copies of a single-camera synthetic problem, frames renumbered (a large problem without regenerating it)."""
     import dataclasses
