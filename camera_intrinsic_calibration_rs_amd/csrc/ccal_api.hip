@@ -76,6 +76,8 @@ int ccal_ctx_create(int device_id, void* hip_stream, ccal_ctx** out) {
 static void ctx_free(ccal_ctx* ctx) {
     ctx_worker_destroy(ctx);
     (void)hipSetDevice(ctx->device);
+    // the batch table first: without destroy_requested (no problem was alive) its release lands in the cache, which the clear then frees
+    ctx_release(ctx, ctx->d_batch_tab, false); ctx_release(ctx, ctx->h_batch_tab, true);
     ctx_cache_clear(ctx);
     if (!ctx->pinned.empty()) {
         (void)hipSetDevice(ctx->device);
@@ -83,11 +85,6 @@ static void ctx_free(ccal_ctx* ctx) {
         for (auto& pr : ctx->pinned) (void)hipHostUnregister(pr.first);
         (void)hipGetLastError();
         ctx->pinned.clear();
-    }
-    if (ctx->d_batch_tab || ctx->h_batch_tab) {
-        (void)hipSetDevice(ctx->device);
-        if (ctx->d_batch_tab) (void)hipFree(ctx->d_batch_tab);
-        if (ctx->h_batch_tab) (void)hipHostFree(ctx->h_batch_tab);
     }
     if (ctx->own_stream && ctx->stream) { (void)hipSetDevice(ctx->device); (void)hipStreamDestroy(ctx->stream); }
     delete ctx;
@@ -117,7 +114,7 @@ int ccal_pin_buffer(ccal_ctx* ctx, void* host_ptr, size_t bytes) {
     CCAL_API_TRY
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (auto& pr : ctx->pinned) if (pr.first == host_ptr) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_pin_buffer: this address is pinned already");
-    if (pinned_device_ptr(host_ptr, bytes)) return CCAL_OK;          // pinned by the caller itself (hipHostMalloc / hipHostRegister): nothing to do
+    if (pinned_device_ptr(host_ptr, bytes)) return CCAL_OK;          // pinned by the caller itself (allocated pinned, or registered): nothing to do
     ctx->pinned.reserve(ctx->pinned.size() + 1);
     const hipError_t e = hipHostRegister(host_ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, CCAL_ERR_HIP, (std::string("ccal_pin_buffer: hipHostRegister: ") + hipGetErrorString(e)).c_str()); }
@@ -232,7 +229,7 @@ int ccal_problem_create(ccal_ctx* ctx, const ccal_problem_desc* d, ccal_problem*
             }
         }
     }
-    // ONE device allocation, sliced (a calibration session creates its problem once: sixteen hipMalloc + memset pairs were a third of
+    // ONE device allocation, sliced (a calibration session creates its problem once: sixteen allocate + memset pairs were a third of
     // ccal_problem_create's 0.25 ms at 600 frames): ProblemLayout, ccal_internal.hpp
     size_t cam_obs[CCAL_MAX_CAMS];
     for (int c = 0; c < d->n_cams; ++c) cam_obs[c] = p->cams[c].obs.size();
@@ -477,7 +474,7 @@ int ccal_init_poses(ccal_problem* p, const double* intr, int min_points, double*
     int rc = ccal_upload_params(p, intr, nullptr, nullptr);
     if (rc != CCAL_OK) return rc;
     const size_t no = (size_t)std::max(p->n_obs, 1);
-    // the two temporaries are slices of the problem's scratch block (kept for the next call: no hipMalloc / hipFree pair per call)
+    // the two temporaries are slices of the problem's scratch block (kept for the next call: no allocate / free pair per call)
     const PoseScratch l((size_t)p->n_obs);
     HIP_TRY(ctx, ensure_scratch(p, l.plan));
     double* d_po = Bound{ p->d_scratch }.at(l.poses);

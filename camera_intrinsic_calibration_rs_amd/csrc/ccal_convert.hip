@@ -15,7 +15,9 @@
 #include <cstdio>
 #include <string>
 
+#include "ccal_call.hpp"
 #include "ccal_device.hpp"
+#include "ccal_host_gn.hpp"
 #include "ccal_internal.hpp"
 #include "ccal_model_inverse.hpp"
 
@@ -97,31 +99,13 @@ __global__ __launch_bounds__(256) void k_convert_gram(const ConvArgs a) {
 }
 
 namespace {
-bool chol_host(double* A, int n) {
-    for (int j = 0; j < n; ++j) {
-        double s = A[j * n + j];
-        for (int k = 0; k < j; ++k) s -= A[j * n + k] * A[j * n + k];
-        if (!(s > 0.0) || !std::isfinite(s)) return false;
-        const double l = std::sqrt(s);
-        A[j * n + j] = l;
-        for (int i = j + 1; i < n; ++i) {
-            double t = A[i * n + j];
-            for (int k = 0; k < j; ++k) t -= A[i * n + k] * A[j * n + k];
-            A[i * n + j] = t / l;
-        }
-    }
-    return true;
-}
-void chol_solve_host(const double* L, int n, double* x) {
-    for (int i = 0; i < n; ++i) { double t = x[i]; for (int k = 0; k < i; ++k) t -= L[i * n + k] * x[k]; x[i] = t / L[i * n + i]; }
-    for (int i = n - 1; i >= 0; --i) { double t = x[i]; for (int k = i + 1; k < n; ++k) t -= L[k * n + i] * x[k]; x[i] = t / L[i * n + i]; }
-}
 // bounds of set_problem_parameter_bound (src/util.rs:29-48); distortion part from the context's conventions table
 void reference_bounds(const ccal_model_conventions& cv, int model, double w, double h, double* lo, double* hi) {
     lo[0] = 0.0; hi[0] = 10000.0; lo[1] = 0.0; hi[1] = 10000.0; lo[2] = 0.0; hi[2] = w; lo[3] = 0.0; hi[3] = h;
     for (int i = 4; i < model_np(model); ++i) { lo[i] = cv.dist_lo[model][i - 4]; hi[i] = cv.dist_hi[model][i - 4]; }
 }
-inline double huber_w(double s, double delta) { return s <= delta * delta ? 1.0 : delta / std::sqrt(s); }
+template <int M> struct LaunchRays { static void go(int g, hipStream_t st, const ConvArgs& a) { hipLaunchKernelGGL(k_convert_rays<M>, dim3(g), dim3(256), 0, st, a); } };
+template <int M> struct LaunchGram { static void go(int g, hipStream_t st, const ConvArgs& a) { hipLaunchKernelGGL(k_convert_gram<M>, dim3(g), dim3(256), 0, st, a); } };
 }  // namespace
 
 }  // namespace ccal
@@ -135,7 +119,7 @@ extern "C" int ccal_convert_model(ccal_ctx* ctx, int src_model, const double* sr
     CCAL_API_TRY
     const int PS = ccal_model_num_params(src_model), P = ccal_model_num_params(tgt_model);
     if (PS < 0 || P < 0 || !src_params || !tgt_params_io || disabled_distortions < 0 || disabled_distortions > P - 4 ||
-        !(width >= 1.0) || !(height >= 1.0)) { ctx->err = "ccal_convert_model: invalid argument"; return CCAL_ERR_INVALID_ARG; }
+        !(width >= 1.0) || !(height >= 1.0)) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_convert_model: invalid argument");
     ccal_report R = {};
     if (src_model == kUCM && tgt_model == kEUCM) {                  // src/util.rs:229-235: closed form
         for (int i = 0; i < 5; ++i) tgt_params_io[i] = src_params[i];
@@ -149,35 +133,34 @@ extern "C" int ccal_convert_model(ccal_ctx* ctx, int src_model, const double* sr
         if (rep) *rep = R;
         return CCAL_OK;
     }
-    if (src_model >= kNumModels || tgt_model >= kNumModels) {
-        // EUCMT is a parameter container here: its projection lives only in the absent camera-intrinsic-model crate
-        ctx->err = "ccal_convert_model: EUCMT can only be the target of the closed-form UCM conversion";
-        return CCAL_ERR_UNSUPPORTED;
-    }
+    // EUCMT is a parameter container here: its projection lives only in the absent camera-intrinsic-model crate
+    if (src_model >= kNumModels || tgt_model >= kNumModels)
+        return fail(ctx, CCAL_ERR_UNSUPPORTED, "ccal_convert_model: EUCMT can only be the target of the closed-form UCM conversion");
     ccal_solver_opts o;
     if (opts) o = *opts; else ccal_set_defaults(&o);
     const double big = std::max(width, height);
     const uint32_t edge = (uint32_t)big / 100u;
     const int steps = (int)(big / 30.0);
-    if (steps < 1 || (uint32_t)height <= 2 * edge || (uint32_t)width <= 2 * edge) { ctx->err = "ccal_convert_model: image too small for the grid"; return CCAL_ERR_INVALID_ARG; }
+    if (steps < 1 || (uint32_t)height <= 2 * edge || (uint32_t)width <= 2 * edge) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_convert_model: image too small for the grid");
     const int n_rows = (int)(((uint32_t)height - 2 * edge + steps - 1) / steps);
     const int n_cols = (int)(((uint32_t)width - 2 * edge + steps - 1) / steps);
     const int n_grid = n_rows * n_cols;
     const int NT = P * (P + 1) / 2, NA = NT + P + 2;
 
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    double* d_buf = nullptr;                    // [src 10 | tgt 10 | out 64 | rays]
-    HIP_TRY(ctx, hipMalloc((void**)&d_buf, sizeof(double) * (size_t)(20 + 64 + (size_t)n_grid * CONV_REC)));
-    struct Free { double* p; ~Free() { (void)hipFree(p); } } guard{ d_buf };
-    HIP_TRY(ctx, test_poison_f64(ctx, d_buf, sizeof(double) * (size_t)(20 + 64 + (size_t)n_grid * CONV_REC), false, st));
+    CallBlock blk(ctx);
+    const auto s_src = blk.add<double>(CCAL_PMAX);
+    const auto s_tgt = blk.add<double>(CCAL_PMAX);
+    const auto s_out = blk.add<double>(64);
+    const auto s_rays = blk.add<double>((size_t)n_grid * CONV_REC);
+    if (!blk.alloc()) return blk.finish("ccal_convert_model");
+    blk.poison(s_src, s_rays);
     // The fit runs in the kernels' canonical OPENCV5 order (k1, k2, p1, p2, k3): both parameter vectors are permuted HERE, at the
     // boundary (ccal_model_conventions.ocv5_order), the kernels get the identity
     ModelRt rt = model_rt(ctx);
     rt.ocv5_perm = kOcv5IdentityPerm;
     const int32_t* ord = ctx->conv.ocv5_order;
     auto canon = [&](int model, int i) { return (model == kOCV5 && i >= 4) ? 4 + ord[i - 4] : i; };     // canonical index -> caller's index
-    ConvArgs a{ d_buf, d_buf + 10, d_buf + 84, n_rows, n_cols, (int32_t)edge, steps, d_buf + 20, rt };
+    const ConvArgs a{ blk.at(s_src), blk.at(s_tgt), blk.at(s_rays), n_rows, n_cols, (int32_t)edge, steps, blk.at(s_out), rt };
 
     double th[CCAL_PMAX] = { 0 }, lo[CCAL_PMAX], hi[CCAL_PMAX], src_c[CCAL_PMAX] = { 0 };
     for (int i = 0; i < PS; ++i) src_c[i] = src_params[canon(src_model, i)];
@@ -189,57 +172,42 @@ extern "C" int ccal_convert_model(ccal_ctx* ctx, int src_model, const double* sr
     }
     reference_bounds(ctx->conv, tgt_model, width, height, lo, hi);
 
-    HIP_TRY(ctx, hipMemcpyAsync(d_buf, src_c, sizeof(double) * PS, hipMemcpyHostToDevice, st));
-    switch (src_model) {
-        case kUCM: hipLaunchKernelGGL(k_convert_rays<kUCM>, dim3((n_grid + 255) / 256), dim3(256), 0, st, a); break;
-        case kEUCM: hipLaunchKernelGGL(k_convert_rays<kEUCM>, dim3((n_grid + 255) / 256), dim3(256), 0, st, a); break;
-        case kKB4: hipLaunchKernelGGL(k_convert_rays<kKB4>, dim3((n_grid + 255) / 256), dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(k_convert_rays<kOCV5>, dim3((n_grid + 255) / 256), dim3(256), 0, st, a); break;
-    }
-    HIP_TRY(ctx, hipGetLastError());
+    blk.upload(s_src, src_c, (size_t)PS);
+    if (blk.ok()) { launch_model<LaunchRays>(src_model, (n_grid + 255) / 256, ctx->stream, a); blk.launched(); }
 
     double out[64];
-    auto eval = [&](const double* t) -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(d_buf + 10, t, sizeof(double) * P, hipMemcpyHostToDevice, st));
-        switch (tgt_model) {
-            case kUCM: hipLaunchKernelGGL(k_convert_gram<kUCM>, dim3(1), dim3(256), 0, st, a); break;
-            case kEUCM: hipLaunchKernelGGL(k_convert_gram<kEUCM>, dim3(1), dim3(256), 0, st, a); break;
-            case kKB4: hipLaunchKernelGGL(k_convert_gram<kKB4>, dim3(1), dim3(256), 0, st, a); break;
-            default: hipLaunchKernelGGL(k_convert_gram<kOCV5>, dim3(1), dim3(256), 0, st, a); break;
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(out, d_buf + 20, sizeof(double) * NA, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        return 0;
+    auto eval = [&](const double* t) -> int {                              // the sums at t, waited for: CCAL_OK or the block's failure
+        blk.upload(s_tgt, t, (size_t)P);
+        if (blk.ok()) { launch_model<LaunchGram>(tgt_model, 1, ctx->stream, a); blk.launched(); }
+        blk.download(out, a.out, (size_t)NA);
+        return blk.finish("ccal_convert_model");
     };
-    if (eval(th) != 0) return CCAL_ERR_HIP;
-    if (out[NT + P + 1] < 1.0) { ctx->err = "ccal_convert_model: the source model cannot unproject any grid point"; return CCAL_ERR_INVALID_ARG; }
+    if (eval(th) != CCAL_OK) return CCAL_ERR_HIP;
+    if (out[NT + P + 1] < 1.0) return fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_convert_model: the source model cannot unproject any grid point");
     double s = out[NT + P];
-    double cur = huber_w(s, 1.0) * s;
+    double cur = huber_weight(s, 1.0) * s;
     R.initial_cost = cur;
     int status = CCAL_OK;
     if (!std::isfinite(cur)) status = CCAL_ERR_NONFINITE;
     for (int it = 0; status == CCAL_OK && it < o.max_iterations; ++it) {
         const double last = cur;
-        const double w = huber_w(s, 1.0);                 // one block: the corrector is a common factor of H and g
+        const double w = huber_weight(s, 1.0);            // one block: the corrector is a common factor of H and g
         double S[81], dx[9];
         int e = 0;
         for (int i = 0; i < P; ++i) for (int j = 0; j <= i; ++j) { S[i * P + j] = S[j * P + i] = w * out[e]; ++e; }
         for (int i = 0; i < P; ++i) dx[i] = fx[i] ? 0.0 : -w * out[NT + i];
         for (int i = 0; i < P; ++i) if (fx[i]) { for (int j = 0; j < P; ++j) { S[i * P + j] = 0.0; S[j * P + i] = 0.0; } S[i * P + i] = 1.0; }
-        if (!chol_host(S, P)) { status = CCAL_ERR_NOT_PD; break; }
-        chol_solve_host(S, P, dx);
+        if (!chol_factor(S, P)) { status = CCAL_ERR_NOT_PD; break; }
+        chol_solve(S, P, dx);
         for (int i = 0; i < P; ++i) if (!fx[i]) th[i] = std::min(std::max(th[i] + dx[i], lo[i]), hi[i]);
-        if (eval(th) != 0) return CCAL_ERR_HIP;
+        if (eval(th) != CCAL_OK) return CCAL_ERR_HIP;
         s = out[NT + P];
-        cur = huber_w(s, 1.0) * s;
+        cur = huber_weight(s, 1.0) * s;
         R.iterations++;
         if (o.verbose) std::printf("[ccal convert_model] iter %d cost %.12g\n", it, cur);
-        const double le = o.error_metric ? std::sqrt(std::max(last, 0.0)) : last, ce = o.error_metric ? std::sqrt(std::max(cur, 0.0)) : cur;
-        if (ce < o.min_error) break;
-        if (std::isnan(cur)) { status = CCAL_ERR_NONFINITE; break; }
-        if (std::fabs(le - ce) < o.min_abs_error_decrease) break;
-        if (std::fabs(le - ce) / le < o.min_rel_error_decrease) break;
+        const GnNext next = gn_decide(last, cur, o.error_metric, o.min_error, o.min_abs_error_decrease, o.min_rel_error_decrease);
+        if (next == GnNext::nonfinite) status = CCAL_ERR_NONFINITE;
+        if (next != GnNext::go_on) break;
         if (it == o.max_iterations - 1) status = CCAL_ERR_NO_CONVERGENCE;
     }
     R.final_cost = cur; R.status = status;

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ccal_host_gn.hpp"
 #include "ccal_internal.hpp"
 
 namespace {
@@ -110,7 +111,7 @@ double cost(const std::vector<Iso>& a, const std::vector<Iso>& binv, const doubl
     for (size_t k = 0; k < a.size(); ++k) {
         double r[6]; se3_residual(a[k], binv[k], x, r);
         double s = 0; for (int i = 0; i < 6; ++i) s += r[i] * r[i];
-        c += (s <= delta * delta ? 1.0 : delta / std::sqrt(s)) * s;
+        c += ccal::huber_weight(s, delta) * s;
     }
     return c;
 }
@@ -152,33 +153,22 @@ extern "C" int ccal_init_camera_extrinsic_opts(const double* poses_cam0, const d
             double r[6], J[6][6];
             se3_residual_jac(a[k], binv[k], x, r, J);
             double s = 0; for (int i = 0; i < 6; ++i) s += r[i] * r[i];
-            const double w = s <= delta * delta ? 1.0 : delta / std::sqrt(s);
+            const double w = ccal::huber_weight(s, delta);
             for (int i = 0; i < 6; ++i) for (int c = 0; c < 6; ++c) {
                 g[c] += w * J[i][c] * r[i];
                 for (int e = 0; e < 6; ++e) H[c * 6 + e] += w * J[i][c] * J[i][e];
             }
         }
-        // Cholesky 6x6
-        double L[36]; std::memcpy(L, H, sizeof L);
-        bool ok = true;
-        for (int j = 0; j < 6 && ok; ++j) {
-            double s = L[j * 6 + j]; for (int q = 0; q < j; ++q) s -= L[j * 6 + q] * L[j * 6 + q];
-            if (!(s > 0)) { ok = false; break; }
-            const double l = std::sqrt(s); L[j * 6 + j] = l;
-            for (int i = j + 1; i < 6; ++i) { double t = L[i * 6 + j]; for (int q = 0; q < j; ++q) t -= L[i * 6 + q] * L[j * 6 + q]; L[i * 6 + j] = t / l; }
-        }
-        if (!ok) { status = CCAL_ERR_NOT_PD; break; }
+        if (!ccal::chol_factor(H, 6)) { status = CCAL_ERR_NOT_PD; break; }
         double dx[6];
-        for (int i = 0; i < 6; ++i) { double t = -g[i]; for (int q = 0; q < i; ++q) t -= L[i * 6 + q] * dx[q]; dx[i] = t / L[i * 6 + i]; }
-        for (int i = 5; i >= 0; --i) { double t = dx[i]; for (int q = i + 1; q < 6; ++q) t -= L[q * 6 + i] * dx[q]; dx[i] = t / L[i * 6 + i]; }
+        for (int i = 0; i < 6; ++i) dx[i] = -g[i];
+        ccal::chol_solve(H, 6, dx);
         for (int i = 0; i < 6; ++i) x[i] += dx[i];
         cur = cost(a, binv, x, delta);
         R.iterations++;
-        const double le = em ? std::sqrt(std::max(last, 0.0)) : last, ce = em ? std::sqrt(std::max(cur, 0.0)) : cur;
-        if (ce < min_err) break;
-        if (std::isnan(cur)) { status = CCAL_ERR_NONFINITE; break; }
-        if (std::fabs(le - ce) < min_abs) break;
-        if (std::fabs(le - ce) / le < min_rel) break;
+        const ccal::GnNext next = ccal::gn_decide(last, cur, em, min_err, min_abs, min_rel);
+        if (next == ccal::GnNext::nonfinite) status = CCAL_ERR_NONFINITE;
+        if (next != ccal::GnNext::go_on) break;
     }
     R.final_cost = cur; R.status = status;
     if (rep) *rep = R;

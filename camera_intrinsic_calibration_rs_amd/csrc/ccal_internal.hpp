@@ -67,7 +67,7 @@ struct ccal_ctx {
     // (created on first use, joined when the context is freed; ccal_solver.hip)
     struct ccal_ctx_worker* worker = nullptr;
     // ccal_solve_batch, session sizes: the argument blocks of a batch's problems, one launch per step for all of them
-    // (k_gram1v_batch reads the table on the device; h_: its pinned staging) - grown on demand, freed with the context
+    // (k_gram1v_batch reads the table on the device; h_: its pinned staging) - blocks of the context's allocator, grown on demand, released with the context
     char* d_batch_tab = nullptr; char* h_batch_tab = nullptr; size_t batch_tab_bytes = 0;
     // ccal_pin_buffer: the caller's ranges this context registered (unregistered by ccal_unpin_buffer or with the context)
     std::vector<std::pair<void*, size_t>> pinned;

@@ -319,7 +319,7 @@ void ccal_multi_problem_destroy(ccal_multi_problem* mp) {
         ccal_problem_destroy(p);
     }
     ccal_multi* m = mp->m;
-    if (mp->d_gather && m) { (void)hipSetDevice(m->ctx[0]->device); (void)hipFree(mp->d_gather); }
+    if (m) ctx_release(m->ctx[0], mp->d_gather, false);      // while the device set still holds its contexts (multi_free below)
     delete mp;
     if (m && --m->n_problems == 0 && m->destroy_requested) multi_free(m);
 }
@@ -509,12 +509,12 @@ int ccal_multi_validation(ccal_multi_problem* mp, int cam, const double* intr, c
     const size_t need = order_stats_block_bytes(total, c0->stream);
     if (need == 0) return mfail(m, CCAL_ERR_HIP, "ccal_multi_validation: sizing the selection's work area failed");
     if (mp->gather_bytes < need) {
-        if (mp->d_gather) { (void)hipFree(mp->d_gather); mp->d_gather = nullptr; mp->gather_bytes = 0; }
-        const size_t want = std::max(need, order_stats_block_bytes(std::max<int64_t>(mp->n_corners, 1), c0->stream));     // every camera of the problem fits
-        if (hipMalloc((void**)&mp->d_gather, want) != hipSuccess) { (void)hipGetLastError(); return mfail(m, CCAL_ERR_NO_MEMORY, "ccal_multi_validation: out of device memory"); }
-        mp->gather_bytes = want;
-        if (test_poison_f64(c0, mp->d_gather, (size_t)total * sizeof(double), false, c0->stream) != hipSuccess)      // (the values, not the work area)
-            return mfail(m, CCAL_ERR_HIP, "ccal_multi_validation: test hook failed");
+        ctx_release(c0, mp->d_gather, false);                // (the call that used it has waited for its statistics)
+        mp->d_gather = nullptr; mp->gather_bytes = 0;
+        // every camera of the problem fits; the plan's one slice of doubles - the values, not the work area - gets the test hook's NaN
+        const CallPlan pl = StatsScratch(0, std::max<int64_t>(std::max<int64_t>(mp->n_corners, 1), total)).plan;
+        if (ctx_block_alloc(c0, pl, &mp->d_gather, false) != hipSuccess) { (void)hipGetLastError(); return mfail(m, CCAL_ERR_NO_MEMORY, "ccal_multi_validation: out of device memory"); }
+        mp->gather_bytes = pl.total;
     }
     double* d_all = reinterpret_cast<double*>(mp->d_gather);
     int64_t at = 0;

@@ -68,7 +68,7 @@ void normal_ws_destroy(ccal_problem* p) {
         if (f->side) { (void)hipStreamSynchronize(f->side); ctx_stream_put(ctx, f->side); }      // (the result's download ran there)
         ctx_release(ctx, f->d_block, false);          // every device buffer of the workspace is a slice of it
         ctx_release(ctx, f->h_block, true);           // h_status | h_result | h_stage
-        if (f->fcbuf) (void)hipFree(f->fcbuf);
+        ctx_release(ctx, f->fcbuf, false);            // (NULL but in -DCCAL_STAMPS builds)
         delete f;
     }
     delete w;
@@ -105,7 +105,7 @@ static int fused_ws_ensure(ccal_problem* p) {
     f->RB1 = fused_red_size(p->K);
     f->n_pw = fused_partial_rows(p->n_obs);
     // ONE device allocation and ONE pinned allocation, sliced (a calibration session creates a problem and solves it once or
-    // twice: fifteen hipMalloc / hipHostMalloc calls and five memsets were 0.46 ms of the first solve's 0.58 at 600 frames)
+    // twice: fifteen device and pinned allocations and five memsets were 0.46 ms of the first solve's 0.58 at 600 frames)
     const FusedLayout l((size_t)p->n_slots, (size_t)p->n_obs, (size_t)w->PF, (size_t)f->PRAW, (size_t)f->RB1, (size_t)f->n_pw);
     HIP_TRY(ctx, ctx_block_alloc(ctx, l.dev, &f->d_block, false));
     HIP_TRY(ctx, ctx_block_alloc(ctx, l.host, &f->h_block, true));
@@ -116,7 +116,7 @@ static int fused_ws_ensure(ccal_problem* p) {
     f->h_status = h.at(l.h_status); f->h_result = h.at(l.h_result); f->h_stage = h.at(l.h_stage);
     // per-frame scratch of diagnostic builds (-DCCAL_STAMPS: in-kernel timestamps, tools/stamps_*.py); the product allocates nothing
 #ifdef CCAL_STAMPS
-    HIP_TRY(ctx, hipMalloc((void**)&f->fcbuf, std::max<size_t>((size_t)std::max(p->n_obs, 1) * 40, 32768) * sizeof(double)));
+    HIP_TRY(ctx, ctx_doubles(ctx, &f->fcbuf, std::max<size_t>((size_t)std::max(p->n_obs, 1) * 40, 32768)));
 #endif
     HIP_TRY(ctx, ctx_stream_get(ctx, &f->side));
     return CCAL_OK;
@@ -1149,11 +1149,10 @@ static void run_iter_group(const IterGroupKey& key, const std::vector<int>& memb
     // the table: grown on demand, kept by the group's first context
     const size_t bytes = (size_t)n * sizeof(FusedArgs);
     if (c0->batch_tab_bytes < bytes) {
-        if (c0->d_batch_tab) (void)hipFree(c0->d_batch_tab);
-        if (c0->h_batch_tab) (void)hipHostFree(c0->h_batch_tab);
+        ctx_release(c0, c0->d_batch_tab, false); ctx_release(c0, c0->h_batch_tab, true);      // (no launch of an earlier batch is left: each ends in a synchronise)
         c0->d_batch_tab = nullptr; c0->h_batch_tab = nullptr; c0->batch_tab_bytes = 0;
         const size_t want = std::max(bytes, (size_t)16 * sizeof(FusedArgs));
-        if (hipMalloc((void**)&c0->d_batch_tab, want) != hipSuccess || hipHostMalloc((void**)&c0->h_batch_tab, want, hipHostMallocDefault) != hipSuccess) {
+        if (ctx_dev_alloc(c0, (void**)&c0->d_batch_tab, want) != hipSuccess || ctx_host_alloc(c0, (void**)&c0->h_batch_tab, want) != hipSuccess) {
             (void)hipGetLastError(); fail_all(members, CCAL_ERR_NO_MEMORY, "ccal_solve_batch: out of memory for the batch table"); (void)hipStreamSynchronize(st); return;
         }
         c0->batch_tab_bytes = want;

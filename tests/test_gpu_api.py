@@ -1,9 +1,15 @@
 """GPU: the reference-shaped API (api.py) end to end through the C ABI -- these read like the
 reference's own tests (tests/optimization_test.rs) and its call sites (src/util.rs)."""
 import numpy as np
+import os
+import sys
+
 import pytest
 
-from camera_intrinsic_calibration_rs_amd import api, synth
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import small_factors as sf  # noqa: E402
+
+from camera_intrinsic_calibration_rs_amd import api, synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -216,6 +222,16 @@ def test_convert_model_vs_oracle(gpu_ctx, oracle, src, src_p, tgt, tgt_p, disabl
     np.testing.assert_allclose(out.params(), p_o, rtol=1e-8, atol=1e-10)
     if disabled:
         assert (np.asarray(out.params())[-disabled:] == 0.0).all()
+
+
+@pytest.mark.parametrize("case", sf.load()["convert"], ids=lambda c: c["name"])
+def test_convert_model_bits_of_the_record(gpu_ctx, case):
+    """ccal_convert_model against the record taken on the MI355X before the call moved onto the one-shot pattern and the host
+    Gauss-Newton kit (tests/golden/small_factors_parent.json): target parameters, final cost, iterations and status, bit for bit -
+    twice in a row on one context: the second call takes its block from the context's cache."""
+    from camera_intrinsic_calibration_rs_amd import _ffi
+    for _ in range(2):
+        assert sf.run_convert(_ffi.load(), gpu_ctx.handle, case) == case["expect"]
 
 
 def test_convert_model_roundtrip_identity(gpu_ctx):
