@@ -172,6 +172,11 @@ SYMBOLS = [
                                             _ip, _ip, _dp]),
     ("ccal_refine_corners_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_int, C.c_int, C.c_double,
                                           _ip, _ip, _dp]),
+    # from pixels to detections: checkerboard-corner candidates of whole images
+    ("ccal_detect_corners_batch", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                            _ip, _ip, _ip, _lp]),
+    ("ccal_detect_corners_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                          _ip, _ip, _ip, _lp]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

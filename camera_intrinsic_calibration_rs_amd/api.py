@@ -22,6 +22,8 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   remap                             (examples/test_pnp.rs:80)           remap (+ engine.UndistortMap for batches)
   the sub-pixel step that ends image_to_option_feature_frame
                                     (src/data_loader.rs:36-70)          refine_corners, redetect_corners (no tag detector here)
+  a detector for plain checkerboards (the reference's tag detector is in the absent aprilgrid crate)
+                                                                        detect_checkerboard, assemble_checkerboard
   (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
    not here yet - see README, "From detections alone")
 
@@ -776,6 +778,243 @@ def redetect_corners(images, model: GenericModel, rtvec_map: Dict[int, RvecTvec]
     p3ds = [[tuple(board_points[k]) for k in ids_k] for ids_k in ids]
     xy, status, _, lam = _ctx(ctx).refine_corners_batch(stack, [u[v] for u, v in zip(uv, valid)], half_win, max_iterations, eps)
     return _kept_frames(len(images), live, ids, p3ds, (W, H), [0] * len(live), xy, status, lam, min_lambda)
+
+
+def _edge_directions(hess: np.ndarray) -> np.ndarray:
+    """Per candidate the two unit zero-curvature directions of its Hessian [[hxx, hxy / 4], [hxy / 4, hyy]] - the two edges that
+    cross at a checkerboard corner: [k, 2, 2].  (hxy of the detector is four times the mixed derivative.)"""
+    h = np.asarray(hess, dtype=np.float64).reshape(-1, 3)
+    M = np.empty((len(h), 2, 2))
+    M[:, 0, 0], M[:, 1, 1], M[:, 0, 1], M[:, 1, 0] = h[:, 0], h[:, 1], h[:, 2] / 4.0, h[:, 2] / 4.0
+    lam, vec = np.linalg.eigh(M)                                    # lam[:, 0] <= lam[:, 1]
+    a, b = np.sqrt(np.maximum(lam[:, 1], 0.0))[:, None], np.sqrt(np.maximum(-lam[:, 0], 0.0))[:, None]
+    d = np.stack([b * vec[:, :, 1] + a * vec[:, :, 0], b * vec[:, :, 1] - a * vec[:, :, 0]], axis=1)
+    return d / np.maximum(np.linalg.norm(d, axis=2, keepdims=True), 1e-300)
+
+
+_CONE_COS = 0.9            # a neighbour lies within about 25 degrees of an edge direction, seen from both ends
+_WEAK = 0.5                # candidates below this fraction of the (cols * rows)-th strongest response are set aside
+
+
+def assemble_checkerboard(xy, hess, pattern: Tuple[int, int], square_size: float) -> Optional[Dict[int, Tuple[float, float]]]:
+    """Corner candidates of ONE image ordered into a complete checkerboard: xy [k, 2] (refined positions, f64) and hess [k, 3] =
+    (hxx, hyy, hxy) as the detector returns them; pattern = (cols, rows) inner corners.  Returns {id: (x, y)} with
+    id = r * cols + c for all cols * rows corners - the board point of id is (c * square_size, r * square_size, 0) - or None.
+
+    Method: candidates whose response hxy^2 - 16 hxx hyy is below half of the (cols * rows)-th strongest are set aside (the
+    L-corners of the outer squares: on the rendered boards of tests/detect_ref.py they respond at 0.18 .. 0.28 of the strongest
+    candidate, the inner corners at 0.64 .. 1).  Each corner's two edge directions are the zero-curvature directions of its
+    Hessian; along each of the four its neighbour is the nearest corner that lies in a cone around that direction, sees this
+    corner in one of its own cones and has the opposite saddle polarity (the Hessians' inner product is negative: black and white
+    swap from one corner to the next).  Every corner, the strongest first, seeds a lattice with a neighbour along each of its two
+    edges; the lattice grows cell by cell: a free cell is predicted from the cells around it (2 p1 - p2 along a row or column,
+    p1 + p2 - p3 across a square) and takes the nearest unused corner of the right polarity within 0.3 of the local spacing.  Then
+    every cell is predicted once more from the finished lattice and takes the corner nearest to that - which puts a true corner
+    back where a stray next to it had been picked.  The first lattice in which exactly one cols x rows (or rows x cols) window is
+    completely filled is the board; cells outside the window are left out.  A partial board therefore returns None: without tags
+    its offset in the pattern cannot be known.
+
+    Stray candidates.  Weak ones are set aside by strength.  Strong ones (tests: six per frame, anywhere in the image, with a true
+    corner's Hessian at 0.64 to 1.5 of its strength, over a range of seeds) do not change the result as long as each is farther
+    than 5 px in x or y from every other candidate - what the detector guarantees at its default nms_radius.  A stray closer to
+    a true corner than that can be taken in its place.  When no board is found every corner has been tried as a seed: about half
+    a second for 60 candidates.
+
+    Labelling: right-handed in the image (c towards r turns like +x towards +y).  That leaves two rotations of the board, four
+    when cols == rows; the one whose id 0 is smallest in (y, x) is chosen.  The choice is a valid pose of a symmetric point set, so
+    intrinsics are unaffected - but two cameras of a rig may choose differently for the same board, and a board that turns through
+    the symmetry between frames changes its labelling with it."""
+    cols, rows = int(pattern[0]), int(pattern[1])
+    if cols < 2 or rows < 2 or not float(square_size) > 0.0:
+        raise ValueError("assemble_checkerboard: pattern (cols, rows) >= 2 each, square_size > 0")
+    P = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    Hs = np.asarray(hess, dtype=np.float64).reshape(-1, 3)
+    if len(P) != len(Hs):
+        raise ValueError("assemble_checkerboard: one Hessian per position")
+    n_want = cols * rows
+    resp = Hs[:, 2] ** 2 - 16.0 * Hs[:, 0] * Hs[:, 1]
+    ok = np.isfinite(P).all(axis=1) & (resp > 0.0)
+    if np.count_nonzero(ok) < n_want:
+        return None
+    ok &= resp >= _WEAK * np.sort(resp[ok])[-n_want]
+    keep = np.flatnonzero(ok)
+    keep = keep[np.lexsort((P[keep, 0], P[keep, 1]))]               # a fixed order, whatever the caller's
+    P, Hs, resp = P[keep], Hs[keep], resp[keep]
+    n = len(P)
+    d2 = _edge_directions(Hs)
+    dirs = np.concatenate([d2, -d2], axis=1)                        # [n, 4, 2]: d1, d2, -d1, -d2
+    diff = P[None, :, :] - P[:, None, :]                            # diff[a, b] = b - a
+    dist = np.linalg.norm(diff, axis=2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        unit = diff / dist[:, :, None]
+    cosd = np.einsum("akc,abc->akb", dirs, np.nan_to_num(unit))     # [a, k, b]: b seen from a against a's direction k
+    in_cone = cosd > _CONE_COS
+    seen_back = in_cone.any(axis=1).T                               # [a, b]: a lies in one of b's cones
+    M = np.stack([Hs[:, 0], Hs[:, 1], Hs[:, 2] / 4.0], axis=1)
+    opposite = (M[:, 0:1] * M[None, :, 0] + M[:, 1:2] * M[None, :, 1] + 2.0 * M[:, 2:3] * M[None, :, 2]) < 0.0
+    cand = in_cone & (seen_back & opposite & (dist > 0.0))[:, None, :]
+    link = np.where(cand, dist[:, None, :], np.inf).argmin(axis=2)  # [a, k]
+    link = np.where(cand.any(axis=2), link, -1)
+    seen = np.zeros(n, dtype=bool)
+    for start in np.argsort(-resp, kind="stable"):                  # seeds in the order of their strength
+        if seen[start]:
+            continue
+        for kb, kc in ((0, 1), (0, 3), (2, 1), (2, 3)):             # a neighbour along each of the seed's two edges
+            b, c = int(link[start, kb]), int(link[start, kc])
+            if b < 0 or c < 0 or b == c:
+                continue
+            cell = _grow_lattice(P, opposite, int(start), b, c, cols + rows)
+            G = _full_window(cell, cols, rows)
+            if G is None:
+                continue
+            e_c, e_r = P[G[0, 1]] - P[G[0, 0]], P[G[1, 0]] - P[G[0, 0]]
+            if e_c[0] * e_r[1] - e_c[1] * e_r[0] < 0.0:             # left-handed: mirror c
+                G = G[:, ::-1]
+            best = None
+            for q in range(4):                                      # rotations keep the handedness
+                A = np.rot90(G, q)
+                if A.shape != (rows, cols):
+                    continue
+                key = (P[A[0, 0], 1], P[A[0, 0], 0])
+                if best is None or key < best[0]:
+                    best = (key, A)
+            A = best[1]
+            return {r * cols + c: (float(P[A[r, c], 0]), float(P[A[r, c], 1])) for r in range(rows) for c in range(cols)}
+        seen[start] = True
+    return None
+
+
+_REACH = 0.3               # a corner is taken for a lattice cell within this fraction of the local spacing of the cell's prediction
+_STEPS = ((1, 0), (0, 1), (-1, 0), (0, -1))
+
+
+def _predict_cell(cell: Dict[Tuple[int, int], int], P: np.ndarray, i: int, j: int):
+    """Where cell (i, j) should lie, from the other cells: 2 p1 - p2 along a row or column, p1 + p2 - p3 across a square, the mean
+    of all that apply, and the smallest spacing among them; None when no stencil applies."""
+    preds, spans = [], []
+    for di, dj in _STEPS:
+        p1, p2 = cell.get((i - di, j - dj)), cell.get((i - 2 * di, j - 2 * dj))
+        if p1 is not None and p2 is not None:
+            preds.append(2.0 * P[p1] - P[p2]); spans.append(np.linalg.norm(P[p1] - P[p2]))
+    for di in (1, -1):
+        for dj in (1, -1):
+            p1, p2, p3 = cell.get((i - di, j)), cell.get((i, j - dj)), cell.get((i - di, j - dj))
+            if p1 is not None and p2 is not None and p3 is not None:
+                preds.append(P[p1] + P[p2] - P[p3]); spans.append(min(np.linalg.norm(P[p1] - P[p3]), np.linalg.norm(P[p2] - P[p3])))
+    return (np.mean(preds, axis=0), min(spans)) if preds else None
+
+
+def _best_for_cell(cell, P, opposite, free, i, j) -> int:
+    """The corner for cell (i, j): the nearest to the cell's prediction among `free` within _REACH of the local spacing whose
+    polarity is opposite to that of every neighbouring cell; -1: none."""
+    pred = _predict_cell(cell, P, i, j)
+    if pred is None:
+        return -1
+    d = np.linalg.norm(P - pred[0], axis=1)
+    ok = (d <= _REACH * pred[1]) & free
+    for di, dj in _STEPS:
+        nb = cell.get((i + di, j + dj))
+        if nb is not None:
+            ok &= opposite[nb]
+    return int(np.argmin(np.where(ok, d, np.inf))) if ok.any() else -1
+
+
+def _grow_lattice(P: np.ndarray, opposite: np.ndarray, a: int, b: int, c: int, limit: int) -> Dict[Tuple[int, int], int]:
+    """The lattice grown from corner a at cell (0, 0) with b at (1, 0) and c at (0, 1): {cell: corner}.  A free cell next to the
+    lattice takes _best_for_cell among the unused corners; repeated until nothing is added, |i|, |j| <= limit.  Then every cell is
+    settled: predicted from the finished lattice around it, it takes the best corner among the unused ones and its own - which puts
+    the true corner back where the seed's nearest neighbour, or an early prediction, had picked a stray next to it."""
+    cell = {(0, 0): a, (1, 0): b, (0, 1): c}
+    used = np.zeros(len(P), dtype=bool)
+    used[[a, b, c]] = True
+    grown = True
+    while grown:
+        grown = False
+        for i, j in sorted({(i + di, j + dj) for i, j in cell for di, dj in _STEPS} - set(cell)):
+            if abs(i) > limit or abs(j) > limit:
+                continue
+            q = _best_for_cell(cell, P, opposite, ~used, i, j)
+            if q >= 0:
+                cell[(i, j)] = q
+                used[q] = True
+                grown = True
+    for _ in range(3):
+        moved = False
+        for i, j in sorted(cell):
+            own = cell.pop((i, j))
+            used[own] = False
+            q = _best_for_cell(cell, P, opposite, ~used, i, j)
+            q = own if q < 0 else q
+            cell[(i, j)] = q
+            used[q] = True
+            moved |= q != own
+        if not moved:
+            break
+    return cell
+
+
+def _full_window(cell: Dict[Tuple[int, int], int], cols: int, rows: int) -> Optional[np.ndarray]:
+    """The one cols x rows (or rows x cols) window of a grown lattice in which every cell holds a corner, as an array [j][i] of
+    corner indices; None when there is none or more than one."""
+    ij = np.array(sorted(cell)); idx = np.array([cell[tuple(c)] for c in ij])
+    ij -= ij.min(axis=0)
+    ni, nj = ij.max(axis=0) + 1
+    G = np.full((nj, ni), -1)
+    G[ij[:, 1], ij[:, 0]] = idx
+    found = []
+    for w, h in sorted({(cols, rows), (rows, cols)}):
+        for j0 in range(nj - h + 1):
+            for i0 in range(ni - w + 1):
+                if (G[j0:j0 + h, i0:i0 + w] >= 0).all():
+                    found.append(G[j0:j0 + h, i0:i0 + w])
+    return found[0] if len(found) == 1 else None
+
+
+def detect_checkerboard_points(images, pattern: Tuple[int, int], square_size: float, step: int = 1, nms_radius: int = 5,
+                               rel_threshold: float = 0.1, half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3,
+                               min_response: int = 1, max_per_image: int = 4096,
+                               ctx: Optional[Context] = None) -> List[Optional[Dict[int, Tuple[float, float]]]]:
+    """detect_checkerboard without the FrameFeature wrapping: per image {id: (x, y)} in f64, or None."""
+    if len(images) == 0:
+        return []
+    imgs = [np.asarray(im) for im in images]
+    if any(im.ndim != 2 or im.shape != imgs[0].shape or im.dtype != imgs[0].dtype for im in imgs):
+        raise ValueError("detect_checkerboard: single-channel images [H][W] of one size and type")
+    stack, _, _ = check_images(np.stack(imgs), True)
+    c = _ctx(ctx)
+    found = c.detect_corners_batch(stack, step, nms_radius, min_response, rel_threshold, max_per_image)
+    xy, status, _, _ = c.refine_corners_batch(stack, [f[0].astype(np.float64) for f in found], half_win, max_iterations, eps)
+    out: List[Optional[Dict[int, Tuple[float, float]]]] = []
+    for k, f in enumerate(found):
+        good = status[k] == _ffi.OK
+        out.append(assemble_checkerboard(xy[k][good], f[1][good], pattern, square_size))
+    return out
+
+
+def detect_checkerboard(images, pattern: Tuple[int, int], square_size: float, step: int = 1, nms_radius: int = 5,
+                        rel_threshold: float = 0.1, half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3,
+                        min_response: int = 1, max_per_image: int = 4096, ctx: Optional[Context] = None) -> List[Optional[FrameFeature]]:
+    """From images alone to detections of a plain checkerboard of pattern = (cols, rows) inner corners: the integer saddle detector
+    over all images in one call (ccal_detect_corners_batch), the sub-pixel refinement of its candidates (refine_corners' rule;
+    corners whose status is not CCAL_OK are dropped), then assemble_checkerboard per image.  images: grey [H][W] each, uint8 or
+    uint16, of one size.  Returns one entry per image: a FrameFeature with time_ns = the image's index, all cols * rows corners
+    (p2d stored as f32 like the reference's FeaturePoint, p3d = (c * square_size, r * square_size, 0) for id = r * cols + c), or
+    None where no complete board was found - partial boards are not returned.  The labelling's symmetry: assemble_checkerboard.
+    min_response scales with the square of the image contrast; as for refine_corners' min_lambda no useful value has been measured
+    here, and the default 1 screens only flat and edge-only neighbourhoods (rel_threshold does the work)."""
+    cols = int(pattern[0])
+    pts = detect_checkerboard_points(images, pattern, square_size, step, nms_radius, rel_threshold, half_win, max_iterations, eps,
+                                     min_response, max_per_image, ctx)
+    out: List[Optional[FrameFeature]] = []
+    for k, found in enumerate(pts):
+        if found is None:
+            out.append(None)
+            continue
+        H, W = np.asarray(images[k]).shape
+        sq = float(square_size)
+        out.append(FrameFeature(k, (W, H), {i: FeaturePoint((float(np.float32(x)), float(np.float32(y))),
+                                                            ((i % cols) * sq, (i // cols) * sq, 0.0)) for i, (x, y) in found.items()}))
+    return out
 
 
 class ReprojectionFactor:

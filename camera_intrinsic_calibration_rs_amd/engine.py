@@ -329,6 +329,54 @@ class Context:
         return self._corners(self.lib.ccal_refine_corners_dev, "ccal_refine_corners_dev", images_ptr, dtype, width, height, n_img,
                              xy_list, half_win, max_iterations, eps)
 
+    # -- from pixels to detections: checkerboard-corner candidates of whole images (ccal_detect_corners_batch, ccal_kernels_detect.hip) --
+    def _detect(self, fn, where, ptr, dtype, width, height, n_img, step, nms_radius, min_response, rel_threshold, max_per_image):
+        if not np.isfinite(rel_threshold):
+            raise ValueError(f"{where}: rel_threshold is not finite")
+        cap, m = int(max_per_image), max(int(n_img), 1)
+        # an image holds at most one candidate per (r + 1) x (r + 1) block of its domain: no room beyond that is needed
+        r1, d = max(int(nms_radius), 0) + 1, 2 * (int(step) + 2)
+        blocks = max(-(-(int(width) - d) // r1), 0) * max(-(-(int(height) - d) // r1), 0)
+        if cap >= 1:
+            cap = max(min(cap, blocks), 1)
+        rows = max(cap, 1)
+        count = np.zeros(m, dtype=np.int32)
+        xy = np.empty((m, rows, 2), dtype=np.int32); hess = np.empty((m, rows, 3), dtype=np.int32)
+        resp = np.empty((m, rows), dtype=np.int64)
+        rc = fn(self.handle, int(dtype), int(width), int(height), int(n_img), C.c_void_p(ptr), int(step), int(nms_radius),
+                int(min_response), int(round(1024.0 * float(rel_threshold))), cap, _ip(count), _ip(xy), _ip(hess), _lp(resp))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        # one compact copy of the stored rows of all images; the per-image results are views of it
+        kept = np.minimum(count[:int(n_img)], rows).astype(np.int64)
+        ends = np.cumsum(kept)
+        flat = np.arange(int(ends[-1]) if int(n_img) else 0) + np.repeat(np.arange(int(n_img)) * rows - (ends - kept), kept)
+        cxy, chess, cresp = xy.reshape(-1, 2).take(flat, axis=0), hess.reshape(-1, 3).take(flat, axis=0), resp.reshape(-1).take(flat)
+        lo, hi, cnt = (ends - kept).tolist(), ends.tolist(), count.tolist()
+        return [(cxy[a:b], chess[a:b], cresp[a:b], c) for a, b, c in zip(lo, hi, cnt)]
+
+    def detect_corners_batch(self, images, step: int = 1, nms_radius: int = 5, min_response: int = 1, rel_threshold: float = 0.1,
+                             max_per_image: int = 4096):
+        """Checkerboard-corner candidates (grey-level saddles) of every image of a batch, by the integer rule stated at
+        ccal_detect_corners_batch in include/ccal.h.  images: [n][H][W], uint8 or uint16.  rel_threshold is the fraction of the image's
+        largest response a candidate must reach (rel_q10 = round(1024 rel_threshold), 0 .. 1).  Returns one tuple per image:
+        (xy int32 [k, 2], hess int32 [k, 3] = (hxx, hyy, hxy), response int64 [k], count) in row-major order of (y, x), with
+        k = min(count, max_per_image).  min_response scales with the square of the image contrast; no useful value has been measured
+        (as for refine_corners_batch's lambda_min), the default 1 screens only flat and edge-only neighbourhoods."""
+        images, dtype, channels = check_images(images, True)
+        if channels != 1:
+            raise ValueError("detect_corners_batch: single-channel images [n][H][W]")
+        n_img, H, W = images.shape[:3]
+        return self._detect(self.lib.ccal_detect_corners_batch, "ccal_detect_corners_batch", images.ctypes.data, dtype, W, H, n_img,
+                            step, nms_radius, min_response, rel_threshold, max_per_image)
+
+    def detect_corners_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, step: int = 1, nms_radius: int = 5,
+                           min_response: int = 1, rel_threshold: float = 0.1, max_per_image: int = 4096):
+        """detect_corners_batch over an image block that is already on the device (a device pointer to [n_img][height][width] of
+        dtype _ffi.PIX_U8 / PIX_U16, its writes complete or enqueued on the context's stream); results are host arrays."""
+        return self._detect(self.lib.ccal_detect_corners_dev, "ccal_detect_corners_dev", images_ptr, dtype, width, height, n_img,
+                            step, nms_radius, min_response, rel_threshold, max_per_image)
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first

@@ -37,6 +37,9 @@
  *                            OtherCamReprojectionFactor + HuberLoss over T_0_b alone, intrinsics and extrinsics fixed, batched
  *   ccal_refine_corners_batch / _dev
  *                            the sub-pixel step at the end of image_to_option_feature_frame  src/data_loader.rs:36-70 (not the detector)
+ *   ccal_detect_corners_batch / _dev
+ *                            checkerboard-corner candidates of whole images (this project's integer saddle rule; the reference's
+ *                            tag detector is in the absent aprilgrid crate)
  *
  * Parameter layout.
  *   intr   [n_cams][CCAL_PMAX]  FULL model parameters [fx,fy,cx,cy,dist...] per camera, like
@@ -658,6 +661,53 @@ int ccal_refine_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int
                             const int64_t* offsets /* [n_img + 1] */, double* xy_io /* [.][2] */,
                             int half_win, int max_iterations, double eps,
                             int32_t* status_out, int32_t* iters_out /* or NULL */, double* lambda_min_out /* or NULL */);
+
+/* ---- from pixels to detections: checkerboard-corner candidates of whole images (saddle detector) ------------------------------
+ * The step in front of the refinement above: every image of a batch searched for grey-level saddles (the inner corners of a
+ * checkerboard), in INTEGER arithmetic throughout - the outputs are decisions, and tests/detect_ref.py, the numpy int64
+ * yardstick, is met bit for bit.  The rule is this project's (the determinant-of-Hessian saddle response the checkerboard
+ * detectors of OpenCV and Kalibr also start from); tags are not decoded here.
+ *
+ * Images: as above - n_img single-channel images of one size, [n_img][height][width] of CCAL_PIX_U8 or CCAL_PIX_U16, a pixel's
+ * centre at integer coordinates, I(x, y) the pixel value.  Parameters: step s in 1 .. 4, nms_radius r in 1 .. 15,
+ * min_response >= 1, rel_q10 in 0 .. 1024, cap >= 1.
+ *   smooth      S(x, y) = sum over i, j in -2 .. 2 of b(i) b(j) I(x + i, y + j), b = [1, 4, 6, 4, 1]: an integer, no division;
+ *               S <= 256 * 65535 < 2^24.
+ *   Hessian     hxx = S(x+s, y) - 2 S(x, y) + S(x-s, y), hyy = S(x, y+s) - 2 S(x, y) + S(x, y-s),
+ *               hxy = S(x+s, y+s) - S(x+s, y-s) - S(x-s, y+s) + S(x-s, y-s): int32, |hxx|, |hyy|, |hxy| <= 2 * 2^24 = 2^25.
+ *   response    R = hxy^2 - 16 hxx hyy in int64: -16 s^4 det H of a quadratic, positive at a saddle, and the same for the
+ *               saddles xy and (x^2 - y^2) / 2 (a rotation by 45 degrees).  |R| <= 2^50 + 16 * 2^50 < 2^55: it cannot overflow.
+ *   domain      the pixels with s + 2 <= x <= width - 1 - (s + 2) and s + 2 <= y <= height - 1 - (s + 2) - every pixel R reads
+ *               lies in the image.  An image too small to have one is valid and yields nothing.
+ *   local max   p in the domain with R(p) >= min_response such that for every domain pixel q != p with |q.x - p.x| <= r and
+ *               |q.y - p.y| <= r: R(p) > R(q) if q precedes p in row-major order (q.y < p.y, or q.y == p.y and q.x < p.x),
+ *               R(p) >= R(q) otherwise.  Pixels outside the domain do not compete.  (Of equal neighbours the first in row-major
+ *               order wins, so two local maxima are never within r of each other in both coordinates.)
+ *   threshold   Rmax = the largest R over the image's domain.  With Rmax > 0: T = max(min_response, (Rmax >> 10) * rel_q10); a
+ *               candidate is a local maximum with R >= T.  With Rmax <= 0 there is no local maximum and no candidate.
+ * Outputs per image k, the candidates in row-major order of (y, x): count_out[k] = their number - it may exceed cap, then the
+ * first cap in that order are stored -, xy_out [n_img][cap][2] = (x, y), hess_out [n_img][cap][3] = (hxx, hyy, hxy),
+ * response_out [n_img][cap] = R (NULL: not wanted).  Rows past min(count, cap) are not written.
+ * min_response scales with the square of the image contrast (R is quadratic in the grey levels), like lambda_min above; no
+ * useful value has been measured.  1 screens flat neighbourhoods and axis-parallel edges (R = 0 exactly there); an oblique
+ * straight edge leaves a positive residue of the differences, which rel_q10 has to cut.
+ * An image's outputs are a pure function of that image and (step, nms_radius, min_response, rel_q10, cap): they do not depend
+ * on its place in the batch, on what else is in it or on how the library cuts the batch into chunks, and they are bit-identical
+ * from run to run (integers only, Rmax by an integer max, a candidate's place fixed by its position: no arrival order anywhere).
+ * ccal_detect_corners_batch: host pointers.  ccal_detect_corners_dev: `images_dev` is a device pointer (the output of
+ * ccal_remap_dev on this context's stream, or a block whose writes are complete); the outputs stay host arrays.  Both return
+ * when the outputs are written.
+ * CCAL_ERR_INVALID_ARG, nothing launched or written: step outside 1 .. 4, nms_radius outside 1 .. 15, min_response < 1, rel_q10
+ * outside 0 .. 1024, cap < 1, a dtype other than the two, width, height <= 0 or n_img < 0, more than 2^31 - 1 pixels in an image,
+ * a NULL required pointer (with n_img > 0: images, count_out, xy_out, hess_out).  n_img == 0 is valid. */
+int ccal_detect_corners_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images,
+                              int step, int nms_radius, int64_t min_response, int rel_q10, int cap,
+                              int32_t* count_out /* [n_img] */, int32_t* xy_out /* [n_img][cap][2] */,
+                              int32_t* hess_out /* [n_img][cap][3] */, int64_t* response_out /* [n_img][cap] or NULL */);
+int ccal_detect_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev,
+                            int step, int nms_radius, int64_t min_response, int rel_q10, int cap,
+                            int32_t* count_out /* [n_img] */, int32_t* xy_out /* [n_img][cap][2] */,
+                            int32_t* hess_out /* [n_img][cap][3] */, int64_t* response_out /* [n_img][cap] or NULL */);
 
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,

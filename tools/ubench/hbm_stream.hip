@@ -10,9 +10,12 @@
 // Sizes: 276 MB (EUCM J block of 10 000 x 144 corners), 467 MB (18-column block), and two 346-MB buffers alternating (the
 // two-camera rig's 691 MB of outputs - beyond the 256-MiB Infinity Cache).
 //   hipcc -O3 --offload-arch=gfx950 -o hbm_stream.bin hbm_stream.hip && ./hbm_stream.bin
+// With byte counts as arguments (./hbm_stream.bin 216576000 134217728) it only reads buffers of those sizes once per launch and
+// prints "read-once <bytes> <us>" for each: the byte-mover time other tools price a one-pass kernel against (tools/time_detect.py).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 #include <algorithm>
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
@@ -87,11 +90,24 @@ struct Timer {
     }
 };
 
-int main() {
+int main(int argc, char** argv) {
     hipStream_t s; CHECK(hipStreamCreate(&s));
     Timer T; T.s = s; CHECK(hipEventCreate(&T.e0)); CHECK(hipEventCreate(&T.e1));
     const size_t cap = 480ull << 20;
     double *A, *B, *sink; float* F;
+    if (argc > 1) {                                   // read-once times of the given sizes only
+        CHECK(hipMalloc(&A, cap)); CHECK(hipMalloc(&sink, 64)); CHECK(hipMemsetAsync(A, 0, cap, s));
+        for (int i = 0; i < 200; ++i) hipLaunchKernelGGL((k_read<false>), dim3(16875), dim3(256), 0, s, A, (size_t)16875, sink);
+        CHECK(hipStreamSynchronize(s));
+        for (int a = 1; a < argc; ++a) {
+            const size_t bytes = std::min<size_t>(strtoull(argv[a], nullptr, 10), cap), nt = bytes / 16384;
+            if (!nt) continue;
+            const double t = T.run([&](int) { hipLaunchKernelGGL((k_read<false>), dim3((unsigned)nt), dim3(256), 0, s, A, nt, sink); });
+            printf("read-once %zu %.2f\n", nt * 16384, t * 1e6);
+        }
+        CHECK(hipStreamSynchronize(s));
+        return 0;
+    }
     CHECK(hipMalloc(&A, cap)); CHECK(hipMalloc(&B, cap)); CHECK(hipMalloc(&sink, 64)); CHECK(hipMalloc(&F, 128ull << 20));
     CHECK(hipMemsetAsync(A, 0, cap, s)); CHECK(hipMemsetAsync(B, 0, cap, s)); CHECK(hipMemsetAsync(F, 0, 128ull << 20, s));
     // clock ramp
