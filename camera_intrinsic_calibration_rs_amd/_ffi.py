@@ -18,12 +18,14 @@ METHOD_GN, METHOD_LM = 0, 1
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1, 2
 MULTI_MAX_DEVICES = 16
 PIX_U8, PIX_U16 = 0, 1                          # ccal_pixel_type
+TAG_OK, TAG_OUTSIDE, TAG_LOW_CONTRAST, TAG_BORDER, TAG_NO_CODE = range(5)        # ccal_tag_reason
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
 _bp = C.POINTER(C.c_uint8)
+_up = C.POINTER(C.c_uint64)
 
 
 class ProblemDesc(C.Structure):
@@ -177,6 +179,11 @@ SYMBOLS = [
                                             _ip, _ip, _ip, _lp]),
     ("ccal_detect_corners_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int,
                                           _ip, _ip, _ip, _lp]),
+    # from pixels to detections: decoding tags in candidate quads
+    ("ccal_decode_tags_batch", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_int, C.c_int, _up, C.c_int, C.c_int,
+                                         C.c_double, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp, _up, _dp]),
+    ("ccal_decode_tags_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_int, C.c_int, _up, C.c_int, C.c_int,
+                                       C.c_double, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp, _up, _dp]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

@@ -22,6 +22,10 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   remap                             (examples/test_pnp.rs:80)           remap (+ engine.UndistortMap for batches)
   the sub-pixel step that ends image_to_option_feature_frame
                                     (src/data_loader.rs:36-70)          refine_corners, redetect_corners (no tag detector here)
+  board::BoardConfig / Board::init_aprilgrid (src/board.rs:7-95)        AprilGridBoard
+  image_to_option_feature_frame's corner naming id = tag_id * 4 + i     frames_from_tags
+  what tag_detector.detect decides for a quad (the absent aprilgrid crate; this project's rule, the family supplied by the
+  caller, quads not proposed here)                                      decode_tags, TagFamily
   a detector for plain checkerboards (the reference's tag detector is in the absent aprilgrid crate)
                                                                         detect_checkerboard, assemble_checkerboard
   (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
@@ -1014,6 +1018,123 @@ def detect_checkerboard(images, pattern: Tuple[int, int], square_size: float, st
         sq = float(square_size)
         out.append(FrameFeature(k, (W, H), {i: FeaturePoint((float(np.float32(x)), float(np.float32(y))),
                                                             ((i % cols) * sq, (i // cols) * sq, 0.0)) for i, (x, y) in found.items()}))
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class TagFamily:
+    """A tag family as data: bits = d * d data cells per tag (d in 3 .. 8) and the table of codes, code m being the tag of id m.
+    A code is the d x d bit image in row-major order from the top-left cell, the first cell in the highest bit (the rule at
+    ccal_decode_tags_batch in include/ccal.h).  NO family table ships with this project: the caller supplies the table of the
+    family the board was printed from (tag36h11 for the usual AprilGrid: bits = 36, 587 codes), taken from the library that
+    printed it.  JSON form: {"name": ..., "bits": ..., "codes": [...]}."""
+    name: str
+    bits: int
+    codes: Tuple[int, ...]
+
+    def __post_init__(self):
+        bits = int(self.bits)
+        if bits not in (9, 16, 25, 36, 49, 64):
+            raise ValueError("TagFamily: bits is the square of 3 .. 8")
+        codes = tuple(int(c) for c in self.codes)
+        if not codes or any(not 0 <= c < (1 << bits) for c in codes):
+            raise ValueError("TagFamily: at least one code, each 0 <= code < 2^bits")
+        object.__setattr__(self, "bits", bits)
+        object.__setattr__(self, "codes", codes)
+
+    @property
+    def d(self) -> int:
+        return int(round(self.bits ** 0.5))
+
+    @staticmethod
+    def from_json_obj(obj) -> "TagFamily":
+        return TagFamily(str(obj["name"]), int(obj["bits"]), tuple(int(c) for c in obj["codes"]))
+
+    def to_json_obj(self):
+        return {"name": self.name, "bits": self.bits, "codes": list(self.codes)}
+
+
+class AprilGridBoard:
+    """board::Board::init_aprilgrid (src/board.rs:46-95) with BoardConfig's fields and defaults (src/board.rs:7-25): id_to_3d maps
+    corner id = tag_id * 4 + i to the corner's board point, in the reference's f32 arithmetic and order of operations.  Tag
+    (r, c) starts at x = c * size * (1 + spacing), y = -r * size * (1 + spacing); its corners i = 0 .. 3 are (x, y), (x + s, y),
+    (x + s, y - s), (x, y - s); ids count from first_id * 4, row by row."""
+
+    def __init__(self, tag_size_meter: float = 0.088, tag_spacing: float = 0.3, tag_rows: int = 6, tag_cols: int = 6, first_id: int = 0):
+        self.tag_size_meter, self.tag_spacing = float(tag_size_meter), float(tag_spacing)
+        self.tag_rows, self.tag_cols, self.first_id = int(tag_rows), int(tag_cols), int(first_id)
+        if self.tag_rows < 0 or self.tag_cols < 0 or self.first_id < 0:
+            raise ValueError("AprilGridBoard: tag_rows, tag_cols and first_id are not negative")
+        f32 = np.float32
+        size, pitch = f32(self.tag_size_meter), f32(1.0) + f32(self.tag_spacing)
+        self.id_to_3d: Dict[int, Tuple[float, float, float]] = {}
+        count_id = self.first_id * 4
+        for r in range(self.tag_rows):
+            for c in range(self.tag_cols):
+                start_x = f32(c) * size * pitch
+                start_y = -f32(r) * size * pitch
+                for i, (x, y) in enumerate(((start_x, start_y), (start_x + size, start_y), (start_x + size, start_y - size),
+                                            (start_x, start_y - size))):
+                    self.id_to_3d[count_id + i] = (float(x), float(y), 0.0)
+                count_id += 4
+
+    @staticmethod
+    def from_json_obj(obj) -> "AprilGridBoard":
+        """From the reference's BoardConfig as serde writes it: tag_size_meter, tag_spacing, tag_rows, tag_cols, first_id."""
+        return AprilGridBoard(obj["tag_size_meter"], obj["tag_spacing"], obj["tag_rows"], obj["tag_cols"], obj["first_id"])
+
+
+def decode_tags(images, quads_list, family: TagFamily, border: int = 1, samples: int = 3, min_contrast: float = 20.0,
+                max_border_errors: int = 0, max_hamming: int = 2, ctx: Optional[Context] = None
+                ) -> List[List[Tuple[int, int, int, np.ndarray]]]:
+    """Candidate quads decoded against a tag family (ccal_decode_tags_batch: one wavefront per quad, all images in one call).
+    images: one grey image [H][W] per entry (uint8 or uint16, all of one size); quads_list: per image an array [n_i, 4, 2] of quads,
+    each in order around the tag's outer border edge, starting anywhere.  Returns per image the list of (tag_id, rot, hamming,
+    corners [4, 2]) of the quads that decode (CCAL_TAG_OK), ascending in tag_id; corners are in the tag's canonical order (top-left,
+    top-right, bottom-right, bottom-left of the code image), whatever corner the quad started at.  When two quads of one image
+    decode to the same id the one with the smaller (hamming, -margin) is kept.  Proposing the quads is not part of this call."""
+    if len(images) != len(quads_list):
+        raise ValueError("decode_tags: one array of quads per image")
+    if not len(images):
+        return []
+    imgs = [np.asarray(im) for im in images]
+    if any(im.ndim != 2 or im.shape != imgs[0].shape or im.dtype != imgs[0].dtype for im in imgs):
+        raise ValueError("decode_tags: single-channel images [H][W] of one size and type")
+    reason, tag_id, rot, ham, corners, _, margin = _ctx(ctx).decode_tags_batch(
+        np.stack(imgs), [np.asarray(q, dtype=np.float64).reshape(-1, 4, 2) for q in quads_list], family.bits, family.codes, border,
+        samples, min_contrast, max_border_errors, max_hamming)
+    out = []
+    for k in range(len(imgs)):
+        best: Dict[int, int] = {}
+        for j in np.flatnonzero(reason[k] == _ffi.TAG_OK):
+            t = int(tag_id[k][j])
+            if t not in best or (ham[k][j], -margin[k][j]) < (ham[k][best[t]], -margin[k][best[t]]):
+                best[t] = int(j)
+        out.append([(t, int(rot[k][j]), int(ham[k][j]), corners[k][j].copy()) for t, j in sorted(best.items())])
+    return out
+
+
+def frames_from_tags(decoded, board: AprilGridBoard, img_w_h: Tuple[int, int], times: Optional[Sequence[int]] = None,
+                     min_corners: int = 24) -> List[Optional[FrameFeature]]:
+    """image_to_option_feature_frame (src/data_loader.rs:36-70) over decode_tags' output: corner i of tag tag_id gets
+    id = tag_id * 4 + i and the board's point of that id; ids the board does not hold are dropped; a frame with fewer than
+    min_corners corners (the reference's MIN_CORNERS = 24) is None.  p2d is stored as the f32 the reference's FeaturePoint holds.
+    times: time_ns per frame (default: the frame's index)."""
+    if times is not None and len(times) != len(decoded):
+        raise ValueError("frames_from_tags: one time per frame")
+    out: List[Optional[FrameFeature]] = []
+    for k, tags in enumerate(decoded):
+        feats: Dict[int, FeaturePoint] = {}
+        for tag in tags:
+            tag_id, corners = int(tag[0]), np.asarray(tag[3], dtype=np.float64).reshape(4, 2)
+            for i in range(4):
+                p3d = board.id_to_3d.get(tag_id * 4 + i)
+                if p3d is not None:
+                    feats[tag_id * 4 + i] = FeaturePoint((float(np.float32(corners[i, 0])), float(np.float32(corners[i, 1]))), p3d)
+        if len(feats) < int(min_corners):
+            out.append(None)
+        else:
+            out.append(FrameFeature(int(times[k]) if times is not None else k, (int(img_w_h[0]), int(img_w_h[1])), feats))
     return out
 
 

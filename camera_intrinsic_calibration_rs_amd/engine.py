@@ -377,6 +377,54 @@ class Context:
         return self._detect(self.lib.ccal_detect_corners_dev, "ccal_detect_corners_dev", images_ptr, dtype, width, height, n_img,
                             step, nms_radius, min_response, rel_threshold, max_per_image)
 
+    # -- from pixels to detections: decoding tags in candidate quads (ccal_decode_tags_batch, ccal_kernels_tags.hip) ------------------
+    def _tags(self, fn, where, ptr, dtype, width, height, n_img, quads_list, family_bits, codes, border, samples, min_contrast,
+              max_border_errors, max_hamming):
+        if len(quads_list) != n_img:
+            raise ValueError(f"{where}: one array of quads per image")
+        d = int(round(max(float(family_bits), 0.0) ** 0.5))
+        if d * d != int(family_bits):
+            raise ValueError(f"{where}: family_bits is not a square")
+        codes = np.ascontiguousarray(np.asarray([int(c) for c in codes], dtype=np.uint64))
+        offs, quads = _pack(quads_list, 8)
+        n = int(offs[-1])
+        m = max(n, 1)
+        reason = np.full(m, -2, dtype=np.int32); tag_id = np.full(m, -2, dtype=np.int32)
+        rot = np.full(m, -2, dtype=np.int32); hamming = np.full(m, -2, dtype=np.int32)
+        corners = np.full((m, 4, 2), np.nan); margin = np.full(m, np.nan)
+        code = np.zeros(m, dtype=np.uint64)
+        up = C.POINTER(C.c_uint64)
+        rc = fn(self.handle, int(dtype), int(width), int(height), int(n_img), C.c_void_p(ptr), _lp(offs), _dp(quads), d, int(border),
+                codes.ctypes.data_as(up), len(codes), int(samples), float(min_contrast), int(max_border_errors), int(max_hamming),
+                _ip(reason), _ip(tag_id), _ip(rot), _ip(hamming), _dp(corners), code.ctypes.data_as(up), _dp(margin))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        cut = [(int(offs[k]), int(offs[k + 1])) for k in range(n_img)]
+        return tuple([arr[a:b] for a, b in cut] for arr in (reason, tag_id, rot, hamming, corners, code, margin))
+
+    def decode_tags_batch(self, images, quads_list, family_bits: int, codes, border: int = 1, samples: int = 3,
+                          min_contrast: float = 20.0, max_border_errors: int = 0, max_hamming: int = 2):
+        """Every candidate quad of a batch of grey images decoded against a tag family, all in one launch, by the rule stated at
+        ccal_decode_tags_batch in include/ccal.h.  images: [n][H][W], uint8 or uint16; quads_list: one array [n_i, 4, 2] of (x, y)
+        corners per image, each quad in order around the tag's outer border edge; family_bits = d * d with d in 3 .. 8 and codes the
+        family's table (integers < 2^family_bits), which the caller supplies.  min_contrast is in grey levels of the images' type.
+        Returns (reason, id, rot, hamming, corners, code, margin), each a list with one array per image: reason [n_i] int32
+        (_ffi.TAG_OK, TAG_OUTSIDE, TAG_LOW_CONTRAST, TAG_BORDER, TAG_NO_CODE), id / rot / hamming [n_i] int32 (-1 unless TAG_OK),
+        corners [n_i, 4, 2] in the tag's canonical order (NaN unless TAG_OK), code [n_i] uint64 as read, margin [n_i]."""
+        images, dtype, channels = check_images(images, True)
+        if channels != 1:
+            raise ValueError("decode_tags_batch: single-channel images [n][H][W]")
+        n_img, H, W = images.shape[:3]
+        return self._tags(self.lib.ccal_decode_tags_batch, "ccal_decode_tags_batch", images.ctypes.data, dtype, W, H, n_img, quads_list,
+                          family_bits, codes, border, samples, min_contrast, max_border_errors, max_hamming)
+
+    def decode_tags_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, quads_list, family_bits: int, codes,
+                        border: int = 1, samples: int = 3, min_contrast: float = 20.0, max_border_errors: int = 0, max_hamming: int = 2):
+        """decode_tags_batch over an image block that is already on the device (a device pointer to [n_img][height][width] of
+        dtype _ffi.PIX_U8 / PIX_U16, its writes complete or enqueued on the context's stream); quads, codes and results are host arrays."""
+        return self._tags(self.lib.ccal_decode_tags_dev, "ccal_decode_tags_dev", images_ptr, dtype, width, height, n_img, quads_list,
+                          family_bits, codes, border, samples, min_contrast, max_border_errors, max_hamming)
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first

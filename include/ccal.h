@@ -40,6 +40,9 @@
  *   ccal_detect_corners_batch / _dev
  *                            checkerboard-corner candidates of whole images (this project's integer saddle rule; the reference's
  *                            tag detector is in the absent aprilgrid crate)
+ *   ccal_decode_tags_batch / _dev
+ *                            which tag a candidate quad holds, its turn and its bit errors, against a caller-supplied family
+ *                            (this project's rule; what tag_detector.detect decides inside the absent aprilgrid crate)
  *
  * Parameter layout.
  *   intr   [n_cams][CCAL_PMAX]  FULL model parameters [fx,fy,cx,cy,dist...] per camera, like
@@ -708,6 +711,74 @@ int ccal_detect_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int
                             int step, int nms_radius, int64_t min_response, int rel_q10, int cap,
                             int32_t* count_out /* [n_img] */, int32_t* xy_out /* [n_img][cap][2] */,
                             int32_t* hess_out /* [n_img][cap][3] */, int64_t* response_out /* [n_img][cap] or NULL */);
+
+/* ---- from pixels to detections: decoding tags in candidate quads (batched quad sampling and code match) -----------------------
+ * What the reference's front end does before it names corners (image_to_option_feature_frame, src/data_loader.rs:36-70: corner
+ * id = tag_id * 4 + i, looked up in Board::init_aprilgrid, src/board.rs:46-95): given an image and a candidate quad, decide which
+ * tag of a family this is, how it is turned and by how many bits it misses.  Quads are NOT proposed here.  The rule is this
+ * project's; the reference's decoder lives in the absent aprilgrid crate, so parity with it is NOT pinned.  A family is data - a
+ * bit count and a list of codes - and the caller supplies it (from the library that printed the board); none is built in.
+ * tests/tag_ref.py is the rule's numpy f64 yardstick; the library evaluates the rule without fused multiply-adds, each product
+ * and sum rounded on its own.
+ *
+ * Images: as for ccal_refine_corners_* - [n_img][height][width] of CCAL_PIX_U8 / CCAL_PIX_U16, a pixel's centre at integer
+ * coordinates, I(x, y) that section's bilinear f64 sample written in differences.  Image k owns the quads
+ * [offsets[k], offsets[k + 1]) of quads [.][4][2] = (x, y); a quad's corners q0 .. q3 go around the tag's OUTER border edge in
+ * order.  Family: d in 3 .. 8 data cells per side, n_codes >= 1 codes, each < 2^(d d).  Parameters: border in 1 .. 2 (black cells
+ * around the data), samples S in 1 .. 4, min_contrast >= 0 and finite, max_border_errors >= 0, max_hamming in 0 .. d d.
+ * n = d + 2 border (at most 12) cells per side.
+ *   1 map        the unit square onto the quad, (0,0) -> q0, (1,0) -> q1, (1,1) -> q2, (0,1) -> q3, q_i = (x_i, y_i):
+ *                S_ = q0 - q1 + q2 - q3, D1 = q1 - q2, D2 = q3 - q2, den = D1.x D2.y - D2.x D1.y,
+ *                g = (S_.x D2.y - D2.x S_.y) / den, h = (D1.x S_.y - S_.x D1.y) / den,
+ *                a = x1 - x0 + g x1, b = x3 - x0 + h x3, c = x0, d_ = y1 - y0 + g y1, e = y3 - y0 + h y3, f = y0,
+ *                w = g u + h v + 1, x = (a u + b v + c) / w, y = (d_ u + e v + f) / w.
+ *   2 cells      cell (row j, col i), i, j in 0 .. n - 1, has S S sample points at u = (i + (2p + 1) / (2S)) / n,
+ *                v = (j + (2q + 1) / (2S)) / n; its value is the mean of I over them (summed q outer, p inner, divided by S S).
+ *   3 inside     every sample point has w finite and > 0, 0 <= x <= width - 1 and 0 <= y <= height - 1 (false for NaN); else
+ *                CCAL_TAG_OUTSIDE.  This also catches den == 0, corners that are not finite and crossed quads.
+ *   4 threshold  lo, hi = the smallest and largest cell value over all n n cells.  !(hi - lo >= min_contrast):
+ *                CCAL_TAG_LOW_CONTRAST.  t = lo + (hi - lo) / 2; a cell is white (1) iff its value > t;
+ *                margin = min over the cells of |value - t|.
+ *   5 border     the white cells among the n n - d d border cells; more than max_border_errors: CCAL_TAG_BORDER.
+ *   6 code       data cell (r, c) = cell (border + r, border + c): code = sum bit(r, c) << (d d - 1 - (r d + c)) - row-major from
+ *                q0's corner, the first cell in the highest bit.
+ *   7 turns      T(B)(r, c) = B(d - 1 - c, r) is one quarter turn clockwise; code_k is the code of T^k(B), k = 0 .. 3.
+ *   8 match      over all (m, k) the smallest key (popcount(code_k ^ codes[m]), m, k) in lexicographic order.  Its distance
+ *                above max_hamming: CCAL_TAG_NO_CODE.  Else CCAL_TAG_OK with id = m, rot = k, hamming.
+ *   9 corners    canonical corner i is the outer corner of the printed tag at the code image's top-left, top-right,
+ *                bottom-right, bottom-left for i = 0 .. 3: corners_out[i] = q[(i + 3 rot) mod 4].
+ * Outputs per quad: reason_out; id_out, rot_out, hamming_out (-1 unless CCAL_TAG_OK); corners_out [.][4][2] (NaN unless
+ * CCAL_TAG_OK; NULL: not wanted); code_out = code_0 (written for every reason past CCAL_TAG_LOW_CONTRAST, 0 otherwise; NULL: not
+ * wanted); margin_out (NaN for CCAL_TAG_OUTSIDE; NULL: not wanted).
+ * A quad's outputs are a pure function of its image, its corners, the family and the parameters: they do not depend on its place
+ * in the batch, on what else is in it or on how the library cuts the batch into chunks, and they are bit-identical from run to
+ * run (a fixed lane-to-cell mapping, lo / hi / margin by exact min / max, the match by the minimum of an integer key, no atomics).
+ * ccal_decode_tags_batch: host pointers.  ccal_decode_tags_dev: `images_dev` is a device pointer (the output of ccal_remap_dev
+ * on this context's stream, or a block whose writes are complete); everything else stays a host array.  Both return when the
+ * outputs are written.
+ * CCAL_ERR_INVALID_ARG, nothing launched or written: a parameter outside the ranges above, a code >= 2^(d d) (d d < 64 only), a
+ * dtype other than the two, width, height <= 0 or n_img < 0, more than 2^31 - 1 pixels in an image or quads in the call, offsets
+ * that do not start at 0 or decrease, a NULL required pointer (with n_img > 0: images, offsets, codes, reason_out, id_out,
+ * rot_out, hamming_out; quads when there are quads).  n_img == 0 and an image without quads are valid. */
+typedef enum {
+    CCAL_TAG_OK = 0,
+    CCAL_TAG_OUTSIDE = 1,
+    CCAL_TAG_LOW_CONTRAST = 2,
+    CCAL_TAG_BORDER = 3,
+    CCAL_TAG_NO_CODE = 4
+} ccal_tag_reason;
+int ccal_decode_tags_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images,
+                           const int64_t* offsets /* [n_img + 1] */, const double* quads /* [.][4][2] */, int d, int border,
+                           const uint64_t* codes /* [n_codes] */, int n_codes, int samples, double min_contrast,
+                           int max_border_errors, int max_hamming,
+                           int32_t* reason_out, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out,
+                           double* corners_out /* [.][4][2] or NULL */, uint64_t* code_out /* or NULL */, double* margin_out /* or NULL */);
+int ccal_decode_tags_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev,
+                         const int64_t* offsets /* [n_img + 1] */, const double* quads /* [.][4][2] */, int d, int border,
+                         const uint64_t* codes /* [n_codes] */, int n_codes, int samples, double min_contrast,
+                         int max_border_errors, int max_hamming,
+                         int32_t* reason_out, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out,
+                         double* corners_out /* [.][4][2] or NULL */, uint64_t* code_out /* or NULL */, double* margin_out /* or NULL */);
 
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
