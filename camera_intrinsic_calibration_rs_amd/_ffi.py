@@ -19,6 +19,8 @@ TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1, 2
 MULTI_MAX_DEVICES = 16
 PIX_U8, PIX_U16 = 0, 1                          # ccal_pixel_type
 TAG_OK, TAG_OUTSIDE, TAG_LOW_CONTRAST, TAG_BORDER, TAG_NO_CODE = range(5)        # ccal_tag_reason
+QUAD_MAX_OUT_EDGES = 8                          # CCAL_QUAD_MAX_OUT_EDGES
+QUAD_FLAG_CUT = 1                               # bit 0 of ccal_propose_quads_*'s flags_out: an out-edge list was cut
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -184,6 +186,11 @@ SYMBOLS = [
                                          C.c_double, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp, _up, _dp]),
     ("ccal_decode_tags_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_int, C.c_int, _up, C.c_int, C.c_int,
                                        C.c_double, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp, _up, _dp]),
+    # from pixels to detections: proposing tag quads from corner candidates
+    ("ccal_propose_quads_batch", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, C.c_int, C.c_double, C.c_int, _ip, _ip, _ip, _dp]),
+    ("ccal_propose_quads_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_double, C.c_double, C.c_double,
+                                         C.c_double, C.c_int, C.c_double, C.c_int, _ip, _ip, _ip, _dp]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

@@ -26,6 +26,8 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   image_to_option_feature_frame's corner naming id = tag_id * 4 + i     frames_from_tags
   what tag_detector.detect decides for a quad (the absent aprilgrid crate; this project's rule, the family supplied by the
   caller, quads not proposed here)                                      decode_tags, TagFamily
+  what tag_detector.detect does for an AprilGrid image as a whole (this project's rules: saddles, their refinement, tag
+  outlines from the saddles, the decoder)                               detect_aprilgrid, propose_quads, merge_points
   a detector for plain checkerboards (the reference's tag detector is in the absent aprilgrid crate)
                                                                         detect_checkerboard, assemble_checkerboard
   (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
@@ -1136,6 +1138,80 @@ def frames_from_tags(decoded, board: AprilGridBoard, img_w_h: Tuple[int, int], t
         else:
             out.append(FrameFeature(int(times[k]) if times is not None else k, (int(img_w_h[0]), int(img_w_h[1])), feats))
     return out
+
+
+def merge_points(xy, radius: float = 1.0) -> np.ndarray:
+    """The points [n, 2] without near-duplicates: in the given order, a point within `radius` px in BOTH coordinates of a point
+    kept before it is dropped.  Two detector candidates can refine onto one saddle, to the last bit or nearly; as separate points
+    they would multiply every outline they belong to."""
+    pts = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    kept = np.zeros((len(pts), 2))
+    n = 0
+    for p in pts:
+        if not (np.abs(kept[:n] - p) <= radius).all(axis=1).any():
+            kept[n] = p
+            n += 1
+    return kept[:n].copy()
+
+
+def _same_images(where: str, images) -> np.ndarray:
+    imgs = [np.asarray(im) for im in images]
+    if any(im.ndim != 2 or im.shape != imgs[0].shape or im.dtype != imgs[0].dtype for im in imgs):
+        raise ValueError(f"{where}: single-channel images [H][W] of one size and type")
+    stack, _, _ = check_images(np.stack(imgs), True)
+    return stack
+
+
+def propose_quads(images, xy_list, family: Optional[TagFamily] = None, border: int = 1, min_side: float = 20.0,
+                  max_side: Optional[float] = None, max_side_ratio: float = 2.0, offset: Optional[float] = None, samples: int = 8,
+                  min_contrast: float = 40.0, max_per_image: int = 1024, ctx: Optional[Context] = None
+                  ) -> List[Tuple[np.ndarray, int, int]]:
+    """Candidate tag outlines of an AprilGrid from refined saddle points (ccal_propose_quads_batch: one wavefront per point, all
+    images in one call; the rule is stated in include/ccal.h).  images: one grey image [H][W] per entry (uint8 or uint16, all of one
+    size); xy_list: per image the refined corner candidates [n_i, 2], in any order - merge_points is applied to them first.
+    offset None: half a cell of the family's tags, 1 / (2 (family.d + 2 border)); without a family 1/16 (36 bits, one border cell).
+    max_side None: half the larger image side.  min_contrast is in grey levels of the images' type (scale it by 257 for uint16
+    images that span the 16 bits).  Returns per image (quads [m, 4, 2] - clockwise in the image, ready for decode_tags -, count,
+    flags): m = min(count, max_per_image); bit 0 of flags says a point had more than 8 out-edges and proposals may be missing."""
+    if len(images) != len(xy_list):
+        raise ValueError("propose_quads: one array of points per image")
+    if not len(images):
+        return []
+    if offset is None:
+        offset = 1.0 / (2.0 * (family.d + 2 * int(border))) if family is not None else 1.0 / 16.0
+    stack = _same_images("propose_quads", images)
+    got = _ctx(ctx).propose_quads_batch(stack, [merge_points(xy) for xy in xy_list], min_side, max_side, max_side_ratio, offset,
+                                        samples, min_contrast, max_per_image)
+    return [(quads, count, flags) for _, quads, count, flags in got]
+
+
+def detect_aprilgrid(images, family: TagFamily, board: AprilGridBoard, step: int = 1, nms_radius: int = 5, rel_threshold: float = 0.1,
+                     half_win: int = 4, min_side: float = 20.0, max_side: Optional[float] = None, min_contrast: float = 40.0,
+                     border: int = 1, max_hamming: int = 2, times: Optional[Sequence[int]] = None, min_corners: int = 24,
+                     ctx: Optional[Context] = None) -> List[Optional[FrameFeature]]:
+    """From images alone to detections of an AprilGrid: the integer saddle detector over all images (ccal_detect_corners_batch), the
+    sub-pixel refinement of its candidates (ccal_refine_corners_batch; candidates whose status is not CCAL_OK are dropped, the rest
+    rounded through the f32 a FeaturePoint holds), merge_points, the quad proposer (ccal_propose_quads_batch, offset from the
+    family's bit count and `border`), the decoder (decode_tags) and frames_from_tags.  images: grey [H][W] each, uint8 or uint16, of
+    one size.  family: the table the board was printed from - none ships with this project.  Returns one entry per image: a
+    FrameFeature (corner id = tag_id * 4 + i, p3d from `board`, time_ns from `times` or the image's index) or None for an image with
+    fewer than min_corners corners.
+    half_win 4 suits tags whose cells are 5 to 6 px: the window around a tag's outer corner has to hold the border cell and the
+    gap square and little of the data cells.  min_contrast goes to BOTH the proposer (bright - dark along an edge) and the decoder
+    (hi - lo over a tag's cells) and is in grey levels of the images' type: for uint16 images the caller scales it (by 257 when
+    they span the 16 bits); nothing here guesses the range from the pixels."""
+    if not len(images):
+        return []
+    stack = _same_images("detect_aprilgrid", images)
+    H, W = stack.shape[1:]
+    c = _ctx(ctx)
+    found = c.detect_corners_batch(stack, step, nms_radius, 1, rel_threshold)
+    xy, status, _, _ = c.refine_corners_batch(stack, [f[0].astype(np.float64) for f in found], half_win)
+    points = [merge_points(np.float32(xy[k][status[k] == _ffi.OK]).astype(np.float64)) for k in range(len(stack))]
+    offset = 1.0 / (2.0 * (family.d + 2 * int(border)))
+    proposed = c.propose_quads_batch(stack, points, min_side, max_side, 2.0, offset, 8, min_contrast)
+    decoded = decode_tags(list(stack), [p[1] for p in proposed], family, border, 3, min_contrast, 0, max_hamming, ctx=c)
+    return frames_from_tags(decoded, board, (W, H), times, min_corners)
 
 
 class ReprojectionFactor:

@@ -1,0 +1,359 @@
+// Quad proposal (ccal_propose_quads_batch / _dev): the refined saddle points of a batch of grey images grouped into candidate tag
+// outlines, by the rule stated at the entry points in include/ccal.h.  Per chunk of whole images three launches, one wavefront per
+// point A, four per workgroup, no LDS, no barriers, no atomics:
+//   edges    k_quad_edges: the lanes stride B over the points of A's image in blocks of 64; a lane runs the length test and then its
+//            own 2 K bilinear f64 samples, and stops once bright - dark has fallen below the threshold (min and max are monotone: the
+//            decision is the same).  The passing lanes of a block are one __ballot mask, a lane's slot is the running count plus the
+//            popcount of the lower mask bits - index order; the first kQuadMaxOut go to adj[A][.], deg[A] keeps the full count.
+//   count    k_quad_chains<false>: the at most 8^3 chains (i, j, k) over the three out-edge lists, 64 per pass in that order - i is
+//            the pass, so wave-uniform; the lists are sorted, so this is the (B, C, D) index order.  cnt[A] = A's quads.
+//   write    k_quad_chains<true>: the same walk, each quad to the row base[A] + its rank in the walk, below the cap.
+// Between count and write the host reads deg and cnt (8 bytes per point), forms per image the count, the flags and the exclusive
+// scan base[] - the point at which it has to synchronise anyway, to size the block of the stored rows - so no per-corner cap enters
+// the rule and the rows of an image are in lexicographic order of (A, B, C, D) whatever the batch looks like.
+// An image's outputs are a pure function of that image, its points and the parameters.  This unit is compiled with
+// -ffp-contract=off (csrc/Makefile): the outputs are decisions, and tests/quad_ref.py, the numpy f64 yardstick, rounds every product
+// and sum on its own.  Every pixel index is clamped to the image; the inside test makes the clamp a no-op, the clamp stays as the guard.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "ccal_call.hpp"
+#include "ccal_quads_plan.hpp"
+
+namespace ccal {
+
+constexpr int kQuadWaves = 4;                 // wavefronts (= points A in flight) per workgroup
+constexpr int kQuadMaxOut = CCAL_QUAD_MAX_OUT_EDGES;
+constexpr int kQuadMaxSamples = 16;
+constexpr int64_t kQuadMaxPoints = 32768;     // per image: the pair search is quadratic
+constexpr size_t kQuadChunkBytes = (size_t)256 << 20;     // the block one launch should need: larger batches go image chunk by chunk
+static_assert(kQuadMaxOut == 8, "a pass of 64 lanes is one i and all (j, k)");
+// the second library only (-DCCAL_TEST_HOOKS): CCAL_TEST_QUADS_CHUNK_BYTES replaces the limit, so that a test cuts a small batch
+// into chunks (tests/test_gpu_quads.py); read on every call
+inline size_t quad_chunk_bytes() {
+#ifdef CCAL_TEST_HOOKS
+    if (const char* e = std::getenv("CCAL_TEST_QUADS_CHUNK_BYTES")) return (size_t)std::strtoull(e, nullptr, 10);
+#endif
+    return kQuadChunkBytes;
+}
+
+struct QuadArgs {
+    const void* img;                    // [n_img][H][W] of T, the chunk's first image first
+    const int64_t* off;                 // [n_img + 1]: the caller's offsets of the chunk's images (not rebased)
+    const double* xy;                   // [n][2], the chunk's first point first
+    int32_t* adj;                       // [n][kQuadMaxOut]: out-edge lists, indices local to the image; slots past min(deg, 8) unwritten
+    int32_t* deg;                       // [n] full out-degree
+    int32_t* cnt;                       // [n] quads whose smallest corner is the point
+    const int32_t* base;                // [n] the rank, within its image, of the point's first quad (written by the host)
+    const int64_t* rowoff;              // [n_img + 1] the first stored row of each image in oidx / oquads
+    int32_t* oidx;                      // [rows][4]
+    double* oquads;                     // [rows][4][2] or NULL
+    int64_t p0;                         // the caller's index of the chunk's first point = off[0]
+    int64_t n;                          // points in the chunk
+    int32_t W, H, n_img, K, cap;
+    double min2, max2, ratio2, offset, min_contrast;
+};
+
+// the point of wavefront g: its image k (the last with off[k] <= p0 + g; images without points are stepped over), the chunk
+// index of the image's first point, the image's point count
+__device__ __forceinline__ void quad_locate(const QuadArgs& a, int64_t g, int& k, int64_t& first, int& m) {
+    const int64_t gp = a.p0 + g;
+    int lo = 0, hi = a.n_img;
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a.off[mid] <= gp) lo = mid; else hi = mid;
+    }
+    k = lo;
+    first = a.off[lo] - a.p0;
+    m = (int)(a.off[lo + 1] - a.off[lo]);
+}
+
+// floor and fraction of one coordinate, the two neighbour indices clamped to [0, n - 1]
+__device__ __forceinline__ void quad_tap(double x, int32_t n, int32_t& i0, int32_t& i1, double& ax) {
+    const double f = floor(x);
+    ax = x - f;
+    const double hi = (double)(n - 1);
+    i0 = (int32_t)fmin(fmax(f, 0.0), hi);            // NaN: fmax gives 0
+    i1 = min(i0 + 1, n - 1);
+}
+
+template <class T>
+__device__ __forceinline__ double quad_sample(const T* img, int32_t W, int32_t H, double x, double y) {
+    int32_t x0, x1, y0, y1;
+    double ax, ay;
+    quad_tap(x, W, x0, x1, ax);
+    quad_tap(y, H, y0, y1, ay);
+    const T* r0 = img + (int64_t)y0 * W;
+    const T* r1 = img + (int64_t)y1 * W;
+    const double p00 = (double)r0[x0], p01 = (double)r0[x1], p10 = (double)r1[x0], p11 = (double)r1[x1];
+    const double top = p00 + ax * (p01 - p00), bot = p10 + ax * (p11 - p10);
+    return top + ay * (bot - top);
+}
+
+template <class T>
+__global__ __launch_bounds__(64 * kQuadWaves) void k_quad_edges(const QuadArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * kQuadWaves + wave;
+    if (g >= a.n) return;                                // wave-uniform; the kernel has no barrier
+    int k, m;
+    int64_t first;
+    quad_locate(a, g, k, first, m);
+    const int la = (int)(g - first);
+    const T* img = static_cast<const T*>(a.img) + (int64_t)k * a.W * a.H;
+    const double* P = a.xy + 2 * first;
+    const double Ax = P[2 * la], Ay = P[2 * la + 1];
+    const double x_hi = (double)(a.W - 1), y_hi = (double)(a.H - 1), k1 = (double)(a.K + 1);
+    int run = 0;
+    for (int b0 = 0; b0 < m; b0 += 64) {
+        const int b = b0 + lane;
+        bool edge = false;
+        if (b < m && b != la) {
+            const double ex = P[2 * b] - Ax, ey = P[2 * b + 1] - Ay;
+            const double L2 = ex * ex + ey * ey;
+            if (L2 >= a.min2 && L2 <= a.max2) {          // false for NaN
+                const double nx = -a.offset * ey, ny = a.offset * ex;
+                double dark = -__builtin_inf(), bright = __builtin_inf();
+                edge = true;
+                for (int s = 0; s < a.K && edge; ++s) {
+                    const double t = (double)(s + 1) / k1;
+                    const double px = Ax + t * ex, py = Ay + t * ey;
+                    const double xi = px + nx, yi = py + ny, xo = px - nx, yo = py - ny;
+                    edge = xi >= 0.0 && xi <= x_hi && yi >= 0.0 && yi <= y_hi && xo >= 0.0 && xo <= x_hi && yo >= 0.0 && yo <= y_hi;
+                    if (edge) {
+                        dark = fmax(dark, quad_sample(img, a.W, a.H, xi, yi));
+                        bright = fmin(bright, quad_sample(img, a.W, a.H, xo, yo));
+                        edge = bright - dark >= a.min_contrast;      // it only falls from here on
+                    }
+                }
+            }
+        }
+        const unsigned long long mask = __ballot(edge);
+        if (edge) {
+            const int slot = run + __popcll(mask & ((1ull << lane) - 1ull));
+            if (slot < kQuadMaxOut) a.adj[(int64_t)kQuadMaxOut * g + slot] = b;
+        }
+        run += __popcll(mask);
+    }
+    if (lane == 0) a.deg[g] = run;
+}
+
+template <bool kWrite>
+__global__ __launch_bounds__(64 * kQuadWaves) void k_quad_chains(const QuadArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * kQuadWaves + wave;
+    if (g >= a.n) return;
+    int img_k, m;
+    int64_t first;
+    quad_locate(a, g, img_k, first, m);
+    const int A = (int)(g - first);
+    const int32_t* adj = a.adj + kQuadMaxOut * first;    // the image's lists and degrees, by local index
+    const int32_t* deg = a.deg + first;
+    const double* P = a.xy + 2 * first;
+    const int dA = min(deg[A], kQuadMaxOut);
+    const double Ax = P[2 * A], Ay = P[2 * A + 1];
+    int run = kWrite ? a.base[g] : 0;                    // quads of the image in front of the pass's first
+    const int64_t row0 = kWrite ? a.rowoff[img_k] : 0;
+    const int j = lane >> 3, kk = lane & 7;
+    for (int i = 0; i < dA; ++i) {                       // pass i: the chains (i, j, kk), 64 in order of the lane number
+        if (kWrite && run >= a.cap) break;
+        const int B = adj[kQuadMaxOut * A + i];
+        bool quad = false;
+        int Cc = 0, D = 0;
+        if (A < B && j < min(deg[B], kQuadMaxOut)) {
+            Cc = adj[kQuadMaxOut * B + j];
+            if (A < Cc && kk < min(deg[Cc], kQuadMaxOut)) {
+                D = adj[kQuadMaxOut * Cc + kk];
+                bool closes = false;
+                if (A < D && D != B) {
+                    const int dD = min(deg[D], kQuadMaxOut);
+                    for (int t = 0; t < dD; ++t) closes = closes || adj[kQuadMaxOut * D + t] == A;
+                }
+                if (closes) {
+                    const double e1x = P[2 * B] - Ax, e1y = P[2 * B + 1] - Ay;
+                    const double e2x = P[2 * Cc] - P[2 * B], e2y = P[2 * Cc + 1] - P[2 * B + 1];
+                    const double e3x = P[2 * D] - P[2 * Cc], e3y = P[2 * D + 1] - P[2 * Cc + 1];
+                    const double e4x = Ax - P[2 * D], e4y = Ay - P[2 * D + 1];
+                    const bool convex = e1x * e2y - e1y * e2x > 0.0 && e2x * e3y - e2y * e3x > 0.0 && e3x * e4y - e3y * e4x > 0.0 &&
+                                        e4x * e1y - e4y * e1x > 0.0;
+                    const double s1 = e1x * e1x + e1y * e1y, s2 = e2x * e2x + e2y * e2y, s3 = e3x * e3x + e3y * e3y, s4 = e4x * e4x + e4y * e4y;
+                    const double smax = fmax(fmax(s1, s2), fmax(s3, s4)), smin = fmin(fmin(s1, s2), fmin(s3, s4));
+                    quad = convex && smax <= a.ratio2 * smin;
+                }
+            }
+        }
+        const unsigned long long mask = __ballot(quad);
+        if (kWrite && quad) {
+            const int r = run + __popcll(mask & ((1ull << lane) - 1ull));
+            if (r < a.cap) {
+                const int64_t row = row0 + r;
+                a.oidx[4 * row] = A; a.oidx[4 * row + 1] = B; a.oidx[4 * row + 2] = Cc; a.oidx[4 * row + 3] = D;
+                if (a.oquads) {
+                    double* q = a.oquads + 8 * row;
+                    q[0] = Ax; q[1] = Ay; q[2] = P[2 * B]; q[3] = P[2 * B + 1];
+                    q[4] = P[2 * Cc]; q[5] = P[2 * Cc + 1]; q[6] = P[2 * D]; q[7] = P[2 * D + 1];
+                }
+            }
+        }
+        run += __popcll(mask);
+    }
+    if (!kWrite && lane == 0) a.cnt[g] = run;
+}
+
+namespace {
+
+int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
+               const int64_t* offsets, const double* xy, double min_side, double max_side, double max_side_ratio, double offset,
+               int samples, double min_contrast, int cap, int32_t* count_out, int32_t* flags_out, int32_t* idx_out, double* quads_out) {
+    char msg[160];
+    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    if (!(min_side >= 1.0)) return bad("min_side < 1");
+    if (!(max_side >= min_side)) return bad("max_side < min_side");
+    if (!(max_side_ratio >= 1.0)) return bad("max_side_ratio < 1");
+    if (!(offset > 0.0 && offset <= 0.25)) return bad("offset outside (0, 0.25]");
+    if (samples < 1 || samples > kQuadMaxSamples) return bad("samples outside 1 .. 16");
+    if (!(min_contrast >= 0.0) || !std::isfinite(min_contrast)) return bad("min_contrast negative or not finite");
+    if (cap < 1) return bad("cap < 1");
+    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
+    if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
+    if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
+    if (n_img == 0) return CCAL_OK;
+    if (!images || !offsets || !count_out || !flags_out || !idx_out) return bad("NULL argument");
+    if (check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
+    if (offsets[n_img] > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 points");
+    for (int k = 0; k < n_img; ++k)
+        if (offsets[k + 1] - offsets[k] > kQuadMaxPoints) return bad("more than 32768 points in an image");
+    if (offsets[n_img] > 0 && !xy) return bad("NULL argument");
+    std::fill(count_out, count_out + n_img, 0);
+    std::fill(flags_out, flags_out + n_img, 0);
+    if (offsets[n_img] == 0) return CCAL_OK;
+
+    // chunks of whole images: as many as keep the chunk's images (host call), points and work arrays within the limit, at least one
+    const size_t ni = (size_t)n_img, img_bytes = (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height;
+    static_assert(kQuadPerPointBytes == 2 * sizeof(double) + (kQuadMaxOut + 3) * sizeof(int32_t), "xy | adj | deg, cnt, base");
+    const std::vector<size_t> cut = quad_chunk_cuts(offsets, ni, quad_per_image_bytes(images_on_device, img_bytes), quad_chunk_bytes());
+    size_t max_img = 0, max_pts = 0;
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        max_img = std::max(max_img, cut[c + 1] - cut[c]);
+        max_pts = std::max(max_pts, (size_t)(offsets[cut[c + 1]] - offsets[cut[c]]));
+    }
+
+    // one block for the largest chunk: offsets, row offsets | images (host call) | points | lists, degrees, counts, bases
+    CallBlock blk(ctx);
+    const auto s_off = blk.add<int64_t>(max_img + 1);
+    const auto s_rowoff = blk.add<int64_t>(max_img + 1);
+    const auto s_img = blk.add<char>(images_on_device ? 0 : img_bytes * max_img);
+    const auto s_xy = blk.add<double>(2 * max_pts);
+    const auto s_adj = blk.add<int32_t>(kQuadMaxOut * max_pts);
+    const auto s_deg = blk.add<int32_t>(max_pts);
+    const auto s_cnt = blk.add<int32_t>(max_pts);
+    const auto s_base = blk.add<int32_t>(max_pts);
+    if (!blk.alloc()) return blk.finish(where);
+
+    QuadArgs a = {};
+    a.off = blk.at(s_off); a.rowoff = blk.at(s_rowoff); a.xy = blk.at(s_xy);
+    a.adj = blk.at(s_adj); a.deg = blk.at(s_deg); a.cnt = blk.at(s_cnt); a.base = blk.at(s_base);
+    a.W = width; a.H = height; a.K = samples; a.cap = cap;
+    a.min2 = min_side * min_side; a.max2 = max_side * max_side; a.ratio2 = max_side_ratio * max_side_ratio;
+    a.offset = offset; a.min_contrast = min_contrast;
+    std::vector<int32_t> h_deg(max_pts), h_cnt(max_pts), h_base(max_pts), h_idx;
+    std::vector<int64_t> rowoff(max_img + 1);
+    std::vector<double> h_quads;
+
+    for (size_t c = 0; c + 1 < cut.size() && blk.ok(); ++c) {
+        const size_t k0 = cut[c], m = cut[c + 1] - k0;
+        const size_t at = (size_t)offsets[k0], np = (size_t)(offsets[k0 + m] - offsets[k0]);
+        if (!np) continue;
+        a.n_img = (int32_t)m; a.p0 = offsets[k0]; a.n = (int64_t)np;
+        a.img = images_on_device ? (const void*)(static_cast<const char*>(images) + k0 * img_bytes) : (const void*)blk.at(s_img);
+        const dim3 grid((unsigned)((np + kQuadWaves - 1) / kQuadWaves)), block(64 * kQuadWaves);
+        blk.upload(s_off, offsets + k0, m + 1);
+        if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
+        blk.upload(s_xy, xy + 2 * at, 2 * np);
+        if (blk.ok()) {
+            if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_quad_edges<uint16_t>, grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL(k_quad_edges<uint8_t>, grid, block, 0, ctx->stream, a);
+            hipLaunchKernelGGL(k_quad_chains<false>, grid, block, 0, ctx->stream, a);
+            blk.launched();
+        }
+        blk.download(h_deg.data(), a.deg, np);
+        blk.download(h_cnt.data(), a.cnt, np);
+        if (blk.ok()) blk.note(hipStreamSynchronize(ctx->stream));
+        if (!blk.ok()) break;
+
+        // per image: the count, the flags, the exclusive scan of the points' counts, the stored rows
+        rowoff[0] = 0;
+        for (size_t i = 0; i < m; ++i) {
+            int64_t count = 0;
+            int32_t flags = 0;
+            for (size_t p = (size_t)offsets[k0 + i] - at, e = (size_t)offsets[k0 + i + 1] - at; p < e; ++p) {
+                h_base[p] = (int32_t)count;               // at most 32768 * 8^3 = 2^24
+                count += h_cnt[p];
+                if (h_deg[p] > kQuadMaxOut) flags |= 1;
+            }
+            count_out[k0 + i] = (int32_t)count;
+            flags_out[k0 + i] = flags;
+            rowoff[i + 1] = rowoff[i] + std::min<int64_t>(count, (int64_t)cap);
+        }
+        const size_t total = (size_t)rowoff[m];
+        if (!total) continue;
+
+        // the stored rows of the chunk, image after image: a block of exactly their size
+        CallBlock rows(ctx);
+        const auto s_oidx = rows.add<int32_t>(4 * total);
+        const auto s_oquads = rows.add<double>(quads_out ? 8 * total : 0);
+        if (!rows.alloc()) return rows.finish(where);
+        a.oidx = rows.at(s_oidx); a.oquads = rows.at(s_oquads);
+        if (quads_out) rows.poison(s_oquads, s_oquads);   // the test hook's NaN over the doubles the kernel writes and never reads
+        blk.upload(s_base, h_base.data(), np);
+        blk.upload(s_rowoff, rowoff.data(), m + 1);
+        if (!blk.ok()) break;                             // no launch: nothing of the unwritten rows reaches the caller's arrays
+        if (rows.ok()) {
+            hipLaunchKernelGGL(k_quad_chains<true>, grid, block, 0, ctx->stream, a);
+            rows.launched();
+        }
+        h_idx.resize(4 * total);
+        if (quads_out) h_quads.resize(8 * total);
+        rows.download(h_idx.data(), a.oidx, 4 * total);
+        rows.download(quads_out ? h_quads.data() : nullptr, a.oquads, 8 * total);
+        const int rc = rows.finish(where);                // synchronises
+        if (rc != CCAL_OK) return rc;
+        for (size_t i = 0; i < m; ++i) {                  // to [k][cap] of the caller's arrays
+            const size_t r0 = (size_t)rowoff[i], nr = (size_t)(rowoff[i + 1] - rowoff[i]), k = k0 + i;
+            if (!nr) continue;
+            std::memcpy(idx_out + 4 * k * (size_t)cap, h_idx.data() + 4 * r0, nr * 4 * sizeof(int32_t));
+            if (quads_out) std::memcpy(quads_out + 8 * k * (size_t)cap, h_quads.data() + 8 * r0, nr * 8 * sizeof(double));
+        }
+    }
+    return blk.finish(where);
+}
+
+}  // namespace
+}  // namespace ccal
+
+using namespace ccal;
+
+extern "C" {
+
+int ccal_propose_quads_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images, const int64_t* offsets,
+                             const double* xy, double min_side, double max_side, double max_side_ratio, double offset, int samples,
+                             double min_contrast, int cap, int32_t* count_out, int32_t* flags_out, int32_t* idx_out, double* quads_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    return quads_call(ctx, "ccal_propose_quads_batch", false, dtype, width, height, n_img, images, offsets, xy, min_side, max_side,
+                      max_side_ratio, offset, samples, min_contrast, cap, count_out, flags_out, idx_out, quads_out);
+    CCAL_API_CATCH(ctx)
+}
+
+int ccal_propose_quads_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev, const int64_t* offsets,
+                           const double* xy, double min_side, double max_side, double max_side_ratio, double offset, int samples,
+                           double min_contrast, int cap, int32_t* count_out, int32_t* flags_out, int32_t* idx_out, double* quads_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    return quads_call(ctx, "ccal_propose_quads_dev", true, dtype, width, height, n_img, images_dev, offsets, xy, min_side, max_side,
+                      max_side_ratio, offset, samples, min_contrast, cap, count_out, flags_out, idx_out, quads_out);
+    CCAL_API_CATCH(ctx)
+}
+
+}  // extern "C"

@@ -425,6 +425,58 @@ class Context:
         return self._tags(self.lib.ccal_decode_tags_dev, "ccal_decode_tags_dev", images_ptr, dtype, width, height, n_img, quads_list,
                           family_bits, codes, border, samples, min_contrast, max_border_errors, max_hamming)
 
+    # -- from pixels to detections: proposing tag quads from corner candidates (ccal_propose_quads_batch, ccal_kernels_quads.hip) ------
+    def _quads(self, fn, where, ptr, dtype, width, height, n_img, xy_list, min_side, max_side, max_side_ratio, offset, samples,
+               min_contrast, max_per_image):
+        if len(xy_list) != n_img:
+            raise ValueError(f"{where}: one array of points per image")
+        if max_side is None:
+            max_side = max(int(width), int(height)) / 2.0
+        offs, xy = _pack(xy_list, 2)
+        cap, m = int(max_per_image), max(int(n_img), 1)
+        # a point starts at most 8^3 chains: no room beyond that is needed
+        most = max((int(offs[k + 1] - offs[k]) for k in range(int(n_img))), default=0)
+        if cap >= 1:
+            cap = max(min(cap, _ffi.QUAD_MAX_OUT_EDGES ** 3 * most), 1)
+        rows = max(cap, 1)
+        count = np.zeros(m, dtype=np.int32); flags = np.zeros(m, dtype=np.int32)
+        # NOT pre-filled with a poison value as the neighbouring wrappers' outputs are: at 1024 images and cap 1024 the two arrays are
+        # 80 MB, and filling them cost 1.1 of a call's 8.07 ms (6.95 ms without).  Rows past min(count, cap) are never read below;
+        # the price is that only a caller of the C entry point with its own sentinels (tests/test_gpu_quads.py: raw_propose) can
+        # see a stored row the library failed to write
+        idx = np.empty((m, rows, 4), dtype=np.int32); quads = np.empty((m, rows, 4, 2))
+        rc = fn(self.handle, int(dtype), int(width), int(height), int(n_img), C.c_void_p(ptr), _lp(offs), _dp(xy), float(min_side),
+                float(max_side), float(max_side_ratio), float(offset), int(samples), float(min_contrast), cap, _ip(count), _ip(flags),
+                _ip(idx), _dp(quads))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        return [(idx[k, :min(int(count[k]), rows)].copy(), quads[k, :min(int(count[k]), rows)].copy(), int(count[k]), int(flags[k]))
+                for k in range(int(n_img))]
+
+    def propose_quads_batch(self, images, xy_list, min_side: float = 20.0, max_side: Optional[float] = None, max_side_ratio: float = 2.0,
+                            offset: float = 1.0 / 16.0, samples: int = 8, min_contrast: float = 40.0, max_per_image: int = 1024):
+        """Candidate tag outlines of an AprilGrid from the refined saddle points of every image of a batch, by the rule stated at
+        ccal_propose_quads_batch in include/ccal.h.  images: [n][H][W], uint8 or uint16; xy_list: one array [n_i, 2] of (x, y) points
+        per image, in any order.  max_side None: half the larger image side.  offset: half a cell of the tag as a fraction of its
+        side, 1 / (2 (d + 2 border)); min_contrast is in grey levels of the images' type.  Returns one tuple per image:
+        (idx int32 [m, 4] - the corners' indices into the image's points -, quads f64 [m, 4, 2] - their coordinates, ready for
+        decode_tags_batch -, count, flags) in lexicographic order of the indices, with m = min(count, max_per_image); bit 0 of flags
+        (_ffi.QUAD_FLAG_CUT): a point had more than 8 out-edges, proposals may be missing."""
+        images, dtype, channels = check_images(images, True)
+        if channels != 1:
+            raise ValueError("propose_quads_batch: single-channel images [n][H][W]")
+        n_img, H, W = images.shape[:3]
+        return self._quads(self.lib.ccal_propose_quads_batch, "ccal_propose_quads_batch", images.ctypes.data, dtype, W, H, n_img, xy_list,
+                           min_side, max_side, max_side_ratio, offset, samples, min_contrast, max_per_image)
+
+    def propose_quads_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, xy_list, min_side: float = 20.0,
+                          max_side: Optional[float] = None, max_side_ratio: float = 2.0, offset: float = 1.0 / 16.0, samples: int = 8,
+                          min_contrast: float = 40.0, max_per_image: int = 1024):
+        """propose_quads_batch over an image block that is already on the device (a device pointer to [n_img][height][width] of
+        dtype _ffi.PIX_U8 / PIX_U16, its writes complete or enqueued on the context's stream); points and results are host arrays."""
+        return self._quads(self.lib.ccal_propose_quads_dev, "ccal_propose_quads_dev", images_ptr, dtype, width, height, n_img, xy_list,
+                           min_side, max_side, max_side_ratio, offset, samples, min_contrast, max_per_image)
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first

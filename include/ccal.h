@@ -43,6 +43,9 @@
  *   ccal_decode_tags_batch / _dev
  *                            which tag a candidate quad holds, its turn and its bit errors, against a caller-supplied family
  *                            (this project's rule; what tag_detector.detect decides inside the absent aprilgrid crate)
+ *   ccal_propose_quads_batch / _dev
+ *                            candidate tag outlines of an AprilGrid from refined saddle points: what feeds ccal_decode_tags_* from
+ *                            images alone (this project's rule)
  *
  * Parameter layout.
  *   intr   [n_cams][CCAL_PMAX]  FULL model parameters [fx,fy,cx,cy,dist...] per camera, like
@@ -715,7 +718,8 @@ int ccal_detect_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int
 /* ---- from pixels to detections: decoding tags in candidate quads (batched quad sampling and code match) -----------------------
  * What the reference's front end does before it names corners (image_to_option_feature_frame, src/data_loader.rs:36-70: corner
  * id = tag_id * 4 + i, looked up in Board::init_aprilgrid, src/board.rs:46-95): given an image and a candidate quad, decide which
- * tag of a family this is, how it is turned and by how many bits it misses.  Quads are NOT proposed here.  The rule is this
+ * tag of a family this is, how it is turned and by how many bits it misses.  Quads are NOT proposed here (ccal_propose_quads_* below
+ * does that for AprilGrids).  The rule is this
  * project's; the reference's decoder lives in the absent aprilgrid crate, so parity with it is NOT pinned.  A family is data - a
  * bit count and a list of codes - and the caller supplies it (from the library that printed the board); none is built in.
  * tests/tag_ref.py is the rule's numpy f64 yardstick; the library evaluates the rule without fused multiply-adds, each product
@@ -779,6 +783,60 @@ int ccal_decode_tags_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_
                          int max_border_errors, int max_hamming,
                          int32_t* reason_out, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out,
                          double* corners_out /* [.][4][2] or NULL */, uint64_t* code_out /* or NULL */, double* margin_out /* or NULL */);
+
+/* ---- from pixels to detections: proposing AprilGrid tag quads from corner candidates ------------------------------------------
+ * The step between the refinement and the decoder above: the refined saddle points of an image grouped into candidate tag
+ * outlines, which go straight into ccal_decode_tags_*.  It rests on the geometry of an AprilGrid (tags with black gap squares at
+ * their corners): a tag's four outer corners are saddles - the black border cell meets the black gap square diagonally -, and
+ * along each outer edge the inside is the black border ring and the outside the white gap strip, for the whole length of the
+ * edge.  Plain AprilTags without gap squares are not served.  The rule is this project's (what the absent aprilgrid crate does in
+ * its place is not pinned); tests/quad_ref.py is its numpy f64 yardstick, and the library evaluates it without fused
+ * multiply-adds, each product and sum rounded on its own, so the yardstick is met exactly.
+ *
+ * Images: as in the three sections above - [n_img][height][width] of CCAL_PIX_U8 / CCAL_PIX_U16, a pixel's centre at integer
+ * coordinates, I(x, y) the bilinear f64 sample written in differences of ccal_refine_corners_*.  Image k owns the points
+ * [offsets[k], offsets[k + 1]) of xy [.][2] = (x, y), f64: the refined candidates, in any order; indices below are local to the image.
+ * Parameters: min_side >= 1 (px; 20 is a useful default), max_side >= min_side (120; half the larger image side in the Python
+ * layers), max_side_ratio >= 1 (2), 0 < offset <= 0.25 (1 / (2 (d + 2 border)) - half a cell - for a family of d x d bits; 1/16
+ * for a 36-bit family with one border cell), samples K in 1 .. 16 (8), min_contrast >= 0 and finite, in grey levels of the dtype
+ * (40 for 8-bit images), cap >= 1.  At offset = 1/8 the inner samples of such a family sit on the boundary between the border
+ * ring and the data cells, and the rendered fixture of the tests loses tags: keep the samples in the middle of the ring.
+ *   1 edge       the directed pair A -> B, A != B: e = B - A, L2 = e.x e.x + e.y e.y; min_side^2 <= L2 <= max_side^2, else no edge.
+ *                n = (-offset * e.y, offset * e.x): the inward offset vector - with y pointing down it points to the right of the
+ *                walk from A to B; no square root.  For k = 0 .. K - 1: t = (k + 1) / (K + 1), p = (A.x + t e.x, A.y + t e.y),
+ *                in_k = I(p + n), out_k = I(p - n).  All 2 K sample points satisfy 0 <= x <= width - 1 and 0 <= y <= height - 1
+ *                (false for NaN), else no edge.  dark = max in_k, bright = min out_k: an edge iff bright - dark >= min_contrast.
+ *   2 lists      out(A) = the B with an edge A -> B in increasing index order, cut to the first CCAL_QUAD_MAX_OUT_EDGES.  If any
+ *                list of an image is cut, bit 0 of that image's flags_out is set: proposals may then be missing.
+ *   3 quads      (A, B, C, D) with B in out(A), C in out(B), D in out(C), A in out(D); all four distinct; A the smallest index
+ *                (each outline appears once); strictly convex and clockwise in image coordinates: with e1 = B - A, e2 = C - B,
+ *                e3 = D - C, e4 = A - D the cross products u.x v.y - u.y v.x of (e1, e2), (e2, e3), (e3, e4), (e4, e1) are all
+ *                > 0; and the largest squared side <= max_side_ratio^2 times the smallest.
+ * Outputs per image k, the quads in lexicographic order of (A, B, C, D): count_out[k] = their number - it may exceed cap, then the
+ * first cap in that order are stored -, idx_out [n_img][cap][4] = the corner indices, quads_out [n_img][cap][4][2] = the corners'
+ * coordinates, bit-equal to the input points (NULL: not wanted), flags_out[k].  Rows past min(count, cap) are not written.
+ * A proposed quad starts at whichever of its corners has the smallest index; ccal_decode_tags_* names the turn.
+ * An image's outputs are a pure function of that image, its points and the parameters: they do not depend on its place in the
+ * batch, on what else is in it, on how the library cuts the batch into chunks or on the run (no atomics; a point's out-edges and
+ * an image's quads are compacted by ballot and prefix in index order).
+ * ccal_propose_quads_batch: host pointers.  ccal_propose_quads_dev: `images_dev` is a device pointer (the output of ccal_remap_dev
+ * on this context's stream, or a block whose writes are complete); everything else stays a host array.  Both return when the
+ * outputs are written.
+ * CCAL_ERR_INVALID_ARG, nothing launched or written: a parameter outside the ranges above, a dtype other than the two, width,
+ * height <= 0 or n_img < 0, more than 2^31 - 1 pixels in an image, offsets that do not start at 0 or decrease, more than 32768
+ * points in one image (the pair search is quadratic) or 2^31 - 1 in the call, a NULL required pointer (with n_img > 0: images,
+ * offsets, count_out, flags_out, idx_out; xy when there are points).  n_img == 0 and an image without points are valid. */
+#define CCAL_QUAD_MAX_OUT_EDGES 8
+int ccal_propose_quads_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images,
+                             const int64_t* offsets /* [n_img + 1] */, const double* xy /* [.][2] */,
+                             double min_side, double max_side, double max_side_ratio, double offset, int samples, double min_contrast,
+                             int cap, int32_t* count_out /* [n_img] */, int32_t* flags_out /* [n_img] */,
+                             int32_t* idx_out /* [n_img][cap][4] */, double* quads_out /* [n_img][cap][4][2] or NULL */);
+int ccal_propose_quads_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev,
+                           const int64_t* offsets /* [n_img + 1] */, const double* xy /* [.][2] */,
+                           double min_side, double max_side, double max_side_ratio, double offset, int samples, double min_contrast,
+                           int cap, int32_t* count_out /* [n_img] */, int32_t* flags_out /* [n_img] */,
+                           int32_t* idx_out /* [n_img][cap][4] */, double* quads_out /* [n_img][cap][4][2] or NULL */);
 
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
