@@ -66,7 +66,23 @@ class ModelConventions(C.Structure):
                 ("unproject_small_radius", C.c_double), ("ocv5_order", C.c_int32 * 5), ("reserved_", C.c_int32)]
 
 
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+class DetectTagsOpts(C.Structure):          # ccal_detect_tags_opts: every field is the stage parameter of that name
+    _fields_ = [
+        ("step", C.c_int32), ("nms_radius", C.c_int32), ("min_response", C.c_int64), ("rel_q10", C.c_int32), ("cand_cap", C.c_int32),
+        ("half_win", C.c_int32), ("max_iterations", C.c_int32), ("eps", C.c_double),
+        ("merge_radius", C.c_double),
+        ("min_side", C.c_double), ("max_side", C.c_double), ("max_side_ratio", C.c_double), ("offset", C.c_double),
+        ("edge_min_contrast", C.c_double), ("edge_samples", C.c_int32), ("quad_cap", C.c_int32),
+        ("border", C.c_int32), ("cell_samples", C.c_int32), ("tag_min_contrast", C.c_double),
+        ("max_border_errors", C.c_int32), ("max_hamming", C.c_int32),
+        ("tag_cap", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
+# bits of ccal_detect_tags_*'s flags_out: an out-edge list was cut; more candidates than cand_cap, quads than quad_cap, tags than tag_cap
+TAGS_FLAG_CUT, TAGS_FLAG_CAND_CAP, TAGS_FLAG_QUAD_CAP, TAGS_FLAG_TAG_CAP = 1, 2, 4, 8
+
+ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 LIB_PATH = os.environ.get("CCAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libccal_hip.so")
 
@@ -191,6 +207,11 @@ SYMBOLS = [
                                            C.c_double, C.c_int, C.c_double, C.c_int, _ip, _ip, _ip, _dp]),
     ("ccal_propose_quads_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _lp, _dp, C.c_double, C.c_double, C.c_double,
                                          C.c_double, C.c_int, C.c_double, C.c_int, _ip, _ip, _ip, _dp]),
+    # from pixels to detections: the four stages in one device-resident call
+    ("ccal_detect_tags_batch", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _up, C.c_int, C.POINTER(DetectTagsOpts),
+                                         _ip, _ip, _ip, _ip, _dp, _dp, _ip, _ip]),
+    ("ccal_detect_tags_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _up, C.c_int, C.POINTER(DetectTagsOpts),
+                                       _ip, _ip, _ip, _ip, _dp, _dp, _ip, _ip]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

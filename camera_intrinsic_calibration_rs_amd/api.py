@@ -28,6 +28,7 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   caller, quads not proposed here)                                      decode_tags, TagFamily
   what tag_detector.detect does for an AprilGrid image as a whole (this project's rules: saddles, their refinement, tag
   outlines from the saddles, the decoder)                               detect_aprilgrid, propose_quads, merge_points
+  the same up to the tags, in one device-resident call                  detect_tags (detect_aprilgrid(fused=True))
   a detector for plain checkerboards (the reference's tag detector is in the absent aprilgrid crate)
                                                                         detect_checkerboard, assemble_checkerboard
   (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
@@ -1185,10 +1186,26 @@ def propose_quads(images, xy_list, family: Optional[TagFamily] = None, border: i
     return [(quads, count, flags) for _, quads, count, flags in got]
 
 
+def detect_tags(images, family: TagFamily, step: int = 1, nms_radius: int = 5, rel_threshold: float = 0.1, half_win: int = 4,
+                min_side: float = 20.0, max_side: Optional[float] = None, min_contrast: float = 40.0, border: int = 1,
+                max_hamming: int = 2, ctx: Optional[Context] = None) -> List[List[Tuple[int, int, int, np.ndarray]]]:
+    """From images alone to the tags of `family` in each, in one device-resident call (ccal_detect_tags_batch: the image block is
+    uploaded once, no candidate, point or quad comes back to the host).  The parameters are detect_aprilgrid's and mean the same.
+    Returns what decode_tags returns for the quads of the staged chain, to the bit: per image the list of (tag_id, rot, hamming,
+    corners [4, 2]), ascending in tag_id."""
+    if not len(images):
+        return []
+    stack = _same_images("detect_tags", images)
+    got = _ctx(ctx).detect_tags_batch(stack, family.bits, family.codes, step, nms_radius, 1, rel_threshold, half_win=half_win,
+                                      min_side=min_side, max_side=max_side, edge_min_contrast=min_contrast, border=border,
+                                      tag_min_contrast=min_contrast, max_hamming=max_hamming)
+    return [[(int(t), int(r), int(h), c.copy()) for t, r, h, c in zip(ids, rot, ham, corners)] for ids, rot, ham, corners, *_ in got]
+
+
 def detect_aprilgrid(images, family: TagFamily, board: AprilGridBoard, step: int = 1, nms_radius: int = 5, rel_threshold: float = 0.1,
                      half_win: int = 4, min_side: float = 20.0, max_side: Optional[float] = None, min_contrast: float = 40.0,
                      border: int = 1, max_hamming: int = 2, times: Optional[Sequence[int]] = None, min_corners: int = 24,
-                     ctx: Optional[Context] = None) -> List[Optional[FrameFeature]]:
+                     ctx: Optional[Context] = None, fused: bool = False) -> List[Optional[FrameFeature]]:
     """From images alone to detections of an AprilGrid: the integer saddle detector over all images (ccal_detect_corners_batch), the
     sub-pixel refinement of its candidates (ccal_refine_corners_batch; candidates whose status is not CCAL_OK are dropped, the rest
     rounded through the f32 a FeaturePoint holds), merge_points, the quad proposer (ccal_propose_quads_batch, offset from the
@@ -1199,12 +1216,18 @@ def detect_aprilgrid(images, family: TagFamily, board: AprilGridBoard, step: int
     half_win 4 suits tags whose cells are 5 to 6 px: the window around a tag's outer corner has to hold the border cell and the
     gap square and little of the data cells.  min_contrast goes to BOTH the proposer (bright - dark along an edge) and the decoder
     (hi - lo over a tag's cells) and is in grey levels of the images' type: for uint16 images the caller scales it (by 257 when
-    they span the 16 bits); nothing here guesses the range from the pixels."""
+    they span the 16 bits); nothing here guesses the range from the pixels.
+    fused=True runs the same chain as ONE call that keeps every intermediate on the device (detect_tags) and gives the same
+    FrameFeatures; the default is the staged chain above."""
     if not len(images):
         return []
     stack = _same_images("detect_aprilgrid", images)
     H, W = stack.shape[1:]
     c = _ctx(ctx)
+    if fused:
+        decoded = detect_tags(list(stack), family, step, nms_radius, rel_threshold, half_win, min_side, max_side, min_contrast, border,
+                              max_hamming, ctx=c)
+        return frames_from_tags(decoded, board, (W, H), times, min_corners)
     found = c.detect_corners_batch(stack, step, nms_radius, 1, rel_threshold)
     xy, status, _, _ = c.refine_corners_batch(stack, [f[0].astype(np.float64) for f in found], half_win)
     points = [merge_points(np.float32(xy[k][status[k] == _ffi.OK]).astype(np.float64)) for k in range(len(stack))]

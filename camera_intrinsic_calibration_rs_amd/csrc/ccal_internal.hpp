@@ -421,4 +421,108 @@ void rccl_comm_abort(void* comm);
 // thread of its own; `inproc` (may be NULL) is aborted when a rank fails
 int solve_sharded_run(ccal_problem** shards, int n, const ccal_solver_opts* o, double* intr_io, double* const* poses_io,
                       double* extr_io, ccal_report* rep, InprocComm* inproc);
+
+// ---- from pixels to detections: the four stages on device buffers --------------------------------------------------------------------
+// Each stage's argument block, its parameter check (the message of the first range missed, or nullptr) and its launch sequence live
+// in the stage's own translation unit, which keeps its compiler flags; the stage's entry points and ccal_detect_tags_*
+// (ccal_kernels_tagchain.hip) enqueue through the same routines.  A routine only enqueues on `s` and returns hipGetLastError().
+// ccal_kernels_detect.hip
+struct DetectArgs {
+    const void* img;                    // [n][H][W] of T
+    int32_t W, H, n;                    // n: images of this chunk
+    int32_t s, r, rel_q10, cap;
+    int64_t min_response;
+    int32_t d0, dw, dh;                 // the domain: x in [d0, d0 + dw), y in [d0, d0 + dh)
+    int32_t nbx, nby;                   // its (r+1) x (r+1) blocks
+    int32_t* pix;                       // [n][nby * nbx]: y * W + x of the block's local maximum, -1: none
+    int32_t* hess;                      // [n][nby * nbx][3]
+    int64_t* resp;                      // [n][nby * nbx]
+    long long* rmax;                    // [n]: max(0, the largest R of the domain)
+    int32_t* rowoff;                    // [n][dh]: candidates of the image in front of the row
+    int32_t* count;                     // [n]
+    const int64_t* imgoff;              // [n + 1]: stored rows in front of the image
+    int32_t* oxy; int32_t* ohess; int64_t* oresp;       // the stored rows of the chunk, image after image
+};
+const char* detect_bad_params(int step, int nms_radius, int64_t min_response, int rel_q10, int cap);
+hipError_t detect_enqueue_find(hipStream_t s, int dtype, const DetectArgs& a);     // clears pix and rmax; tiles, rows: count[] is final
+hipError_t detect_enqueue_emit(hipStream_t s, const DetectArgs& a);               // the stored rows, once imgoff[] is there
+// ccal_kernels_corners.hip
+struct CornerArgs {
+    const void* img;                    // [n_img][H][W] of T
+    const int64_t* off;                 // [n_img + 1]
+    double* xy;                         // [n][2] in: start, out: result
+    int32_t* status; int32_t* iters;    // [n]
+    double* lam;                        // [n]
+    int64_t n;                          // corners in all
+    int32_t W, H, n_img;
+    int32_t h, max_it;
+    double eps;
+};
+const char* corners_bad_params(int half_win, int max_iterations, double eps);
+hipError_t corners_enqueue(hipStream_t s, int dtype, const CornerArgs& a);
+// ccal_kernels_quads.hip
+struct QuadArgs {
+    const void* img;                    // [n_img][H][W] of T, the chunk's first image first
+    const int64_t* off;                 // [n_img + 1]: the caller's offsets of the chunk's images (not rebased)
+    const double* xy;                   // [n][2], the chunk's first point first
+    int32_t* adj;                       // [n][CCAL_QUAD_MAX_OUT_EDGES]: out-edge lists, indices local to the image; slots past min(deg, 8) unwritten
+    int32_t* deg;                       // [n] full out-degree
+    int32_t* cnt;                       // [n] quads whose smallest corner is the point
+    const int32_t* base;                // [n] the rank, within its image, of the point's first quad (an exclusive scan of cnt)
+    const int64_t* rowoff;              // [n_img + 1] the first stored row of each image in oidx / oquads
+    int32_t* oidx;                      // [rows][4]
+    double* oquads;                     // [rows][4][2] or NULL
+    int64_t p0;                         // the caller's index of the chunk's first point = off[0]
+    int64_t n;                          // points in the chunk
+    int32_t W, H, n_img, K, cap;
+    double min2, max2, ratio2, offset, min_contrast;
+};
+constexpr int64_t kQuadMaxPoints = 32768;     // per image: the pair search is quadratic
+const char* quads_bad_params(double min_side, double max_side, double max_side_ratio, double offset, int samples, double min_contrast, int cap);
+void quads_set_params(QuadArgs& a, double min_side, double max_side, double max_side_ratio, double offset, int samples, double min_contrast, int cap);
+hipError_t quads_enqueue_count(hipStream_t s, int dtype, const QuadArgs& a);       // edges, then the count walk: adj, deg, cnt
+hipError_t quads_enqueue_write(hipStream_t s, const QuadArgs& a);                 // the stored rows, once base[] and rowoff[] are there
+// ccal_kernels_tags.hip
+struct TagArgs {
+    const void* img;                    // [n_img][H][W] of T, the chunk's first image first
+    const int64_t* off;                 // [n_img + 1]: the caller's offsets of the chunk's images (not rebased)
+    const double* quads;                // [n][4][2], the chunk's first quad first
+    const unsigned long long* codes;    // [n_codes]
+    int32_t* reason; int32_t* id; int32_t* rot; int32_t* hamming;      // [n]
+    double* corners;                    // [n][4][2]
+    unsigned long long* code;           // [n]
+    double* margin;                     // [n]
+    int64_t q0;                         // the caller's index of the chunk's first quad = off[0]
+    int64_t n;                          // quads in the chunk
+    int32_t W, H, n_img;
+    int32_t d, border, n_codes, S;
+    int32_t max_border, max_hamming;
+    double min_contrast;
+};
+const char* tags_bad_params(int d, int border, const uint64_t* codes, int n_codes, int samples, double min_contrast, int max_border_errors,
+                            int max_hamming);
+hipError_t tags_enqueue(hipStream_t s, int dtype, const TagArgs& a);
+// ccal_kernels_tagchain.hip: the two decision kernels of ccal_detect_tags_* on device arrays (the second library's test entry points
+// run them alone, ccal_test_hooks.hip)
+struct MergeArgs {
+    const int64_t* off;                 // [n_img + 1]: image k owns the points [off[k], off[k + 1]) of xy, status and out
+    const double* xy;                   // [.][2]
+    const int32_t* status;              // [.] only CCAL_OK goes on; NULL: every point does
+    double* out;                        // [.][2]: the kept points of image k from off[k] on, in order
+    int32_t* kept;                      // [n_img]
+    int32_t n_img, cap;                 // cap: the most points of one image (the walk's clamp)
+    double radius;
+};
+hipError_t tagchain_enqueue_merge(hipStream_t s, const MergeArgs& a);
+struct SelectArgs {
+    const int64_t* off;                 // [n_img + 1]: image k owns the rows [off[k], off[k + 1]) of the decoder's outputs
+    const int32_t* reason; const int32_t* id; const int32_t* rot; const int32_t* hamming;
+    const double* corners; const double* margin;
+    int32_t* win;                       // [.] work: 1 for the row that keeps its id
+    int32_t* count; int32_t* n_ok;      // [n_img]: distinct ids, CCAL_TAG_OK rows
+    int32_t* oid; int32_t* orot; int32_t* oham;         // [n_img][rows]
+    double* ocorners; double* omargin;  // [n_img][rows][4][2], [n_img][rows]
+    int32_t n_img, cap, rows;           // cap: the most quads of one image (the walk's clamp); rows: tags stored per image
+};
+hipError_t tagchain_enqueue_select(hipStream_t s, const SelectArgs& a);
 }  // namespace ccal

@@ -19,17 +19,7 @@ constexpr int kCornerWaves = 4;              // wavefronts (= corners in flight)
 constexpr int kCornerMaxHalf = 15;           // half_win 1 .. 15: a patch of at most 33 x 33 doubles per wavefront
 constexpr int kCornerWTab = 2 * kCornerMaxHalf + 2;      // the weight table's room per wavefront (31 used)
 
-struct CornerArgs {
-    const void* img;                    // [n_img][H][W] of T
-    const int64_t* off;                 // [n_img + 1]
-    double* xy;                         // [n][2] in: start, out: result
-    int32_t* status; int32_t* iters;    // [n]
-    double* lam;                        // [n]
-    int64_t n;                          // corners in all
-    int32_t W, H, n_img;
-    int32_t h, max_it;
-    double eps;
-};
+// CornerArgs: ccal_internal.hpp
 
 // producer and consumer are lanes of the same wavefront: LDS operations of one wave execute in order, this only keeps the compiler
 // from moving accesses across the hand-off
@@ -132,6 +122,22 @@ __global__ __launch_bounds__(64 * kCornerWaves) void k_corner_refine(const Corne
     }
 }
 
+const char* corners_bad_params(int half_win, int max_iterations, double eps) {
+    if (half_win < 1 || half_win > kCornerMaxHalf) return "half_win outside 1 .. 15";
+    if (max_iterations < 1) return "max_iterations < 1";
+    if (!(eps >= 0.0) || !std::isfinite(eps)) return "eps negative or not finite";
+    return nullptr;
+}
+
+hipError_t corners_enqueue(hipStream_t s, int dtype, const CornerArgs& a) {
+    const int ps = 2 * a.h + 3;
+    const size_t lds = sizeof(double) * (size_t)kCornerWaves * (size_t)(ps * ps + kCornerWTab);
+    const dim3 grid((unsigned)(((size_t)a.n + kCornerWaves - 1) / kCornerWaves));
+    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_corner_refine<uint16_t>, grid, dim3(64 * kCornerWaves), lds, s, a);
+    else hipLaunchKernelGGL(k_corner_refine<uint8_t>, grid, dim3(64 * kCornerWaves), lds, s, a);
+    return hipGetLastError();
+}
+
 namespace {
 
 int corners_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
@@ -139,9 +145,7 @@ int corners_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dt
                  int32_t* iters_out, double* lambda_min_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
-    if (half_win < 1 || half_win > kCornerMaxHalf) return bad("half_win outside 1 .. 15");
-    if (max_iterations < 1) return bad("max_iterations < 1");
-    if (!(eps >= 0.0) || !std::isfinite(eps)) return bad("eps negative or not finite");
+    if (const char* what = corners_bad_params(half_win, max_iterations, eps)) return bad(what);
     if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
     if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
     if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
@@ -172,14 +176,7 @@ int corners_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dt
     blk.upload(s_off, offsets, ni + 1);
     if (!images_on_device) blk.upload(s_img, images, b_img);
     blk.upload(s_xy, xy_io, 2 * n);
-    if (blk.ok()) {
-        const int ps = 2 * half_win + 3;
-        const size_t lds = sizeof(double) * (size_t)kCornerWaves * (size_t)(ps * ps + kCornerWTab);
-        const dim3 grid((unsigned)((n + kCornerWaves - 1) / kCornerWaves));
-        if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_corner_refine<uint16_t>, grid, dim3(64 * kCornerWaves), lds, ctx->stream, a);
-        else hipLaunchKernelGGL(k_corner_refine<uint8_t>, grid, dim3(64 * kCornerWaves), lds, ctx->stream, a);
-        blk.launched();
-    }
+    if (blk.ok()) blk.note(corners_enqueue(ctx->stream, dtype, a));
     blk.download(xy_io, a.xy, 2 * n);
     blk.download(status_out, a.status, n);
     blk.download(iters_out, a.iters, n);

@@ -35,22 +35,7 @@ inline size_t det_chunk_bytes() {
 }
 constexpr int64_t kDetNone = INT64_MIN;       // R of a pixel outside the domain: it never competes
 
-struct DetectArgs {
-    const void* img;                    // [n][H][W] of T
-    int32_t W, H, n;                    // n: images of this chunk
-    int32_t s, r, rel_q10, cap;
-    int64_t min_response;
-    int32_t d0, dw, dh;                 // the domain: x in [d0, d0 + dw), y in [d0, d0 + dh)
-    int32_t nbx, nby;                   // its (r+1) x (r+1) blocks
-    int32_t* pix;                       // [n][nby * nbx]: y * W + x of the block's local maximum, -1: none
-    int32_t* hess;                      // [n][nby * nbx][3]
-    int64_t* resp;                      // [n][nby * nbx]
-    long long* rmax;                    // [n]: max(0, the largest R of the domain)
-    int32_t* rowoff;                    // [n][dh]: candidates of the image in front of the row
-    int32_t* count;                     // [n]
-    const int64_t* imgoff;              // [n + 1]: stored rows in front of the image
-    int32_t* oxy; int32_t* ohess; int64_t* oresp;       // the stored rows of the chunk, image after image
-};
+// DetectArgs: ccal_internal.hpp
 
 __host__ __device__ inline size_t det_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 // LDS of k_detect_tiles: S [SW][SW] int32 | a union of { Hs [IW][SW] int32, I [IW][IW] u16 } and R [RW][RW] int64
@@ -218,6 +203,33 @@ __global__ __launch_bounds__(kDetThreads) void k_detect_emit(const DetectArgs a)
     });
 }
 
+const char* detect_bad_params(int step, int nms_radius, int64_t min_response, int rel_q10, int cap) {
+    if (step < 1 || step > kDetMaxStep) return "step outside 1 .. 4";
+    if (nms_radius < 1 || nms_radius > kDetMaxRadius) return "nms_radius outside 1 .. 15";
+    if (min_response < 1) return "min_response < 1";
+    if (rel_q10 < 0 || rel_q10 > 1024) return "rel_q10 outside 0 .. 1024";
+    if (cap < 1) return "cap < 1";
+    return nullptr;
+}
+
+hipError_t detect_enqueue_find(hipStream_t s, int dtype, const DetectArgs& a) {
+    const size_t nb = (size_t)a.nbx * (size_t)a.nby, m = (size_t)a.n;
+    hipError_t e = hipMemsetAsync(a.pix, 0xFF, nb * m * sizeof(int32_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.rmax, 0, m * sizeof(long long), s);
+    if (e != hipSuccess) return e;
+    const size_t lds = det_lds_bytes(a.s, a.r);
+    const dim3 grid((unsigned)((a.dw + kDetTile - 1) / kDetTile), (unsigned)((a.dh + kDetTile - 1) / kDetTile), (unsigned)m);
+    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_detect_tiles<uint16_t>, grid, dim3(kDetThreads), lds, s, a);
+    else hipLaunchKernelGGL(k_detect_tiles<uint8_t>, grid, dim3(kDetThreads), lds, s, a);
+    hipLaunchKernelGGL(k_detect_rows, dim3((unsigned)m), dim3(kDetThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t detect_enqueue_emit(hipStream_t s, const DetectArgs& a) {
+    hipLaunchKernelGGL(k_detect_emit, dim3((unsigned)((a.dh + kDetThreads - 1) / kDetThreads), (unsigned)a.n), dim3(kDetThreads), 0, s, a);
+    return hipGetLastError();
+}
+
 namespace {
 
 int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
@@ -225,11 +237,7 @@ int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dty
                 int32_t* hess_out, int64_t* response_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
-    if (step < 1 || step > kDetMaxStep) return bad("step outside 1 .. 4");
-    if (nms_radius < 1 || nms_radius > kDetMaxRadius) return bad("nms_radius outside 1 .. 15");
-    if (min_response < 1) return bad("min_response < 1");
-    if (rel_q10 < 0 || rel_q10 > 1024) return bad("rel_q10 outside 0 .. 1024");
-    if (cap < 1) return bad("cap < 1");
+    if (const char* what = detect_bad_params(step, nms_radius, min_response, rel_q10, cap)) return bad(what);
     if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
     if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
     if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
@@ -268,8 +276,6 @@ int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dty
     a.pix = blk.at(s_pix); a.hess = blk.at(s_hess); a.resp = blk.at(s_resp); a.rmax = blk.at(s_rmax);
     a.rowoff = blk.at(s_rowoff); a.count = blk.at(s_count); a.imgoff = blk.at(s_imgoff);
     a.oxy = blk.at(s_oxy); a.ohess = blk.at(s_ohess); a.oresp = blk.at(s_oresp);
-    const size_t lds = det_lds_bytes(step, r);
-    const unsigned tiles_x = (unsigned)((dw + kDetTile - 1) / kDetTile), tiles_y = (unsigned)((dh + kDetTile - 1) / kDetTile);
     std::vector<int64_t> imgoff(nc + 1);
     std::vector<int32_t> h_xy, h_hess;
     std::vector<int64_t> h_resp;
@@ -280,16 +286,8 @@ int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dty
         a.img = images_on_device ? (const void*)(static_cast<const char*>(images) + k0 * img_bytes) : (const void*)blk.at(s_img);
         blk.poison(s_hess, s_resp);                    // the test hook's 0xFF over what the kernels write before they read it:
         blk.poison(s_oxy, s_oresp);                    // the slots' payload and the stored rows (not the indices, counts and offsets)
-        blk.memset(s_pix, 0xFF, nb * m);
-        blk.memset(s_rmax, 0, m);
         if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
-        if (blk.ok()) {
-            const dim3 grid(tiles_x, tiles_y, (unsigned)m);
-            if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_detect_tiles<uint16_t>, grid, dim3(kDetThreads), lds, ctx->stream, a);
-            else hipLaunchKernelGGL(k_detect_tiles<uint8_t>, grid, dim3(kDetThreads), lds, ctx->stream, a);
-            hipLaunchKernelGGL(k_detect_rows, dim3((unsigned)m), dim3(kDetThreads), 0, ctx->stream, a);
-            blk.launched();
-        }
+        if (blk.ok()) blk.note(detect_enqueue_find(ctx->stream, dtype, a));
         blk.download(count_out + k0, a.count, m);
         if (blk.ok()) blk.note(hipStreamSynchronize(ctx->stream));
         if (!blk.ok()) break;
@@ -298,11 +296,7 @@ int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dty
         const size_t total = (size_t)imgoff[m];
         if (!total) continue;
         blk.upload(s_imgoff, imgoff.data(), m + 1);
-        if (blk.ok()) {
-            hipLaunchKernelGGL(k_detect_emit, dim3((unsigned)((dh + kDetThreads - 1) / kDetThreads), (unsigned)m), dim3(kDetThreads), 0,
-                               ctx->stream, a);
-            blk.launched();
-        }
+        if (blk.ok()) blk.note(detect_enqueue_emit(ctx->stream, a));
         h_xy.resize(2 * total); h_hess.resize(3 * total);
         if (response_out) h_resp.resize(total);
         blk.download(h_xy.data(), a.oxy, 2 * total);

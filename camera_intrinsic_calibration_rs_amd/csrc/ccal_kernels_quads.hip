@@ -27,7 +27,6 @@ namespace ccal {
 constexpr int kQuadWaves = 4;                 // wavefronts (= points A in flight) per workgroup
 constexpr int kQuadMaxOut = CCAL_QUAD_MAX_OUT_EDGES;
 constexpr int kQuadMaxSamples = 16;
-constexpr int64_t kQuadMaxPoints = 32768;     // per image: the pair search is quadratic
 constexpr size_t kQuadChunkBytes = (size_t)256 << 20;     // the block one launch should need: larger batches go image chunk by chunk
 static_assert(kQuadMaxOut == 8, "a pass of 64 lanes is one i and all (j, k)");
 // the second library only (-DCCAL_TEST_HOOKS): CCAL_TEST_QUADS_CHUNK_BYTES replaces the limit, so that a test cuts a small batch
@@ -39,22 +38,7 @@ inline size_t quad_chunk_bytes() {
     return kQuadChunkBytes;
 }
 
-struct QuadArgs {
-    const void* img;                    // [n_img][H][W] of T, the chunk's first image first
-    const int64_t* off;                 // [n_img + 1]: the caller's offsets of the chunk's images (not rebased)
-    const double* xy;                   // [n][2], the chunk's first point first
-    int32_t* adj;                       // [n][kQuadMaxOut]: out-edge lists, indices local to the image; slots past min(deg, 8) unwritten
-    int32_t* deg;                       // [n] full out-degree
-    int32_t* cnt;                       // [n] quads whose smallest corner is the point
-    const int32_t* base;                // [n] the rank, within its image, of the point's first quad (written by the host)
-    const int64_t* rowoff;              // [n_img + 1] the first stored row of each image in oidx / oquads
-    int32_t* oidx;                      // [rows][4]
-    double* oquads;                     // [rows][4][2] or NULL
-    int64_t p0;                         // the caller's index of the chunk's first point = off[0]
-    int64_t n;                          // points in the chunk
-    int32_t W, H, n_img, K, cap;
-    double min2, max2, ratio2, offset, min_contrast;
-};
+// QuadArgs: ccal_internal.hpp
 
 // the point of wavefront g: its image k (the last with off[k] <= p0 + g; images without points are stepped over), the chunk
 // index of the image's first point, the image's point count
@@ -201,6 +185,38 @@ __global__ __launch_bounds__(64 * kQuadWaves) void k_quad_chains(const QuadArgs 
     if (!kWrite && lane == 0) a.cnt[g] = run;
 }
 
+const char* quads_bad_params(double min_side, double max_side, double max_side_ratio, double offset, int samples, double min_contrast, int cap) {
+    if (!(min_side >= 1.0)) return "min_side < 1";
+    if (!(max_side >= min_side)) return "max_side < min_side";
+    if (!(max_side_ratio >= 1.0)) return "max_side_ratio < 1";
+    if (!(offset > 0.0 && offset <= 0.25)) return "offset outside (0, 0.25]";
+    if (samples < 1 || samples > kQuadMaxSamples) return "samples outside 1 .. 16";
+    if (!(min_contrast >= 0.0) || !std::isfinite(min_contrast)) return "min_contrast negative or not finite";
+    if (cap < 1) return "cap < 1";
+    return nullptr;
+}
+
+// the squares are formed here, in the unit without fused multiply-adds, for every caller alike
+void quads_set_params(QuadArgs& a, double min_side, double max_side, double max_side_ratio, double offset, int samples, double min_contrast, int cap) {
+    a.K = samples; a.cap = cap;
+    a.min2 = min_side * min_side; a.max2 = max_side * max_side; a.ratio2 = max_side_ratio * max_side_ratio;
+    a.offset = offset; a.min_contrast = min_contrast;
+}
+
+hipError_t quads_enqueue_count(hipStream_t s, int dtype, const QuadArgs& a) {
+    const dim3 grid((unsigned)(((size_t)a.n + kQuadWaves - 1) / kQuadWaves)), block(64 * kQuadWaves);
+    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_quad_edges<uint16_t>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_quad_edges<uint8_t>, grid, block, 0, s, a);
+    hipLaunchKernelGGL(k_quad_chains<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t quads_enqueue_write(hipStream_t s, const QuadArgs& a) {
+    const dim3 grid((unsigned)(((size_t)a.n + kQuadWaves - 1) / kQuadWaves)), block(64 * kQuadWaves);
+    hipLaunchKernelGGL(k_quad_chains<true>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
 namespace {
 
 int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
@@ -208,13 +224,7 @@ int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtyp
                int samples, double min_contrast, int cap, int32_t* count_out, int32_t* flags_out, int32_t* idx_out, double* quads_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
-    if (!(min_side >= 1.0)) return bad("min_side < 1");
-    if (!(max_side >= min_side)) return bad("max_side < min_side");
-    if (!(max_side_ratio >= 1.0)) return bad("max_side_ratio < 1");
-    if (!(offset > 0.0 && offset <= 0.25)) return bad("offset outside (0, 0.25]");
-    if (samples < 1 || samples > kQuadMaxSamples) return bad("samples outside 1 .. 16");
-    if (!(min_contrast >= 0.0) || !std::isfinite(min_contrast)) return bad("min_contrast negative or not finite");
-    if (cap < 1) return bad("cap < 1");
+    if (const char* what = quads_bad_params(min_side, max_side, max_side_ratio, offset, samples, min_contrast, cap)) return bad(what);
     if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
     if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
     if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
@@ -254,9 +264,8 @@ int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtyp
     QuadArgs a = {};
     a.off = blk.at(s_off); a.rowoff = blk.at(s_rowoff); a.xy = blk.at(s_xy);
     a.adj = blk.at(s_adj); a.deg = blk.at(s_deg); a.cnt = blk.at(s_cnt); a.base = blk.at(s_base);
-    a.W = width; a.H = height; a.K = samples; a.cap = cap;
-    a.min2 = min_side * min_side; a.max2 = max_side * max_side; a.ratio2 = max_side_ratio * max_side_ratio;
-    a.offset = offset; a.min_contrast = min_contrast;
+    a.W = width; a.H = height;
+    quads_set_params(a, min_side, max_side, max_side_ratio, offset, samples, min_contrast, cap);
     std::vector<int32_t> h_deg(max_pts), h_cnt(max_pts), h_base(max_pts), h_idx;
     std::vector<int64_t> rowoff(max_img + 1);
     std::vector<double> h_quads;
@@ -267,16 +276,10 @@ int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtyp
         if (!np) continue;
         a.n_img = (int32_t)m; a.p0 = offsets[k0]; a.n = (int64_t)np;
         a.img = images_on_device ? (const void*)(static_cast<const char*>(images) + k0 * img_bytes) : (const void*)blk.at(s_img);
-        const dim3 grid((unsigned)((np + kQuadWaves - 1) / kQuadWaves)), block(64 * kQuadWaves);
         blk.upload(s_off, offsets + k0, m + 1);
         if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
         blk.upload(s_xy, xy + 2 * at, 2 * np);
-        if (blk.ok()) {
-            if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_quad_edges<uint16_t>, grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL(k_quad_edges<uint8_t>, grid, block, 0, ctx->stream, a);
-            hipLaunchKernelGGL(k_quad_chains<false>, grid, block, 0, ctx->stream, a);
-            blk.launched();
-        }
+        if (blk.ok()) blk.note(quads_enqueue_count(ctx->stream, dtype, a));
         blk.download(h_deg.data(), a.deg, np);
         blk.download(h_cnt.data(), a.cnt, np);
         if (blk.ok()) blk.note(hipStreamSynchronize(ctx->stream));
@@ -309,10 +312,7 @@ int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtyp
         blk.upload(s_base, h_base.data(), np);
         blk.upload(s_rowoff, rowoff.data(), m + 1);
         if (!blk.ok()) break;                             // no launch: nothing of the unwritten rows reaches the caller's arrays
-        if (rows.ok()) {
-            hipLaunchKernelGGL(k_quad_chains<true>, grid, block, 0, ctx->stream, a);
-            rows.launched();
-        }
+        if (rows.ok()) rows.note(quads_enqueue_write(ctx->stream, a));
         h_idx.resize(4 * total);
         if (quads_out) h_quads.resize(8 * total);
         rows.download(h_idx.data(), a.oidx, 4 * total);

@@ -37,22 +37,7 @@ inline size_t tag_chunk_bytes() {
     return kTagChunkBytes;
 }
 
-struct TagArgs {
-    const void* img;                    // [n_img][H][W] of T, the chunk's first image first
-    const int64_t* off;                 // [n_img + 1]: the caller's offsets of the chunk's images (not rebased)
-    const double* quads;                // [n][4][2], the chunk's first quad first
-    const unsigned long long* codes;    // [n_codes]
-    int32_t* reason; int32_t* id; int32_t* rot; int32_t* hamming;      // [n]
-    double* corners;                    // [n][4][2]
-    unsigned long long* code;           // [n]
-    double* margin;                     // [n]
-    int64_t q0;                         // the caller's index of the chunk's first quad = off[0]
-    int64_t n;                          // quads in the chunk
-    int32_t W, H, n_img;
-    int32_t d, border, n_codes, S;
-    int32_t max_border, max_hamming;
-    double min_contrast;
-};
+// TagArgs: ccal_internal.hpp
 
 // floor and fraction of one coordinate, the two neighbour indices clamped to [0, n - 1]
 __device__ __forceinline__ void tag_tap(double x, int32_t n, int32_t& i0, int32_t& i1, double& ax) {
@@ -233,6 +218,30 @@ __global__ __launch_bounds__(64 * kTagWaves) void k_decode_tags(const TagArgs a)
     }
 }
 
+// codes == nullptr: the ranges alone (the entry points check them before the image arguments, the table after)
+const char* tags_bad_params(int d, int border, const uint64_t* codes, int n_codes, int samples, double min_contrast, int max_border_errors,
+                            int max_hamming) {
+    if (d < 3 || d > 8) return "d outside 3 .. 8";
+    if (border < 1 || border > 2) return "border outside 1 .. 2";
+    if (n_codes < 1) return "n_codes < 1";
+    if (samples < 1 || samples > 4) return "samples outside 1 .. 4";
+    if (!(min_contrast >= 0.0) || !std::isfinite(min_contrast)) return "min_contrast negative or not finite";
+    if (max_border_errors < 0) return "max_border_errors < 0";
+    if (max_hamming < 0 || max_hamming > d * d) return "max_hamming outside 0 .. d * d";
+    if (codes && d * d < 64)                              // at d = 8 every uint64 is a code: nothing to test, and no shift by 64
+        for (int i = 0; i < n_codes; ++i)
+            if (codes[i] >> (d * d)) return "a code of more than d * d bits";
+    return nullptr;
+}
+
+hipError_t tags_enqueue(hipStream_t s, int dtype, const TagArgs& a) {
+    static_assert(kTagMaxSide * kTagMaxSide <= 64 * kTagCellChunks, "three cells per lane hold the largest grid");
+    const dim3 grid((unsigned)(((size_t)a.n + kTagWaves - 1) / kTagWaves));
+    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_decode_tags<uint16_t>, grid, dim3(64 * kTagWaves), 0, s, a);
+    else hipLaunchKernelGGL(k_decode_tags<uint8_t>, grid, dim3(64 * kTagWaves), 0, s, a);
+    return hipGetLastError();
+}
+
 namespace {
 
 int tags_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
@@ -241,27 +250,17 @@ int tags_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype
               int32_t* hamming_out, double* corners_out, uint64_t* code_out, double* margin_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
-    if (d < 3 || d > 8) return bad("d outside 3 .. 8");
-    if (border < 1 || border > 2) return bad("border outside 1 .. 2");
-    if (n_codes < 1) return bad("n_codes < 1");
-    if (samples < 1 || samples > 4) return bad("samples outside 1 .. 4");
-    if (!(min_contrast >= 0.0) || !std::isfinite(min_contrast)) return bad("min_contrast negative or not finite");
-    if (max_border_errors < 0) return bad("max_border_errors < 0");
-    if (max_hamming < 0 || max_hamming > d * d) return bad("max_hamming outside 0 .. d * d");
+    if (const char* what = tags_bad_params(d, border, nullptr, n_codes, samples, min_contrast, max_border_errors, max_hamming)) return bad(what);
     if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
     if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
     if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
-    if (codes && d * d < 64)                              // at d = 8 every uint64 is a code: nothing to test, and no shift by 64
-        for (int i = 0; i < n_codes; ++i)
-            if (codes[i] >> (d * d)) return bad("a code of more than d * d bits");
+    if (const char* what = tags_bad_params(d, border, codes, n_codes, samples, min_contrast, max_border_errors, max_hamming)) return bad(what);
     if (n_img == 0) return CCAL_OK;
     if (!images || !offsets || !codes || !reason_out || !id_out || !rot_out || !hamming_out) return bad("NULL argument");
     if (check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
     if (offsets[n_img] > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 quads");
     if (offsets[n_img] == 0) return CCAL_OK;
     if (!quads) return bad("NULL argument");
-    static_assert(kTagMaxSide * kTagMaxSide <= 64 * kTagCellChunks, "three cells per lane hold the largest grid");
-
     // chunks of whole images: as many as keep the chunk's images (host call), quads and outputs within the limit, at least one
     const size_t ni = (size_t)n_img, img_bytes = (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height;
     const size_t per_quad = 8 * sizeof(double) + 4 * sizeof(int32_t) + 8 * sizeof(double) + sizeof(uint64_t) + sizeof(double);
@@ -313,12 +312,7 @@ int tags_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype
         blk.upload(s_off, offsets + k0, m + 1);
         if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
         blk.upload(s_quads, quads + 8 * at, 8 * nq);
-        if (blk.ok()) {
-            const dim3 grid((unsigned)((nq + kTagWaves - 1) / kTagWaves));
-            if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_decode_tags<uint16_t>, grid, dim3(64 * kTagWaves), 0, ctx->stream, a);
-            else hipLaunchKernelGGL(k_decode_tags<uint8_t>, grid, dim3(64 * kTagWaves), 0, ctx->stream, a);
-            blk.launched();
-        }
+        if (blk.ok()) blk.note(tags_enqueue(ctx->stream, dtype, a));
         blk.download(reason_out + at, a.reason, nq);
         blk.download(id_out + at, a.id, nq);
         blk.download(rot_out + at, a.rot, nq);

@@ -1,0 +1,55 @@
+// How ccal_detect_tags_* sizes its device block and cuts a batch into chunks of whole images: plain arithmetic, no context and no HIP
+// include, so that a plain C++ program can hold it to the groupings the tests rely on (tests/cpp/test_tagchain_plan.cpp,
+// tests/test_detect_tags_cpu.py).  The counts of an image are not known before its stages have run, so the bound per image comes from
+// the caps alone, each cut to what the image's size allows; every image of a call has the same bound, and a chunk is a fixed number
+// of images.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+namespace ccal {
+
+// device bytes per row of each kind:
+//   slot       the detector's (r+1) x (r+1) blocks: pix 4 | hess 12 | resp 8
+//   candidate  the detector's stored row 28 (xy 8, hess 12, resp 8) | start / refined xy 16, lambda 8, status 4, iterations 4 |
+//              merged xy 16 | compacted point 16 | out-edge list 32, degree, count, base 12
+//   quad       indices 16, coordinates 64 | decoded corners 64, margin 8, code 8, reason, id, rot, hamming 16 | the selection's mark 4
+//   tag        id, rot, hamming 12 | corners 64 | margin 8
+//   image      the detector's Rmax 8 and count 4, three offsets 24, kept / quads / flags / tags / OK quads 20 - rounded up to 64
+constexpr size_t kChainPerSlotBytes = 24, kChainPerCandBytes = 136, kChainPerQuadBytes = 180, kChainPerTagBytes = 84, kChainPerImageBytes = 64;
+constexpr size_t kChainMaxImages = 65535;        // a grid's y and z extents
+constexpr size_t kChainQuadsPerPoint = 512;      // 8^3 chains start at a point
+
+struct ChainShape {
+    size_t img_bytes = 0;          // one image
+    size_t dw = 0, dh = 0;         // the detector's domain; 0 x 0: none, the call has nothing to launch
+    size_t slots = 0;              // its (r+1) x (r+1) blocks = the most candidates an image can have
+    size_t cand = 0, quads = 0, tags = 0;        // rows per image: the caps, each cut to what can occur
+};
+
+inline ChainShape chain_shape(size_t width, size_t height, size_t itemsize, size_t step, size_t r, size_t cand_cap, size_t quad_cap,
+                              size_t tag_cap, size_t n_codes) {
+    ChainShape s;
+    s.img_bytes = itemsize * width * height;
+    const size_t d0 = step + 2;
+    if (width <= 2 * d0 || height <= 2 * d0) return s;
+    s.dw = width - 2 * d0; s.dh = height - 2 * d0;
+    s.slots = ((s.dw + r) / (r + 1)) * ((s.dh + r) / (r + 1));
+    s.cand = std::min(cand_cap, s.slots);
+    s.quads = std::min(quad_cap, kChainQuadsPerPoint * s.cand);
+    s.tags = std::min(tag_cap, std::min(s.quads, n_codes));          // an image's tags have distinct ids
+    return s;
+}
+
+inline size_t chain_per_image_bytes(bool images_on_device, const ChainShape& s) {
+    return (images_on_device ? 0 : s.img_bytes) + s.slots * kChainPerSlotBytes + s.dh * 4 + s.cand * kChainPerCandBytes +
+           s.quads * kChainPerQuadBytes + s.tags * kChainPerTagBytes + kChainPerImageBytes;
+}
+
+// images per chunk: as many as keep the chunk within `limit` bytes, at least one
+inline size_t chain_images_per_chunk(size_t n_img, size_t per_image, size_t limit) {
+    return std::min(std::min(n_img, kChainMaxImages), std::max<size_t>(limit / per_image, 1));
+}
+
+}  // namespace ccal

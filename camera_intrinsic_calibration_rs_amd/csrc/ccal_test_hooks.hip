@@ -79,4 +79,101 @@ extern "C" int ccal_test_device_math(ccal_ctx* ctx, int op, int64_t n, const dou
     return CCAL_OK;
     CCAL_API_CATCH(ctx)
 }
+
+// The two decision kernels of ccal_detect_tags_* alone, on arrays of the tests' choice (tests/test_gpu_detect_tags.py).  The output
+// arrays go to the device as the caller filled them and come back whole: what a kernel does not write keeps the caller's value.
+namespace {
+int hook_offsets(ccal_ctx* ctx, const char* where, int n_img, const int64_t* offsets, size_t* most) {
+    if (n_img < 1 || !offsets) return ccal::fail(ctx, CCAL_ERR_INVALID_ARG, "a test hook: n_img >= 1 and offsets");
+    if (ccal::check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
+    if (offsets[n_img] > (int64_t)INT32_MAX) return ccal::fail(ctx, CCAL_ERR_INVALID_ARG, "a test hook: more than 2^31 - 1 rows");
+    *most = 0;
+    for (int k = 0; k < n_img; ++k) *most = std::max(*most, (size_t)(offsets[k + 1] - offsets[k]));
+    return CCAL_OK;
+}
+}  // namespace
+
+// image k owns the points [offsets[k], offsets[k + 1]); status NULL: every point goes on.  kept_out [n_img]; xy_out [.][2]: the kept
+// points of image k from offsets[k] on
+extern "C" int ccal_test_merge_points(ccal_ctx* ctx, int n_img, const int64_t* offsets, const double* xy, const int32_t* status,
+                                      double radius, int32_t* kept_out, double* xy_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    const char* where = "ccal_test_merge_points";
+    size_t most = 0;
+    if (const int rc = hook_offsets(ctx, where, n_img, offsets, &most)) return rc;
+    if (!kept_out || !(radius >= 0.0)) return ccal::fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_test_merge_points: kept_out and a radius >= 0");
+    const size_t n = (size_t)offsets[n_img], ni = (size_t)n_img;
+    if (n && (!xy || !xy_out)) return ccal::fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_test_merge_points: both point arrays");
+    ccal::CallBlock blk(ctx);
+    const auto s_off = blk.add<int64_t>(ni + 1);
+    const auto s_status = blk.add<int32_t>(status ? n : 0);
+    const auto s_kept = blk.add<int32_t>(ni);
+    const auto s_xy = blk.add<double>(2 * n);
+    const auto s_out = blk.add<double>(2 * n);
+    if (!blk.alloc()) return blk.finish(where);
+    blk.upload(s_off, offsets, ni + 1);
+    if (status) blk.upload(s_status, status, n);
+    blk.upload(s_xy, xy, 2 * n);
+    blk.upload(s_out, xy_out, 2 * n);
+    ccal::MergeArgs a = {};
+    a.off = blk.at(s_off); a.xy = blk.at(s_xy); a.status = blk.at(s_status); a.out = blk.at(s_out); a.kept = blk.at(s_kept);
+    a.n_img = n_img; a.cap = (int32_t)most; a.radius = radius;
+    if (blk.ok()) blk.note(ccal::tagchain_enqueue_merge(ctx->stream, a));
+    blk.download(kept_out, a.kept, ni);
+    blk.download(xy_out, a.out, 2 * n);
+    return blk.finish(where);
+    CCAL_API_CATCH(ctx)
+}
+
+// image k owns the decoder's rows [offsets[k], offsets[k + 1]); outputs [n_img] and [n_img][rows]
+extern "C" int ccal_test_select_tags(ccal_ctx* ctx, int n_img, const int64_t* offsets, const int32_t* reason, const int32_t* id,
+                                     const int32_t* rot, const int32_t* hamming, const double* corners, const double* margin, int rows,
+                                     int32_t* count_out, int32_t* n_ok_out, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out,
+                                     double* corners_out, double* margin_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    const char* where = "ccal_test_select_tags";
+    size_t most = 0;
+    if (const int rc = hook_offsets(ctx, where, n_img, offsets, &most)) return rc;
+    const size_t n = (size_t)offsets[n_img], ni = (size_t)n_img;
+    if (rows < 1 || !count_out || !n_ok_out || !id_out || !rot_out || !hamming_out || !corners_out || !margin_out ||
+        (n && (!reason || !id || !rot || !hamming || !corners || !margin)))
+        return ccal::fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_test_select_tags: rows >= 1 and every array");
+    const size_t t = (size_t)rows * ni;
+    ccal::CallBlock blk(ctx);
+    const auto s_off = blk.add<int64_t>(ni + 1);
+    const auto s_reason = blk.add<int32_t>(n);
+    const auto s_id = blk.add<int32_t>(n);
+    const auto s_rot = blk.add<int32_t>(n);
+    const auto s_ham = blk.add<int32_t>(n);
+    const auto s_win = blk.add<int32_t>(n);
+    const auto s_count = blk.add<int32_t>(ni);
+    const auto s_nok = blk.add<int32_t>(ni);
+    const auto s_oid = blk.add<int32_t>(t);
+    const auto s_orot = blk.add<int32_t>(t);
+    const auto s_oham = blk.add<int32_t>(t);
+    const auto s_corners = blk.add<double>(8 * n);
+    const auto s_margin = blk.add<double>(n);
+    const auto s_ocorners = blk.add<double>(8 * t);
+    const auto s_omargin = blk.add<double>(t);
+    if (!blk.alloc()) return blk.finish(where);
+    blk.upload(s_off, offsets, ni + 1);
+    blk.upload(s_reason, reason, n); blk.upload(s_id, id, n); blk.upload(s_rot, rot, n); blk.upload(s_ham, hamming, n);
+    blk.upload(s_corners, corners, 8 * n); blk.upload(s_margin, margin, n);
+    blk.upload(s_oid, id_out, t); blk.upload(s_orot, rot_out, t); blk.upload(s_oham, hamming_out, t);
+    blk.upload(s_ocorners, corners_out, 8 * t); blk.upload(s_omargin, margin_out, t);
+    ccal::SelectArgs a = {};
+    a.off = blk.at(s_off); a.reason = blk.at(s_reason); a.id = blk.at(s_id); a.rot = blk.at(s_rot); a.hamming = blk.at(s_ham);
+    a.corners = blk.at(s_corners); a.margin = blk.at(s_margin); a.win = blk.at(s_win); a.count = blk.at(s_count); a.n_ok = blk.at(s_nok);
+    a.oid = blk.at(s_oid); a.orot = blk.at(s_orot); a.oham = blk.at(s_oham); a.ocorners = blk.at(s_ocorners); a.omargin = blk.at(s_omargin);
+    a.n_img = n_img; a.cap = (int32_t)most; a.rows = rows;
+    if (blk.ok()) blk.note(ccal::tagchain_enqueue_select(ctx->stream, a));
+    blk.download(count_out, a.count, ni);
+    blk.download(n_ok_out, a.n_ok, ni);
+    blk.download(id_out, a.oid, t); blk.download(rot_out, a.orot, t); blk.download(hamming_out, a.oham, t);
+    blk.download(corners_out, a.ocorners, 8 * t); blk.download(margin_out, a.omargin, t);
+    return blk.finish(where);
+    CCAL_API_CATCH(ctx)
+}
 #endif

@@ -477,6 +477,86 @@ class Context:
         return self._quads(self.lib.ccal_propose_quads_dev, "ccal_propose_quads_dev", images_ptr, dtype, width, height, n_img, xy_list,
                            min_side, max_side, max_side_ratio, offset, samples, min_contrast, max_per_image)
 
+    # -- from pixels to detections: the four stages in one device-resident call (ccal_detect_tags_batch, ccal_kernels_tagchain.hip) ----
+    def _detect_tags(self, fn, where, ptr, dtype, width, height, n_img, family_bits, codes, step, nms_radius, min_response, rel_threshold,
+                     max_candidates, half_win, max_iterations, eps, merge_radius, min_side, max_side, max_side_ratio, offset,
+                     edge_samples, edge_min_contrast, max_quads, border, cell_samples, tag_min_contrast, max_border_errors, max_hamming,
+                     max_tags):
+        if not np.isfinite(rel_threshold):
+            raise ValueError(f"{where}: rel_threshold is not finite")
+        d = int(round(max(float(family_bits), 0.0) ** 0.5))
+        if d * d != int(family_bits):
+            raise ValueError(f"{where}: family_bits is not a square")
+        codes = np.ascontiguousarray(np.asarray([int(c) for c in codes], dtype=np.uint64))
+        if max_side is None:
+            max_side = max(int(width), int(height)) / 2.0
+        if offset is None:
+            offset = 1.0 / (2.0 * (d + 2 * int(border)))
+        if max_tags is None:
+            max_tags = max(len(codes), 1)              # an image's tags have distinct ids
+        o = _ffi.DetectTagsOpts(
+            step=int(step), nms_radius=int(nms_radius), min_response=int(min_response), rel_q10=int(round(1024.0 * float(rel_threshold))),
+            cand_cap=int(max_candidates), half_win=int(half_win), max_iterations=int(max_iterations), eps=float(eps),
+            merge_radius=float(merge_radius), min_side=float(min_side), max_side=float(max_side), max_side_ratio=float(max_side_ratio),
+            offset=float(offset), edge_min_contrast=float(edge_min_contrast), edge_samples=int(edge_samples), quad_cap=int(max_quads),
+            border=int(border), cell_samples=int(cell_samples), tag_min_contrast=float(tag_min_contrast),
+            max_border_errors=int(max_border_errors), max_hamming=int(max_hamming), tag_cap=int(max_tags))
+        m, rows = max(int(n_img), 1), max(int(max_tags), 1)
+        count = np.zeros(m, dtype=np.int32); flags = np.zeros(m, dtype=np.int32); stats = np.zeros((m, 4), dtype=np.int32)
+        tag_id = np.full((m, rows), -2, dtype=np.int32); rot = np.full((m, rows), -2, dtype=np.int32)
+        hamming = np.full((m, rows), -2, dtype=np.int32)
+        corners = np.full((m, rows, 4, 2), np.nan); margin = np.full((m, rows), np.nan)
+        rc = fn(self.handle, int(dtype), int(width), int(height), int(n_img), C.c_void_p(ptr), d, codes.ctypes.data_as(C.POINTER(C.c_uint64)),
+                len(codes), C.byref(o), _ip(count), _ip(tag_id), _ip(rot), _ip(hamming), _dp(corners), _dp(margin), _ip(flags), _ip(stats))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        out = []
+        for k in range(int(n_img)):
+            n = min(int(count[k]), rows)
+            out.append((tag_id[k, :n].copy(), rot[k, :n].copy(), hamming[k, :n].copy(), corners[k, :n].copy(), margin[k, :n].copy(),
+                        int(count[k]), int(flags[k]), stats[k].copy()))
+        return out
+
+    def detect_tags_batch(self, images, family_bits: int, codes, step: int = 1, nms_radius: int = 5, min_response: int = 1,
+                          rel_threshold: float = 0.1, max_candidates: int = 4096, half_win: int = 4, max_iterations: int = 30,
+                          eps: float = 1e-3, merge_radius: float = 1.0, min_side: float = 20.0, max_side: Optional[float] = None,
+                          max_side_ratio: float = 2.0, offset: Optional[float] = None, edge_samples: int = 8,
+                          edge_min_contrast: float = 40.0, max_quads: int = 1024, border: int = 1, cell_samples: int = 3,
+                          tag_min_contrast: float = 40.0, max_border_errors: int = 0, max_hamming: int = 2, max_tags: Optional[int] = None):
+        """From a batch of grey images to the tags of a family in each, in ONE call that keeps every intermediate on the device:
+        detector, refinement, merge, proposer, decoder and the best quad per id, by the rule stated at ccal_detect_tags_batch in
+        include/ccal.h.  images: [n][H][W], uint8 or uint16; family_bits = d * d and codes as for decode_tags_batch.  The other
+        parameters are the stages' (detect_corners_batch, refine_corners_batch, api.merge_points, propose_quads_batch,
+        decode_tags_batch); max_side None: half the larger image side; offset None: half a cell, 1 / (2 (d + 2 border)); max_tags
+        None: the family's size.  The contrasts are in grey levels of the images' type.  Returns one tuple per image: (id int32 [m],
+        rot [m], hamming [m], corners f64 [m, 4, 2] in the tag's canonical order, margin [m], count, flags, stats int32 [4]) in
+        ascending id, m = min(count, max_tags); flags: _ffi.TAGS_FLAG_*; stats = candidates found, points after the merge, quads
+        found, decodable quads before the selection."""
+        images, dtype, channels = check_images(images, True)
+        if channels != 1:
+            raise ValueError("detect_tags_batch: single-channel images [n][H][W]")
+        n_img, H, W = images.shape[:3]
+        return self._detect_tags(self.lib.ccal_detect_tags_batch, "ccal_detect_tags_batch", images.ctypes.data, dtype, W, H, n_img,
+                                 family_bits, codes, step, nms_radius, min_response, rel_threshold, max_candidates, half_win,
+                                 max_iterations, eps, merge_radius, min_side, max_side, max_side_ratio, offset, edge_samples,
+                                 edge_min_contrast, max_quads, border, cell_samples, tag_min_contrast, max_border_errors, max_hamming,
+                                 max_tags)
+
+    def detect_tags_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, family_bits: int, codes, step: int = 1,
+                        nms_radius: int = 5, min_response: int = 1, rel_threshold: float = 0.1, max_candidates: int = 4096,
+                        half_win: int = 4, max_iterations: int = 30, eps: float = 1e-3, merge_radius: float = 1.0, min_side: float = 20.0,
+                        max_side: Optional[float] = None, max_side_ratio: float = 2.0, offset: Optional[float] = None,
+                        edge_samples: int = 8, edge_min_contrast: float = 40.0, max_quads: int = 1024, border: int = 1,
+                        cell_samples: int = 3, tag_min_contrast: float = 40.0, max_border_errors: int = 0, max_hamming: int = 2,
+                        max_tags: Optional[int] = None):
+        """detect_tags_batch over an image block that is already on the device (a device pointer to [n_img][height][width] of
+        dtype _ffi.PIX_U8 / PIX_U16, its writes complete or enqueued on the context's stream); the family and the results are host arrays."""
+        return self._detect_tags(self.lib.ccal_detect_tags_dev, "ccal_detect_tags_dev", images_ptr, dtype, width, height, n_img,
+                                 family_bits, codes, step, nms_radius, min_response, rel_threshold, max_candidates, half_win,
+                                 max_iterations, eps, merge_radius, min_side, max_side, max_side_ratio, offset, edge_samples,
+                                 edge_min_contrast, max_quads, border, cell_samples, tag_min_contrast, max_border_errors, max_hamming,
+                                 max_tags)
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first

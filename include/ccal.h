@@ -838,6 +838,79 @@ int ccal_propose_quads_dev(ccal_ctx* ctx, int dtype, int width, int height, int 
                            int cap, int32_t* count_out /* [n_img] */, int32_t* flags_out /* [n_img] */,
                            int32_t* idx_out /* [n_img][cap][4] */, double* quads_out /* [n_img][cap][4][2] or NULL */);
 
+/* ---- from pixels to detections: AprilGrid tags from images in one call ------------------------------------------------------------
+ * What the reference does per image in one function (image_to_option_feature_frame, src/data_loader.rs:36-70), up to the tags: the
+ * four sections above chained on the device - the image block is uploaded once per chunk (not at all by the _dev form) and no
+ * per-point or per-quad array comes back before the tags.  Looking the corners up on a board (id * 4 + i, MIN_CORNERS) stays with
+ * the caller.  The rule composes the four rules above by reference and adds only the links; tests/tagchain_ref.py is its numpy
+ * yardstick, and the four calls above with the links done on the host give the same bits.
+ *
+ * Images: as above - [n_img][height][width] of CCAL_PIX_U8 / CCAL_PIX_U16.  Family: d, codes, n_codes as for ccal_decode_tags_*.
+ * Options: every field of ccal_detect_tags_opts is named after the stage parameter it feeds and has that parameter's range; there
+ * are no defaults (the Python layer's: step 1, nms_radius 5, min_response 1, rel_q10 102, cand_cap 4096; half_win 4,
+ * max_iterations 30, eps 1e-3; merge_radius 1; min_side 20, max_side half the larger image side, max_side_ratio 2, offset
+ * 1 / (2 (d + 2 border)), edge_samples 8, edge_min_contrast 40, quad_cap 1024; border 1, cell_samples 3, tag_min_contrast 40,
+ * max_border_errors 0, max_hamming 2).  Per image:
+ *   1 candidates  ccal_detect_corners_* with (step, nms_radius, min_response, rel_q10): the stored candidates are the first
+ *                 min(count, cand_cap) in row-major order.
+ *   2 starts      the integer (x, y) of each stored candidate as f64.
+ *   3 refine      ccal_refine_corners_* with (half_win, max_iterations, eps) on those starts; only corners with status CCAL_OK go on,
+ *                 in candidate order.
+ *   4 round       each coordinate through f32 (round to nearest even) and back to f64: the f32 a FeaturePoint holds.
+ *   5 merge       the points in that order; a point is dropped if |dx| <= merge_radius and |dy| <= merge_radius against a point
+ *                 KEPT before it (a dropped point screens nothing).  The difference of two f32 values is exact in f64: no rounding
+ *                 enters the test.
+ *   6 propose     ccal_propose_quads_* with (min_side, max_side, max_side_ratio, offset, edge_samples, edge_min_contrast) on the kept
+ *                 points: the stored quads are the first min(count, quad_cap) in its lexicographic order.
+ *   7 decode      ccal_decode_tags_* with (border, cell_samples, tag_min_contrast, max_border_errors, max_hamming) on every stored quad.
+ *   8 select      among the image's CCAL_TAG_OK quads each id keeps the quad with the smallest (hamming, -margin); on an exact tie
+ *                 the quad earlier in the proposer's order.  The tags are listed in ascending id.
+ * Outputs per image k: count_out[k] = the number of distinct ids - it may exceed tag_cap, then the first tag_cap are stored -,
+ * id_out, rot_out, hamming_out [n_img][tag_cap], corners_out [n_img][tag_cap][4][2] in the decoder's canonical order, margin_out
+ * [n_img][tag_cap] (NULL: not wanted), flags_out[k] (bit 0: the proposer's cut-list bit; bit 1: more candidates than cand_cap;
+ * bit 2: more quads than quad_cap; bit 3: more tags than tag_cap), stats_out [n_img][4] (NULL: not wanted) = candidates found,
+ * points after the merge, quads found, CCAL_TAG_OK quads before the selection.  Rows past min(count, tag_cap) are not written.
+ * An image's outputs are a pure function of that image, the family and the options: they do not depend on its place in the batch,
+ * on what else is in it, on how the library cuts the batch into chunks or on the run.  The links use no atomics; every order is an
+ * index order (the merge walks the candidates one by one, the selection compares every pair, the scans are prefix sums).
+ * ccal_detect_tags_batch: host pointers.  ccal_detect_tags_dev: `images_dev` is a device pointer (the output of ccal_remap_dev on
+ * this context's stream, or a block whose writes are complete); everything else stays a host array.  Both return when the outputs
+ * are written.
+ * CCAL_ERR_INVALID_ARG, nothing launched or written: opts NULL, a field outside its stage's range, merge_radius negative or not
+ * finite, cand_cap outside 1 .. 32768 (the proposer's point limit), quad_cap or tag_cap < 1, a code >= 2^(d d) (d d < 64 only), a
+ * dtype other than the two, width, height <= 0 or n_img < 0, more than 2^31 - 1 pixels in an image, a NULL required pointer (with
+ * n_img > 0: images, codes, count_out, id_out, rot_out, hamming_out, corners_out, flags_out).  n_img == 0 is valid. */
+typedef struct {
+    /* detector */
+    int32_t step, nms_radius;
+    int64_t min_response;
+    int32_t rel_q10, cand_cap;
+    /* refinement */
+    int32_t half_win, max_iterations;
+    double eps;
+    /* merge */
+    double merge_radius;
+    /* proposer */
+    double min_side, max_side, max_side_ratio, offset, edge_min_contrast;
+    int32_t edge_samples, quad_cap;
+    /* decoder */
+    int32_t border, cell_samples;
+    double tag_min_contrast;
+    int32_t max_border_errors, max_hamming;
+    /* output */
+    int32_t tag_cap, reserved_;
+} ccal_detect_tags_opts;
+int ccal_detect_tags_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images,
+                           int d, const uint64_t* codes /* [n_codes] */, int n_codes, const ccal_detect_tags_opts* opts,
+                           int32_t* count_out /* [n_img] */, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out /* [n_img][tag_cap] */,
+                           double* corners_out /* [n_img][tag_cap][4][2] */, double* margin_out /* [n_img][tag_cap] or NULL */,
+                           int32_t* flags_out /* [n_img] */, int32_t* stats_out /* [n_img][4] or NULL */);
+int ccal_detect_tags_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev,
+                         int d, const uint64_t* codes /* [n_codes] */, int n_codes, const ccal_detect_tags_opts* opts,
+                         int32_t* count_out /* [n_img] */, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out /* [n_img][tag_cap] */,
+                         double* corners_out /* [n_img][tag_cap][4][2] */, double* margin_out /* [n_img][tag_cap] or NULL */,
+                         int32_t* flags_out /* [n_img] */, int32_t* stats_out /* [n_img][4] or NULL */);
+
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
                              double* err_out /* [n_corners] Euclidean px error */);

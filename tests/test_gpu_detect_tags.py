@@ -1,0 +1,431 @@
+"""GPU: AprilGrid tags from images in one device-resident call (ccal_kernels_tagchain.hip, ccal_detect_tags_batch / _dev,
+Context.detect_tags_batch, api.detect_tags, api.detect_aprilgrid(fused=True)).
+
+The oracle is the STAGED chain on the same context: the four stage entry points (ccal_detect_corners_batch,
+ccal_refine_corners_batch, ccal_propose_quads_batch, ccal_decode_tags_batch) with the links of the rule in include/ccal.h done on
+the host by tests/tagchain_ref.py (merge, select) - what api.detect_aprilgrid does by default.  The fused call runs the same stage
+kernels on the same inputs and its links are comparisons and copies, so EVERY output is compared as bits, the f64 corners and
+margins included: no tolerance anywhere.  The two link kernels are also held to numpy alone, through the second library's hooks.
+Nothing is larger than 640 x 240; every case takes a few seconds at most."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tag_ref  # noqa: E402
+import tagchain_ref as ref  # noqa: E402
+
+from camera_intrinsic_calibration_rs_amd import _ffi, api  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+SENT_I, SENT_F = -77, -3.25
+IP, LP, DP, UP = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+OUTS = ("count", "id", "rot", "hamming", "corners", "margin", "flags", "stats")
+D = tag_ref.GRID_D
+CODES = tuple(tag_ref.grid_family().codes)
+
+
+def _code(dtype):
+    return _ffi.PIX_U8 if np.dtype(dtype) == np.uint8 else _ffi.PIX_U16
+
+
+def raw_detect(ctx, images, o, fn=None, ptr=None, **change):
+    """The C entry point on a batch [n][H][W], every output prefilled with a sentinel: {"rc"} + OUTS.  change: arguments replaced
+    (tests of invalid ones); "null": names of pointers passed as NULL; "opts_null": no options."""
+    images = np.ascontiguousarray(images)
+    n_img, H, W = images.shape
+    a = dict(dtype=_code(images.dtype), w=W, h=H, n=n_img, d=D, codes=CODES, n_codes=None, null=(), opts_null=False)
+    a.update(change)
+    codes = np.ascontiguousarray(np.asarray(a["codes"], dtype=np.uint64))
+    opts = _ffi.DetectTagsOpts(**o)
+    m, rows = max(n_img, 1), max(int(o["tag_cap"]), 1)
+    out = {"count": np.full(m, SENT_I, dtype=np.int32), "flags": np.full(m, SENT_I, dtype=np.int32),
+           "stats": np.full((m, 4), SENT_I, dtype=np.int32), "id": np.full((m, rows), SENT_I, dtype=np.int32),
+           "rot": np.full((m, rows), SENT_I, dtype=np.int32), "hamming": np.full((m, rows), SENT_I, dtype=np.int32),
+           "corners": np.full((m, rows, 4, 2), SENT_F), "margin": np.full((m, rows), SENT_F)}
+    p = lambda name, t: None if name in a["null"] else out[name].ctypes.data_as(t)      # noqa: E731
+    fn = fn or ctx.lib.ccal_detect_tags_batch
+    img_ptr = None if "images" in a["null"] else C.c_void_p(images.ctypes.data if ptr is None else ptr)
+    out["rc"] = fn(ctx.handle, a["dtype"], a["w"], a["h"], a["n"], img_ptr, a["d"], None if "codes" in a["null"] else codes.ctypes.data_as(UP),
+                   len(codes) if a["n_codes"] is None else a["n_codes"], None if a["opts_null"] else C.byref(opts),
+                   p("count", IP), p("id", IP), p("rot", IP), p("hamming", IP), p("corners", DP), p("margin", DP), p("flags", IP), p("stats", IP))
+    return out
+
+
+def untouched(out):
+    return all(bool((out[k] == (SENT_F if out[k].dtype == np.float64 else SENT_I)).all()) for k in OUTS)
+
+
+def bits(out, k=None):
+    return b"".join((out[key] if k is None else out[key][k]).tobytes() for key in OUTS)
+
+
+_STAGED = {}
+
+
+def staged(ctx, images, o, key=None):
+    """The oracle: the four stage calls on `ctx`, the links on the host.  Per image what tagchain_ref.chain returns (count, id, rot,
+    hamming, corners, margin, flags, stats, refined, points, decoded).  key: computed once and shared."""
+    if key is not None and key in _STAGED:
+        return _STAGED[key]
+    images = np.ascontiguousarray(images)
+    found = ctx.detect_corners_batch(images, o["step"], o["nms_radius"], o["min_response"], o["rel_q10"] / 1024.0, o["cand_cap"])
+    xy, status, _, _ = ctx.refine_corners_batch(images, [f[0].astype(np.float64) for f in found], o["half_win"], o["max_iterations"], o["eps"])
+    refined = [np.float32(xy[k][status[k] == _ffi.OK]).astype(np.float64) for k in range(len(images))]
+    points = [ref.merge(r, o["merge_radius"]) for r in refined]
+    prop = ctx.propose_quads_batch(images, points, o["min_side"], o["max_side"], o["max_side_ratio"], o["offset"], o["edge_samples"],
+                                   o["edge_min_contrast"], o["quad_cap"])
+    reason, tag_id, rot, ham, corners, _, margin = ctx.decode_tags_batch(images, [p[1] for p in prop], D * D, CODES, o["border"],
+                                                                         o["cell_samples"], o["tag_min_contrast"], o["max_border_errors"],
+                                                                         o["max_hamming"])
+    out = []
+    for k in range(len(images)):
+        win = ref.select(reason[k], tag_id[k], ham[k], margin[k])
+        m = min(len(win), o["tag_cap"])
+        w = np.array(win[:m], dtype=np.int64)
+        flags = (prop[k][3] & ref.FLAG_CUT) | (ref.FLAG_CAND_CAP if found[k][3] > o["cand_cap"] else 0) | \
+            (ref.FLAG_QUAD_CAP if prop[k][2] > o["quad_cap"] else 0) | (ref.FLAG_TAG_CAP if len(win) > o["tag_cap"] else 0)
+        out.append({"count": len(win), "id": tag_id[k][w], "rot": rot[k][w], "hamming": ham[k][w], "corners": corners[k][w], "margin": margin[k][w],
+                    "flags": flags, "stats": [found[k][3], len(points[k]), prop[k][2], int((reason[k] == _ffi.TAG_OK).sum())],
+                    "refined": refined[k], "points": points[k], "quads": prop[k][1], "reason": reason[k], "all_id": tag_id[k],
+                    "all_margin": margin[k]})
+    if key is not None:
+        _STAGED[key] = out
+    return out
+
+
+def check_against_staged(got, want, tag_cap, where=""):
+    """Exact: count, flags, stats, the stored rows' integers and the bits of their doubles, the sentinel in every row past them."""
+    assert got["rc"] == _ffi.OK, where
+    for k, w in enumerate(want):
+        at = (where, k)
+        assert (int(got["count"][k]), int(got["flags"][k]), got["stats"][k].tolist()) == (w["count"], w["flags"], [int(s) for s in w["stats"]]), at
+        m = min(w["count"], tag_cap)
+        for key in ("id", "rot", "hamming"):
+            assert np.array_equal(got[key][k, :m], w[key][:m]), at + (key,)
+            assert (got[key][k, m:] == SENT_I).all(), at + (key,)
+        for key in ("corners", "margin"):
+            assert got[key][k, :m].tobytes() == np.ascontiguousarray(w[key][:m], dtype=np.float64).tobytes(), at + (key,)
+            assert (got[key][k, m:] == SENT_F).all(), at + (key,)
+
+
+def frames(dtype):
+    return tag_ref.grid_frames(dtype)[0]
+
+
+# ---- 1. parity with the staged chain ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nms_radius", [5, 3])
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16], ids=["u8", "u16"])
+def test_parity_with_the_staged_chain(gpu_ctx, dtype, nms_radius):
+    imgs = frames(dtype)
+    o = ref.opts(dtype, nms_radius=nms_radius)
+    want = staged(gpu_ctx, imgs, o, key=("frames", np.dtype(dtype).name, nms_radius))
+    assert all(w["count"] == 6 and w["id"].tolist() == list(range(6)) for w in want)
+    if nms_radius == 3:                                  # else the case shows nothing about merging
+        assert any(len(w["points"]) < len(w["refined"]) for w in want)
+    got = raw_detect(gpu_ctx, imgs, o)
+    check_against_staged(got, want, o["tag_cap"], f"{np.dtype(dtype).name} r {nms_radius}")
+    print(f"{np.dtype(dtype).name} nms_radius {nms_radius}: stats {got['stats'].tolist()}, merged "
+          f"{[len(w['refined']) - len(w['points']) for w in want]}")
+    again = raw_detect(gpu_ctx, imgs, o)
+    assert bits(again) == bits(got)                      # two runs: the same bits
+    lean = raw_detect(gpu_ctx, imgs, o, null=("margin", "stats"))         # the two optional outputs
+    assert lean["rc"] == _ffi.OK and (lean["margin"] == SENT_F).all() and (lean["stats"] == SENT_I).all()
+    for key in ("count", "id", "rot", "hamming", "corners", "flags"):
+        assert lean[key].tobytes() == got[key].tobytes(), key
+
+
+# ---- 2. every id twice: the selection -----------------------------------------------------------------------------------------------------
+def test_montages_keep_the_better_quad_of_each_pair(gpu_ctx):
+    imgs = np.stack([ref.montage(0), ref.montage(1)])
+    o = ref.opts(np.uint8, 640, 240)
+    want = staged(gpu_ctx, imgs, o, key="montages")
+    for w in want:
+        ok = w["reason"] == _ffi.TAG_OK
+        assert sorted(w["all_id"][ok].tolist()) == sorted(list(range(6)) * 2)          # the staged chain finds every id twice
+        assert len(set(w["all_margin"][ok].tolist())) == 12
+    got = raw_detect(gpu_ctx, imgs, o)
+    check_against_staged(got, want, o["tag_cap"], "montages")
+    assert got["count"].tolist() == [6, 6] and got["stats"][:, 3].tolist() == [12, 12]
+    fam = api.TagFamily("toy", 36, CODES)
+    choice = api.decode_tags(list(imgs), [w["quads"] for w in want], fam, 1, 3, 40.0, 0, 2, ctx=gpu_ctx)
+    for k, tags in enumerate(choice):
+        assert [t[0] for t in tags] == got["id"][k, :6].tolist() and [t[1] for t in tags] == got["rot"][k, :6].tolist()
+        assert [t[2] for t in tags] == got["hamming"][k, :6].tolist()
+        assert np.stack([t[3] for t in tags]).tobytes() == got["corners"][k, :6].tobytes()
+
+
+# ---- 3. the caps ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("caps", [dict(cand_cap=60), dict(quad_cap=1), dict(tag_cap=2), dict(cand_cap=90, quad_cap=2, tag_cap=1)],
+                         ids=["cand_cap", "quad_cap", "tag_cap", "all three"])
+def test_caps_store_the_first_rows_and_set_their_flags(gpu_ctx, caps):
+    """The frames have 97 .. 123 candidates, 6 quads and 6 tags each; with the first 90 candidates alone they still have 3 .. 5 quads
+    and 2 tags (the CPU chain's figures), so every cap below cuts something in every frame and its bit is set."""
+    imgs = frames(np.uint8)
+    full = staged(gpu_ctx, imgs, ref.opts(np.uint8), key=("frames", "uint8", 5))
+    assert all(w["stats"][0] > 90 and w["stats"][2] == 6 and w["count"] == 6 for w in full)
+    o = ref.opts(np.uint8, **caps)
+    want = staged(gpu_ctx, imgs, o)
+    bit = {"cand_cap": ref.FLAG_CAND_CAP, "quad_cap": ref.FLAG_QUAD_CAP, "tag_cap": ref.FLAG_TAG_CAP}
+    assert all(w["flags"] == sum(bit[name] for name in caps) for w in want), [w["flags"] for w in want]
+    got = raw_detect(gpu_ctx, imgs, o)
+    check_against_staged(got, want, o["tag_cap"], str(caps))           # rows past min(count, tag_cap) keep the sentinel
+    if caps == dict(tag_cap=2):
+        assert got["count"].tolist() == [6] * 4 and (got["id"][:, :2] == [0, 1]).all()
+
+
+# ---- 4. batch shape -------------------------------------------------------------------------------------------------------------------------
+def test_a_mixed_batch_image_by_image(gpu_ctx):
+    imgs = ref.mixed_batch(np.uint8)
+    H, W = imgs.shape[1:]
+    o = ref.opts(np.uint8, W, H)
+    want = staged(gpu_ctx, imgs, o)
+    assert [w["count"] for w in want] == [want[0]["count"], 0, 0, 4] and want[0]["count"] >= 1
+    assert want[1]["stats"] == [0, 0, 0, 0] and want[2]["stats"][1] >= 20 and want[2]["stats"][3] == 0     # points, no tags
+    whole = raw_detect(gpu_ctx, imgs, o)
+    check_against_staged(whole, want, o["tag_cap"], "mixed")
+    for k in range(len(imgs)):
+        alone = raw_detect(gpu_ctx, imgs[k:k + 1], o)
+        assert alone["rc"] == _ffi.OK and bits(alone, 0) == bits(whole, k), k
+    back = raw_detect(gpu_ctx, imgs[::-1], o)
+    assert b"".join(bits(back, k) for k in range(len(imgs) - 1, -1, -1)) == b"".join(bits(whole, k) for k in range(len(imgs)))
+
+
+def test_no_images_and_images_without_a_domain_are_valid(gpu_ctx):
+    o = ref.opts()
+    for fn in (gpu_ctx.lib.ccal_detect_tags_batch, gpu_ctx.lib.ccal_detect_tags_dev):
+        got = raw_detect(gpu_ctx, np.zeros((0, 48, 64), dtype=np.uint8), o, fn=fn, null=OUTS + ("images", "codes"))
+        assert got["rc"] == _ffi.OK
+    assert gpu_ctx.detect_tags_dev(0, _ffi.PIX_U8, 64, 48, 0, 36, CODES) == []
+    tiny = raw_detect(gpu_ctx, np.full((2, 6, 40), 9, dtype=np.uint8), dict(o, max_side=20.0))        # 6 rows: no domain at step 1
+    assert tiny["rc"] == _ffi.OK and (tiny["count"] == 0).all() and (tiny["flags"] == 0).all() and (tiny["stats"] == 0).all()
+    assert (tiny["id"] == SENT_I).all() and (tiny["corners"] == SENT_F).all()
+
+
+# ---- 5. chunks ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("per_chunk", [1, 2], ids=["an image per chunk", "groups of two"])
+def test_a_batch_cut_into_chunks(dev_ctx, gpu_ctx, monkeypatch, per_chunk):
+    """The library runs a batch whose block would exceed 256 MB in chunks of whole images; the second library reads the limit from
+    CCAL_TEST_TAGCHAIN_CHUNK_BYTES (tests only).  The limits come from tagchain_ref.chunk_limit, and
+    tests/test_detect_tags_cpu.py holds on the CPU that the library's planner cuts the four frames exactly so - for the host call,
+    whose chunk counts the pixels, and for the _dev call.  Host and device entry: the product's bits."""
+    import torch
+    imgs = frames(np.uint8)
+    o = ref.opts(np.uint8, nms_radius=3)
+    whole = raw_detect(gpu_ctx, imgs, o)
+    check_against_staged(whole, staged(gpu_ctx, imgs, o, key=("frames", "uint8", 3)), o["tag_cap"], "whole")
+    raw = torch.from_numpy(imgs.copy()).cuda()
+    torch.cuda.synchronize()
+    monkeypatch.setenv("CCAL_TEST_TAGCHAIN_CHUNK_BYTES", str(ref.chunk_limit(False, imgs.shape[1:], 1, o, len(CODES), per_chunk)))
+    got = raw_detect(dev_ctx, imgs, o)
+    assert got["rc"] == _ffi.OK and bits(got) == bits(whole)
+    monkeypatch.setenv("CCAL_TEST_TAGCHAIN_CHUNK_BYTES", str(ref.chunk_limit(True, imgs.shape[1:], 1, o, len(CODES), per_chunk)))
+    got = raw_detect(dev_ctx, imgs, o, fn=dev_ctx.lib.ccal_detect_tags_dev, ptr=raw.data_ptr())
+    assert got["rc"] == _ffi.OK and bits(got) == bits(whole)
+
+
+# ---- 6. the allocation poison ---------------------------------------------------------------------------------------------------------------
+def test_parity_on_poisoned_workspace(dev_ctx, gpu_ctx, monkeypatch):
+    """The second library with CCAL_TEST_POISON_ALLOC=1 (tests/test_gpu_poison.py): every double of the chain's block starts as NaN
+    bytes in every chunk; each is written before it is read."""
+    cases = [(frames(np.uint16), ref.opts(np.uint16, nms_radius=3)), (ref.mixed_batch(np.uint8), None),
+             (frames(np.uint8), ref.opts(np.uint8, cand_cap=100, quad_cap=3, tag_cap=1))]
+    clean = []
+    for imgs, o in cases:
+        o = o or ref.opts(np.uint8, imgs.shape[2], imgs.shape[1])
+        clean.append((imgs, o, raw_detect(gpu_ctx, imgs, o)))
+    monkeypatch.setenv("CCAL_TEST_POISON_ALLOC", "1")
+    for imgs, o, want in clean:
+        got = raw_detect(dev_ctx, imgs, o)
+        assert want["rc"] == got["rc"] == _ffi.OK and bits(got) == bits(want)
+
+
+# ---- 7. the _dev entry ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16], ids=["u8", "u16"])
+def test_dev_entry_point_on_a_block_written_by_remap_dev(gpu_ctx, dtype):
+    """The images go through ccal_remap_dev with an identity map (every output pixel reads its own source pixel: the same bytes)
+    into a torch-allocated block; ccal_detect_tags_dev follows on the context's stream without a synchronise in between."""
+    import torch
+    imgs = np.ascontiguousarray(frames(dtype))
+    n, H, W = imgs.shape
+    o = ref.opts(dtype)
+    host = raw_detect(gpu_ctx, imgs, o)
+    check_against_staged(host, staged(gpu_ctx, imgs, o, key=("frames", np.dtype(dtype).name, 5)), o["tag_cap"], "host")
+    xm, ym = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32))
+    m = gpu_ctx.undistort_map_from_arrays(np.ascontiguousarray(xm), np.ascontiguousarray(ym))
+    try:
+        src = torch.from_numpy(imgs.view(np.uint8).copy()).cuda()
+        dst = torch.zeros_like(src)
+        torch.cuda.synchronize()
+        m.remap_dev(src.data_ptr(), dst.data_ptr(), _code(dtype), 1, W, H, n)
+        dev = raw_detect(gpu_ctx, imgs, o, fn=gpu_ctx.lib.ccal_detect_tags_dev, ptr=dst.data_ptr())
+        assert dst.cpu().numpy().tobytes() == imgs.tobytes()
+    finally:
+        m.close()
+    assert dev["rc"] == _ffi.OK and bits(dev) == bits(host)
+    scale = 257.0 if dtype == np.uint16 else 1.0
+    wrapped = gpu_ctx.detect_tags_dev(dst.data_ptr(), _code(dtype), W, H, n, 36, CODES, edge_min_contrast=40.0 * scale,
+                                      tag_min_contrast=40.0 * scale, max_tags=o["tag_cap"])
+    for k, (ids, rot, ham, corners, margin, count, flags, stats) in enumerate(wrapped):
+        assert (count, flags, stats.tolist()) == (int(host["count"][k]), int(host["flags"][k]), host["stats"][k].tolist())
+        assert np.array_equal(ids, host["id"][k, :count]) and corners.tobytes() == host["corners"][k, :count].tobytes()
+
+
+# ---- 8. invalid arguments -------------------------------------------------------------------------------------------------------------------
+def test_invalid_arguments_write_nothing(gpu_ctx):
+    imgs = frames(np.uint8)[:2]
+    good = ref.opts()
+    nan, inf = float("nan"), float("inf")
+    bad_opts = [dict(step=0), dict(step=5), dict(nms_radius=0), dict(nms_radius=16), dict(min_response=0), dict(rel_q10=-1), dict(rel_q10=1025),
+                dict(cand_cap=0), dict(cand_cap=32769), dict(half_win=0), dict(half_win=16), dict(max_iterations=0), dict(eps=-1.0),
+                dict(eps=nan), dict(eps=inf), dict(merge_radius=-0.5), dict(merge_radius=nan), dict(merge_radius=inf), dict(min_side=0.5),
+                dict(min_side=nan), dict(max_side=19.0), dict(max_side=nan), dict(max_side_ratio=0.9), dict(offset=0.0), dict(offset=0.26),
+                dict(offset=nan), dict(edge_samples=0), dict(edge_samples=17), dict(edge_min_contrast=-1.0), dict(edge_min_contrast=inf),
+                dict(quad_cap=0), dict(border=0), dict(border=3), dict(cell_samples=0), dict(cell_samples=5), dict(tag_min_contrast=-1.0),
+                dict(tag_min_contrast=nan), dict(max_border_errors=-1), dict(max_hamming=-1), dict(max_hamming=37), dict(tag_cap=0),
+                dict(tag_cap=-3)]
+    bad_args = [dict(d=2), dict(d=9), dict(n_codes=0), dict(codes=CODES[:3] + (1 << 36,)), dict(dtype=2), dict(dtype=-1), dict(w=0), dict(h=-1),
+                dict(n=-1), dict(w=65536, h=32768), dict(opts_null=True), dict(null=("images",)), dict(null=("codes",)), dict(null=("count",)),
+                dict(null=("id",)), dict(null=("rot",)), dict(null=("hamming",)), dict(null=("corners",)), dict(null=("flags",))]
+    for fn in (gpu_ctx.lib.ccal_detect_tags_batch, gpu_ctx.lib.ccal_detect_tags_dev):
+        for change in bad_opts:
+            got = raw_detect(gpu_ctx, imgs, dict(good, **change), fn=fn)
+            assert got["rc"] == _ffi.ERR_INVALID_ARG and untouched(got) and gpu_ctx.last_error(), change
+        for change in bad_args:
+            got = raw_detect(gpu_ctx, imgs, good, fn=fn, **change)
+            assert got["rc"] == _ffi.ERR_INVALID_ARG and untouched(got) and gpu_ctx.last_error(), change
+    with pytest.raises(ValueError):
+        gpu_ctx.detect_tags_batch(np.zeros((1, 45, 67, 3), dtype=np.uint8), 36, CODES)                       # colour
+    with pytest.raises(ValueError):
+        gpu_ctx.detect_tags_batch(np.zeros((1, 45, 67), dtype=np.float32), 36, CODES)
+    with pytest.raises(ValueError):
+        gpu_ctx.detect_tags_batch(np.zeros((1, 45, 67), dtype=np.uint8), 35, CODES)                          # not a square
+
+
+# ---- 9. the two link kernels alone, against numpy -------------------------------------------------------------------------------------------
+def hook_merge(ctx, xy_list, status_list, radius):
+    offs = np.zeros(len(xy_list) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in xy_list], out=offs[1:])
+    n = int(offs[-1])
+    xy = np.ascontiguousarray(np.concatenate(xy_list).reshape(-1, 2), dtype=np.float64)
+    status = None if status_list is None else np.ascontiguousarray(np.concatenate(status_list), dtype=np.int32)
+    kept = np.full(len(xy_list), SENT_I, dtype=np.int32)
+    out = np.full((max(n, 1), 2), SENT_F)
+    fn = ctx.lib.ccal_test_merge_points
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, LP, DP, IP, C.c_double, IP, DP]
+    rc = fn(ctx.handle, len(xy_list), offs.ctypes.data_as(LP), xy.ctypes.data_as(DP), None if status is None else status.ctypes.data_as(IP),
+            float(radius), kept.ctypes.data_as(IP), out.ctypes.data_as(DP))
+    assert rc == _ffi.OK, ctx.last_error()
+    return offs, kept, out
+
+
+def test_merge_kernel_against_numpy(dev_ctx):
+    """Images of 0, 1, 63, 64, 65, 130 and 4096 points (twice: dense, and sparse enough that more points are kept than the kernel
+    holds in LDS) in one launch.  The coordinates lie on a half-pixel lattice with a few nanometres added to some: after the
+    rounding through f32 there are exact duplicates and distances exactly equal to the radius.  A third of the rows carry a status
+    that is not CCAL_OK.  Exact: the counts, the kept points' bits, the sentinel behind them."""
+    rng = np.random.default_rng(20)
+    sizes = [(0, 4), (1, 4), (63, 24), (64, 24), (65, 24), (130, 40), (4096, 200), (4096, 1400)]
+    xy_list, status_list = [], []
+    for n, span in sizes:
+        p = rng.integers(0, span, (n, 2)).astype(np.float64) * 0.5 + rng.choice([0.0, 1e-9, -1e-9], (n, 2))
+        xy_list.append(p)
+        status_list.append(rng.choice([_ffi.OK, _ffi.OK, _ffi.ERR_NO_CONVERGENCE, _ffi.NO_RESULT], n).astype(np.int32))
+    for statuses in (status_list, None):
+        offs, kept, out = hook_merge(dev_ctx, xy_list, statuses, 1.0)
+        for k, p in enumerate(xy_list):
+            live = p if statuses is None else p[statuses[k] == _ffi.OK]
+            want = ref.merge(np.float32(live).astype(np.float64), 1.0)
+            a = int(offs[k])
+            assert int(kept[k]) == len(want), (k, statuses is None)
+            assert out[a:a + len(want)].tobytes() == want.tobytes(), k
+            assert (out[a + len(want):int(offs[k + 1])] == SENT_F).all(), k
+        if statuses is None:
+            assert kept[-1] > 2048 and 1 < kept[-2] < 2048 and kept[2] < 63                   # both tiers of the kept list; merges happen
+    # chains a - b - c: b within the radius of a, c within the radius of b but not of a - c is kept
+    chain = np.array([[10.0, 10.0], [11.0, 10.5], [12.0, 11.0], [13.0, 11.5], [14.0, 12.0], [10.0, 11.0], [50.0, 50.0], [50.0, 50.0]])
+    for r in (1.0, 0.0, 2.0):
+        offs, kept, out = hook_merge(dev_ctx, [chain], None, r)
+        want = ref.merge(chain, r)
+        assert int(kept[0]) == len(want) and out[:len(want)].tobytes() == want.tobytes(), r
+    assert ref.merge(chain, 1.0).tolist() == [[10.0, 10.0], [12.0, 11.0], [14.0, 12.0], [50.0, 50.0]]
+
+
+def test_select_kernel_against_numpy(dev_ctx):
+    """Images of 1, 64, 65 and 1024 decoded quads in one launch: ids out of order from a range wider than the stored rows, hamming
+    0 .. 2, margins from five values (exact (hamming, margin) ties, which the row order breaks), two rows in five not CCAL_TAG_OK
+    and carrying ids and margins that would win.  Exact: counts, the OK counts, every stored row, the sentinel behind them."""
+    rng = np.random.default_rng(21)
+    sizes, rows = (1, 64, 65, 1024), 40
+    n = sum(sizes)
+    offs = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=offs[1:])
+    reason = rng.choice([_ffi.TAG_OK, _ffi.TAG_OK, _ffi.TAG_OK, _ffi.TAG_BORDER, _ffi.TAG_NO_CODE], n).astype(np.int32)
+    tag_id = rng.integers(0, 60, n).astype(np.int32)
+    rot = rng.integers(0, 4, n).astype(np.int32)
+    ham = rng.integers(0, 3, n).astype(np.int32)
+    margin = rng.integers(1, 6, n).astype(np.float64) * 0.5
+    margin[reason != _ffi.TAG_OK] = 99.0
+    ham[reason != _ffi.TAG_OK] = 0
+    corners = rng.random((n, 4, 2)) * 300.0
+    m = len(sizes)
+    out = {"count": np.full(m, SENT_I, np.int32), "n_ok": np.full(m, SENT_I, np.int32), "id": np.full((m, rows), SENT_I, np.int32),
+           "rot": np.full((m, rows), SENT_I, np.int32), "hamming": np.full((m, rows), SENT_I, np.int32),
+           "corners": np.full((m, rows, 4, 2), SENT_F), "margin": np.full((m, rows), SENT_F)}
+    fn = dev_ctx.lib.ccal_test_select_tags
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, LP, IP, IP, IP, IP, DP, DP, C.c_int, IP, IP, IP, IP, IP, DP, DP]
+    rc = fn(dev_ctx.handle, m, offs.ctypes.data_as(LP), reason.ctypes.data_as(IP), tag_id.ctypes.data_as(IP), rot.ctypes.data_as(IP),
+            ham.ctypes.data_as(IP), corners.ctypes.data_as(DP), margin.ctypes.data_as(DP), rows, out["count"].ctypes.data_as(IP),
+            out["n_ok"].ctypes.data_as(IP), out["id"].ctypes.data_as(IP), out["rot"].ctypes.data_as(IP), out["hamming"].ctypes.data_as(IP),
+            out["corners"].ctypes.data_as(DP), out["margin"].ctypes.data_as(DP))
+    assert rc == _ffi.OK, dev_ctx.last_error()
+    ties = 0
+    for k in range(m):
+        a, b = int(offs[k]), int(offs[k + 1])
+        win = ref.select(reason[a:b], tag_id[a:b], ham[a:b], margin[a:b])
+        assert int(out["count"][k]) == len(win) and int(out["n_ok"][k]) == int((reason[a:b] == _ffi.TAG_OK).sum()), k
+        s = min(len(win), rows)
+        w = a + np.array(win[:s], dtype=np.int64)
+        assert np.array_equal(out["id"][k, :s], tag_id[w]) and np.array_equal(out["rot"][k, :s], rot[w]) and np.array_equal(out["hamming"][k, :s], ham[w]), k
+        assert out["corners"][k, :s].tobytes() == corners[w].tobytes() and out["margin"][k, :s].tobytes() == margin[w].tobytes(), k
+        assert (out["id"][k, s:] == SENT_I).all() and (out["corners"][k, s:] == SENT_F).all() and (out["margin"][k, s:] == SENT_F).all(), k
+        for j in win:                                    # an exact tie that only the row order decides
+            same = (reason[a:b] == _ffi.TAG_OK) & (tag_id[a:b] == tag_id[a + j]) & (ham[a:b] == ham[a + j]) & (margin[a:b] == margin[a + j])
+            ties += int(same.sum() > 1)
+    assert ties > 10 and int(out["count"][3]) > rows and int(out["count"][0]) <= 1
+
+
+# ---- 10. the engine and api layers ------------------------------------------------------------------------------------------------------------
+def test_context_and_api_wrappers(gpu_ctx):
+    imgs = frames(np.uint8)
+    o = ref.opts(np.uint8)
+    want = staged(gpu_ctx, imgs, o, key=("frames", "uint8", 5))
+    got = gpu_ctx.detect_tags_batch(imgs, 36, CODES)                     # the defaults are OPTS; max_side None: half of 320
+    for k, (ids, rot, ham, corners, margin, count, flags, stats) in enumerate(got):
+        w = want[k]
+        assert (count, flags, stats.tolist()) == (w["count"], w["flags"], [int(s) for s in w["stats"]]) and ids.dtype == np.int32
+        assert np.array_equal(ids, w["id"]) and np.array_equal(rot, w["rot"]) and np.array_equal(ham, w["hamming"])
+        assert corners.tobytes() == np.ascontiguousarray(w["corners"]).tobytes() and margin.tobytes() == np.ascontiguousarray(w["margin"]).tobytes()
+    two = gpu_ctx.detect_tags_batch(imgs, 36, CODES, max_tags=2)
+    assert all(len(t[0]) == 2 and t[5] == 6 and t[6] == _ffi.TAGS_FLAG_TAG_CAP for t in two)
+    fam = api.TagFamily("toy", 36, CODES)
+    board = api.AprilGridBoard(tag_ref.GRID.tag_size_meter, tag_ref.GRID.tag_spacing, tag_ref.GRID.tag_rows, tag_ref.GRID.tag_cols)
+    tags = api.detect_tags(list(imgs), fam, ctx=gpu_ctx)
+    choice = api.decode_tags(list(imgs), [w["quads"] for w in want], fam, 1, 3, 40.0, 0, 2, ctx=gpu_ctx)
+    assert len(tags) == len(choice) == 4
+    for a, b in zip(tags, choice):
+        assert [t[:3] for t in a] == [t[:3] for t in b] and all(x[3].tobytes() == y[3].tobytes() for x, y in zip(a, b))
+    assert api.detect_tags([], fam, ctx=gpu_ctx) == []
+    times = [100 + k for k in range(len(imgs))]
+    assert api.detect_aprilgrid(list(imgs), fam, board, times=times, ctx=gpu_ctx, fused=True) == \
+        api.detect_aprilgrid(list(imgs), fam, board, times=times, ctx=gpu_ctx)
+    part = ref.cropped_frame(np.uint8)
+    assert api.detect_aprilgrid([part], fam, board, ctx=gpu_ctx, fused=True) == [None] == api.detect_aprilgrid([part], fam, board, ctx=gpu_ctx)
+    low = api.detect_aprilgrid([part], fam, board, min_corners=16, ctx=gpu_ctx, fused=True)
+    assert low[0] is not None and low == api.detect_aprilgrid([part], fam, board, min_corners=16, ctx=gpu_ctx)
+    assert sorted(low[0].features) == [4 * m + i for m in (0, 1, 3, 4) for i in range(4)]
+    assert api.detect_aprilgrid([], fam, board, ctx=gpu_ctx, fused=True) == []
