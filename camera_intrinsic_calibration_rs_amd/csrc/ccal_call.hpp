@@ -4,9 +4,12 @@
 //   CallBlock  the plan, the block and a sticky hipError_t: after the first failure every step is a no-op and finish() reports it;
 //              the destructor drains the stream before the block goes back to the context's cache, on every way out
 //   check_offsets  the argument check of a batched call's CSR offsets, with the call's name in the message
+//   GreyBatch  the image arguments of the image stages' calls: their check, an image's bytes, the device pointer to a chunk's images
+//   test_chunk_bytes  the tests' way to make those calls cut a small batch into chunks
 // Host only; for the translation units of the one-shot entry points ("One-shot calls").
 #pragma once
 #include <cstdio>
+#include <cstdlib>
 #include "ccal_internal.hpp"
 #include "ccal_plan.hpp"
 
@@ -73,5 +76,41 @@ public:
         return ok() ? CCAL_OK : hip_fail(ctx, where, e);
     }
 };
+
+// A batch of grey images [n_img][height][width] of CCAL_PIX_U8 / CCAL_PIX_U16, in host memory (a _batch entry point) or already on
+// the device (_dev).
+struct GreyBatch {
+    int dtype, width, height, n_img;
+    const void* images;
+    bool on_device;
+    // the message of the first argument out of range, or nullptr (images == NULL is the caller's check: it comes after n_img == 0)
+    const char* bad() const {
+        if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return "dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16";
+        if (width <= 0 || height <= 0 || n_img < 0) return "a size is not positive";
+        if ((int64_t)width * height > (int64_t)INT32_MAX) return "more than 2^31 - 1 pixels in an image";
+        return nullptr;
+    }
+    size_t img_bytes() const { return (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height; }
+    size_t staged_bytes(size_t m) const { return on_device ? 0 : img_bytes() * m; }       // room in the call's block for m images
+    // the device pointer to the images k0 .. k0 + m - 1: where they are, or slice s of the block, to which they are uploaded
+    const void* chunk(CallBlock& blk, Slice<char> s, size_t k0, size_t m) const {
+        const char* first = static_cast<const char*>(images) + k0 * img_bytes();
+        if (on_device) return first;
+        blk.upload(s, first, img_bytes() * m);
+        return blk.at(s);
+    }
+};
+
+// The block one launch sequence of an image stage should need; larger batches go chunk by chunk.  In the second library only
+// (-DCCAL_TEST_HOOKS) the environment variable `env` replaces the limit, so that a test cuts a small batch into chunks
+// (test_a_batch_cut_into_chunks of tests/test_gpu_detect.py, test_gpu_quads.py, test_gpu_tags.py, test_gpu_detect_tags.py); read on
+// every call.  static: the units of one library are compiled with and without the macro.
+static inline size_t test_chunk_bytes(const char* env, size_t dflt) {
+#ifdef CCAL_TEST_HOOKS
+    if (const char* e = std::getenv(env)) return (size_t)std::strtoull(e, nullptr, 10);
+#endif
+    (void)env;
+    return dflt;
+}
 
 }  // namespace ccal

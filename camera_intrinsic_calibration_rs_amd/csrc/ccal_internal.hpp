@@ -499,8 +499,8 @@ struct TagArgs {
     int32_t max_border, max_hamming;
     double min_contrast;
 };
-const char* tags_bad_params(int d, int border, const uint64_t* codes, int n_codes, int samples, double min_contrast, int max_border_errors,
-                            int max_hamming);
+const char* tags_bad_params(int d, int border, int n_codes, int samples, double min_contrast, int max_border_errors, int max_hamming);
+const char* tags_bad_codes(int d, const uint64_t* codes, int n_codes);       // the table, once the ranges hold
 hipError_t tags_enqueue(hipStream_t s, int dtype, const TagArgs& a);
 // ccal_kernels_tagchain.hip: the two decision kernels of ccal_detect_tags_* on device arrays (the second library's test entry points
 // run them alone, ccal_test_hooks.hip)

@@ -12,6 +12,7 @@
 // Every pixel index is clamped to the image; the inside test makes the clamp a no-op, the clamp stays as the guard.
 #include <cmath>
 #include "ccal_call.hpp"
+#include "ccal_image_device.hpp"
 
 namespace ccal {
 
@@ -20,23 +21,6 @@ constexpr int kCornerMaxHalf = 15;           // half_win 1 .. 15: a patch of at 
 constexpr int kCornerWTab = 2 * kCornerMaxHalf + 2;      // the weight table's room per wavefront (31 used)
 
 // CornerArgs: ccal_internal.hpp
-
-// producer and consumer are lanes of the same wavefront: LDS operations of one wave execute in order, this only keeps the compiler
-// from moving accesses across the hand-off
-__device__ __forceinline__ void corner_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// floor and fraction of one coordinate, the two neighbour indices clamped to [0, n - 1]
-__device__ __forceinline__ void corner_tap(double x, int32_t n, int32_t& i0, int32_t& i1, double& ax) {
-    const double f = floor(x);
-    ax = x - f;
-    const double hi = (double)(n - 1);
-    i0 = (int32_t)fmin(fmax(f, 0.0), hi);            // NaN: fmax gives 0
-    i1 = min(i0 + 1, n - 1);
-}
 
 template <class T>
 __global__ __launch_bounds__(64 * kCornerWaves) void k_corner_refine(const CornerArgs a) {
@@ -48,17 +32,11 @@ __global__ __launch_bounds__(64 * kCornerWaves) void k_corner_refine(const Corne
     double* P = corner_lds + (size_t)wave * (size_t)(ps * ps + kCornerWTab);
     double* w1 = P + ps * ps;
 
-    // the image of corner g: the last k with off[k] <= g (images without corners are stepped over)
-    int lo = 0, hi = a.n_img;
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (a.off[mid] <= g) lo = mid; else hi = mid;
-    }
-    const T* img = static_cast<const T*>(a.img) + (int64_t)lo * a.W * a.H;
+    const T* img = static_cast<const T*>(a.img) + (int64_t)image_of_row(a.off, a.n_img, g) * a.W * a.H;
     const int32_t W = a.W, H = a.H;
 
     if (lane < side) { const double t = (double)(lane - h) / (double)h; w1[lane] = exp(-(t * t)); }
-    corner_lds_sync();
+    wave_handoff();
     double sw = 0.0;
     for (int i = 0; i < side; ++i) sw += w1[i];
     const double sum_w = sw * sw;
@@ -74,18 +52,9 @@ __global__ __launch_bounds__(64 * kCornerWaves) void k_corner_refine(const Corne
         if (!inside) { status = CCAL_NO_RESULT; break; }
         for (int p = lane; p < ps * ps; p += 64) {
             const int pj = p / ps, pi = p - pj * ps;
-            int32_t x0, x1, y0, y1;
-            double ax, ay;
-            corner_tap(cx + (double)(pi - h - 1), W, x0, x1, ax);
-            corner_tap(cy + (double)(pj - h - 1), H, y0, y1, ay);
-            const T* r0 = img + (int64_t)y0 * W;
-            const T* r1 = img + (int64_t)y1 * W;
-            const double p00 = (double)r0[x0], p01 = (double)r0[x1], p10 = (double)r1[x0], p11 = (double)r1[x1];
-            // the difference form: a constant neighbourhood samples to exactly its value, whatever the fractions
-            const double top = p00 + ax * (p01 - p00), bot = p10 + ax * (p11 - p10);
-            P[p] = top + ay * (bot - top);
+            P[p] = image_sample(img, W, H, cx + (double)(pi - h - 1), cy + (double)(pj - h - 1));
         }
-        corner_lds_sync();
+        wave_handoff();
         double sa = 0.0, sb = 0.0, sd = 0.0, su = 0.0, sv = 0.0;
         for (int p = lane; p < side * side; p += 64) {
             const int wj = p / side, wi = p - wj * side;
@@ -98,7 +67,7 @@ __global__ __launch_bounds__(64 * kCornerWaves) void k_corner_refine(const Corne
             su += w * (xx * di + xy * dj);
             sv += w * (xy * di + yy * dj);
         }
-        corner_lds_sync();                 // the next iterate's patch is written after every lane has read this one
+        wave_handoff();                 // the next iterate's patch is written after every lane has read this one
         for (int off = 32; off > 0; off >>= 1) {
             sa += __shfl_xor(sa, off, 64); sb += __shfl_xor(sb, off, 64); sd += __shfl_xor(sd, off, 64);
             su += __shfl_xor(su, off, 64); sv += __shfl_xor(sv, off, 64);
@@ -140,29 +109,26 @@ hipError_t corners_enqueue(hipStream_t s, int dtype, const CornerArgs& a) {
 
 namespace {
 
-int corners_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
-                 const int64_t* offsets, double* xy_io, int half_win, int max_iterations, double eps, int32_t* status_out,
-                 int32_t* iters_out, double* lambda_min_out) {
+int corners_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, const int64_t* offsets, double* xy_io, int half_win, int max_iterations,
+                 double eps, int32_t* status_out, int32_t* iters_out, double* lambda_min_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
     if (const char* what = corners_bad_params(half_win, max_iterations, eps)) return bad(what);
-    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
-    if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
-    if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
+    if (const char* what = b.bad()) return bad(what);
+    const int n_img = b.n_img;
     if (n_img == 0) return CCAL_OK;
-    if (!images || !offsets || !status_out) return bad("NULL argument");
+    if (!b.images || !offsets || !status_out) return bad("NULL argument");
     if (check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
     const int64_t n64 = offsets[n_img];
     if (n64 > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 corners");
     if (n64 == 0) return CCAL_OK;
     if (!xy_io) return bad("NULL argument");
     const size_t n = (size_t)n64, ni = (size_t)n_img;
-    const size_t b_img = images_on_device ? 0 : (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height * ni;
 
     // one block: offsets | images (host call) | corners, lambda_min | status, iterations
     CallBlock blk(ctx);
     const auto s_off = blk.add<int64_t>(ni + 1);
-    const auto s_img = blk.add<char>(b_img);
+    const auto s_img = blk.add<char>(b.staged_bytes(ni));
     const auto s_xy = blk.add<double>(2 * n);
     const auto s_lam = blk.add<double>(n);
     const auto s_status = blk.add<int32_t>(n);
@@ -170,13 +136,12 @@ int corners_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dt
     if (!blk.alloc()) return blk.finish(where);
     blk.poison(s_xy, s_lam);
     CornerArgs a = {};
-    a.img = images_on_device ? images : (const void*)blk.at(s_img);
     a.off = blk.at(s_off); a.xy = blk.at(s_xy); a.lam = blk.at(s_lam); a.status = blk.at(s_status); a.iters = blk.at(s_iters);
-    a.n = n64; a.W = width; a.H = height; a.n_img = n_img; a.h = half_win; a.max_it = max_iterations; a.eps = eps;
+    a.n = n64; a.W = b.width; a.H = b.height; a.n_img = n_img; a.h = half_win; a.max_it = max_iterations; a.eps = eps;
     blk.upload(s_off, offsets, ni + 1);
-    if (!images_on_device) blk.upload(s_img, images, b_img);
+    a.img = b.chunk(blk, s_img, 0, ni);
     blk.upload(s_xy, xy_io, 2 * n);
-    if (blk.ok()) blk.note(corners_enqueue(ctx->stream, dtype, a));
+    if (blk.ok()) blk.note(corners_enqueue(ctx->stream, b.dtype, a));
     blk.download(xy_io, a.xy, 2 * n);
     blk.download(status_out, a.status, n);
     blk.download(iters_out, a.iters, n);
@@ -196,8 +161,8 @@ int ccal_refine_corners_batch(ccal_ctx* ctx, int dtype, int width, int height, i
                               double* lambda_min_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return corners_call(ctx, "ccal_refine_corners_batch", false, dtype, width, height, n_img, images, offsets, xy_io, half_win,
-                        max_iterations, eps, status_out, iters_out, lambda_min_out);
+    return corners_call(ctx, "ccal_refine_corners_batch", GreyBatch{ dtype, width, height, n_img, images, false }, offsets, xy_io,
+                        half_win, max_iterations, eps, status_out, iters_out, lambda_min_out);
     CCAL_API_CATCH(ctx)
 }
 
@@ -206,8 +171,8 @@ int ccal_refine_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int
                             double* lambda_min_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return corners_call(ctx, "ccal_refine_corners_dev", true, dtype, width, height, n_img, images_dev, offsets, xy_io, half_win,
-                        max_iterations, eps, status_out, iters_out, lambda_min_out);
+    return corners_call(ctx, "ccal_refine_corners_dev", GreyBatch{ dtype, width, height, n_img, images_dev, true }, offsets, xy_io,
+                        half_win, max_iterations, eps, status_out, iters_out, lambda_min_out);
     CCAL_API_CATCH(ctx)
 }
 

@@ -14,10 +14,11 @@
 //                   offset: row-major order of (y, x) by construction.  Candidates past cap are counted, not stored.
 // No per-pixel response map leaves the LDS.  Every global index is guarded by the image / slot / row bounds it was sized with.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 #include "ccal_call.hpp"
+#include "ccal_image_device.hpp"
+#include "ccal_image_plan.hpp"
 
 namespace ccal {
 
@@ -25,14 +26,6 @@ constexpr int kDetTile = 32;                  // the tile's side in domain pixel
 constexpr int kDetThreads = 256;
 constexpr int kDetMaxStep = 4, kDetMaxRadius = 15;
 constexpr size_t kDetChunkBytes = (size_t)256 << 20;      // the workspace one block should hold: larger batches go in chunks
-// the second library only (-DCCAL_TEST_HOOKS): CCAL_TEST_DETECT_CHUNK_BYTES replaces the limit, so that a test cuts a batch of small
-// images into chunks (tests/test_gpu_detect.py); read on every call
-inline size_t det_chunk_bytes() {
-#ifdef CCAL_TEST_HOOKS
-    if (const char* e = std::getenv("CCAL_TEST_DETECT_CHUNK_BYTES")) return (size_t)std::strtoull(e, nullptr, 10);
-#endif
-    return kDetChunkBytes;
-}
 constexpr int64_t kDetNone = INT64_MIN;       // R of a pixel outside the domain: it never competes
 
 // DetectArgs: ccal_internal.hpp
@@ -169,11 +162,7 @@ __global__ __launch_bounds__(kDetThreads) void k_detect_rows(const DetectArgs a)
         const int row = base + tid;
         int32_t c = 0;
         if (row < a.dh && T != INT64_MAX) det_row_slots(a, k, row, T, [&](int64_t, int32_t) { ++c; });
-        int32_t inc = c;                               // inclusive scan within the wavefront
-        for (int off = 1; off < 64; off <<= 1) {
-            const int32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const int32_t inc = wave_scan_inclusive(c, lane);
         if (lane == 63) wave_sum[wave] = inc;
         __syncthreads();
         int32_t front = 0, total = 0;
@@ -232,37 +221,34 @@ hipError_t detect_enqueue_emit(hipStream_t s, const DetectArgs& a) {
 
 namespace {
 
-int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
-                int step, int nms_radius, int64_t min_response, int rel_q10, int cap, int32_t* count_out, int32_t* xy_out,
-                int32_t* hess_out, int64_t* response_out) {
+int detect_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int step, int nms_radius, int64_t min_response, int rel_q10, int cap,
+                int32_t* count_out, int32_t* xy_out, int32_t* hess_out, int64_t* response_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
     if (const char* what = detect_bad_params(step, nms_radius, min_response, rel_q10, cap)) return bad(what);
-    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
-    if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
-    if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
+    if (const char* what = b.bad()) return bad(what);
+    const int n_img = b.n_img;
     if (n_img == 0) return CCAL_OK;
-    if (!images || !count_out || !xy_out || !hess_out) return bad("NULL argument");
+    if (!b.images || !count_out || !xy_out || !hess_out) return bad("NULL argument");
 
-    const int d0 = step + 2, dw = width - 2 * d0, dh = height - 2 * d0, r = nms_radius;
-    if (dw <= 0 || dh <= 0) {                          // no domain: nothing to launch
+    const DetectDomain dm = detect_domain(b.width, b.height, step, nms_radius);
+    if (!dm.dw) {                                      // no domain: nothing to launch
         std::fill(count_out, count_out + n_img, 0);
         return CCAL_OK;
     }
-    const int nbx = (dw + r) / (r + 1), nby = (dh + r) / (r + 1);
-    const size_t nb = (size_t)nbx * (size_t)nby, rows_cap = std::min<size_t>((size_t)cap, nb);
-    const size_t img_bytes = (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height;
-    const size_t per_image = nb * 24 + (size_t)dh * 4 + rows_cap * 24 + (images_on_device ? 0 : img_bytes) + 64;
-    const size_t nc = std::min<size_t>(std::min<size_t>((size_t)n_img, 65535), std::max<size_t>(det_chunk_bytes() / per_image, 1));
+    const size_t nb = dm.slots(), dh = (size_t)dm.dh, rows_cap = std::min<size_t>((size_t)cap, nb);
+    const size_t per_image = nb * 24 + dh * 4 + rows_cap * 24 + b.staged_bytes(1) + 64;
+    const size_t limit = test_chunk_bytes("CCAL_TEST_DETECT_CHUNK_BYTES", kDetChunkBytes);
+    const size_t nc = std::min<size_t>(std::min<size_t>((size_t)n_img, 65535), std::max<size_t>(limit / per_image, 1));
 
     // one block for the largest chunk: images (host call) | slots | rows, counts, offsets | the stored rows
     CallBlock blk(ctx);
-    const auto s_img = blk.add<char>(images_on_device ? 0 : img_bytes * nc);
+    const auto s_img = blk.add<char>(b.staged_bytes(nc));
     const auto s_pix = blk.add<int32_t>(nb * nc);
     const auto s_rmax = blk.add<long long>(nc);
     const auto s_hess = blk.add<int32_t>(3 * nb * nc);
     const auto s_resp = blk.add<int64_t>(nb * nc);
-    const auto s_rowoff = blk.add<int32_t>((size_t)dh * nc);
+    const auto s_rowoff = blk.add<int32_t>(dh * nc);
     const auto s_count = blk.add<int32_t>(nc);
     const auto s_imgoff = blk.add<int64_t>(nc + 1);
     const auto s_oxy = blk.add<int32_t>(2 * rows_cap * nc);
@@ -271,8 +257,8 @@ int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dty
     if (!blk.alloc()) return blk.finish(where);
 
     DetectArgs a = {};
-    a.W = width; a.H = height; a.s = step; a.r = r; a.rel_q10 = rel_q10; a.cap = cap; a.min_response = min_response;
-    a.d0 = d0; a.dw = dw; a.dh = dh; a.nbx = nbx; a.nby = nby;
+    a.W = b.width; a.H = b.height; a.s = step; a.r = nms_radius; a.rel_q10 = rel_q10; a.cap = cap; a.min_response = min_response;
+    a.d0 = dm.d0; a.dw = dm.dw; a.dh = dm.dh; a.nbx = dm.nbx; a.nby = dm.nby;
     a.pix = blk.at(s_pix); a.hess = blk.at(s_hess); a.resp = blk.at(s_resp); a.rmax = blk.at(s_rmax);
     a.rowoff = blk.at(s_rowoff); a.count = blk.at(s_count); a.imgoff = blk.at(s_imgoff);
     a.oxy = blk.at(s_oxy); a.ohess = blk.at(s_ohess); a.oresp = blk.at(s_oresp);
@@ -283,11 +269,10 @@ int detect_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dty
     for (size_t k0 = 0; k0 < (size_t)n_img && blk.ok(); k0 += nc) {
         const size_t m = std::min(nc, (size_t)n_img - k0);
         a.n = (int32_t)m;
-        a.img = images_on_device ? (const void*)(static_cast<const char*>(images) + k0 * img_bytes) : (const void*)blk.at(s_img);
         blk.poison(s_hess, s_resp);                    // the test hook's 0xFF over what the kernels write before they read it:
         blk.poison(s_oxy, s_oresp);                    // the slots' payload and the stored rows (not the indices, counts and offsets)
-        if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
-        if (blk.ok()) blk.note(detect_enqueue_find(ctx->stream, dtype, a));
+        a.img = b.chunk(blk, s_img, k0, m);
+        if (blk.ok()) blk.note(detect_enqueue_find(ctx->stream, b.dtype, a));
         blk.download(count_out + k0, a.count, m);
         if (blk.ok()) blk.note(hipStreamSynchronize(ctx->stream));
         if (!blk.ok()) break;
@@ -327,7 +312,7 @@ int ccal_detect_corners_batch(ccal_ctx* ctx, int dtype, int width, int height, i
                               int64_t* response_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return detect_call(ctx, "ccal_detect_corners_batch", false, dtype, width, height, n_img, images, step, nms_radius, min_response,
+    return detect_call(ctx, "ccal_detect_corners_batch", GreyBatch{ dtype, width, height, n_img, images, false }, step, nms_radius, min_response,
                        rel_q10, cap, count_out, xy_out, hess_out, response_out);
     CCAL_API_CATCH(ctx)
 }
@@ -337,7 +322,7 @@ int ccal_detect_corners_dev(ccal_ctx* ctx, int dtype, int width, int height, int
                             int64_t* response_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return detect_call(ctx, "ccal_detect_corners_dev", true, dtype, width, height, n_img, images_dev, step, nms_radius, min_response,
+    return detect_call(ctx, "ccal_detect_corners_dev", GreyBatch{ dtype, width, height, n_img, images_dev, true }, step, nms_radius, min_response,
                        rel_q10, cap, count_out, xy_out, hess_out, response_out);
     CCAL_API_CATCH(ctx)
 }

@@ -16,11 +16,11 @@
 // and sum on its own.  Every pixel index is clamped to the image; the inside test makes the clamp a no-op, the clamp stays as the guard.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 #include "ccal_call.hpp"
-#include "ccal_quads_plan.hpp"
+#include "ccal_image_device.hpp"
+#include "ccal_image_plan.hpp"
 
 namespace ccal {
 
@@ -29,51 +29,15 @@ constexpr int kQuadMaxOut = CCAL_QUAD_MAX_OUT_EDGES;
 constexpr int kQuadMaxSamples = 16;
 constexpr size_t kQuadChunkBytes = (size_t)256 << 20;     // the block one launch should need: larger batches go image chunk by chunk
 static_assert(kQuadMaxOut == 8, "a pass of 64 lanes is one i and all (j, k)");
-// the second library only (-DCCAL_TEST_HOOKS): CCAL_TEST_QUADS_CHUNK_BYTES replaces the limit, so that a test cuts a small batch
-// into chunks (tests/test_gpu_quads.py); read on every call
-inline size_t quad_chunk_bytes() {
-#ifdef CCAL_TEST_HOOKS
-    if (const char* e = std::getenv("CCAL_TEST_QUADS_CHUNK_BYTES")) return (size_t)std::strtoull(e, nullptr, 10);
-#endif
-    return kQuadChunkBytes;
-}
 
 // QuadArgs: ccal_internal.hpp
 
 // the point of wavefront g: its image k (the last with off[k] <= p0 + g; images without points are stepped over), the chunk
 // index of the image's first point, the image's point count
 __device__ __forceinline__ void quad_locate(const QuadArgs& a, int64_t g, int& k, int64_t& first, int& m) {
-    const int64_t gp = a.p0 + g;
-    int lo = 0, hi = a.n_img;
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (a.off[mid] <= gp) lo = mid; else hi = mid;
-    }
-    k = lo;
-    first = a.off[lo] - a.p0;
-    m = (int)(a.off[lo + 1] - a.off[lo]);
-}
-
-// floor and fraction of one coordinate, the two neighbour indices clamped to [0, n - 1]
-__device__ __forceinline__ void quad_tap(double x, int32_t n, int32_t& i0, int32_t& i1, double& ax) {
-    const double f = floor(x);
-    ax = x - f;
-    const double hi = (double)(n - 1);
-    i0 = (int32_t)fmin(fmax(f, 0.0), hi);            // NaN: fmax gives 0
-    i1 = min(i0 + 1, n - 1);
-}
-
-template <class T>
-__device__ __forceinline__ double quad_sample(const T* img, int32_t W, int32_t H, double x, double y) {
-    int32_t x0, x1, y0, y1;
-    double ax, ay;
-    quad_tap(x, W, x0, x1, ax);
-    quad_tap(y, H, y0, y1, ay);
-    const T* r0 = img + (int64_t)y0 * W;
-    const T* r1 = img + (int64_t)y1 * W;
-    const double p00 = (double)r0[x0], p01 = (double)r0[x1], p10 = (double)r1[x0], p11 = (double)r1[x1];
-    const double top = p00 + ax * (p01 - p00), bot = p10 + ax * (p11 - p10);
-    return top + ay * (bot - top);
+    k = image_of_row(a.off, a.n_img, a.p0 + g);
+    first = a.off[k] - a.p0;
+    m = (int)(a.off[k + 1] - a.off[k]);
 }
 
 template <class T>
@@ -106,8 +70,8 @@ __global__ __launch_bounds__(64 * kQuadWaves) void k_quad_edges(const QuadArgs a
                     const double xi = px + nx, yi = py + ny, xo = px - nx, yo = py - ny;
                     edge = xi >= 0.0 && xi <= x_hi && yi >= 0.0 && yi <= y_hi && xo >= 0.0 && xo <= x_hi && yo >= 0.0 && yo <= y_hi;
                     if (edge) {
-                        dark = fmax(dark, quad_sample(img, a.W, a.H, xi, yi));
-                        bright = fmin(bright, quad_sample(img, a.W, a.H, xo, yo));
+                        dark = fmax(dark, image_sample(img, a.W, a.H, xi, yi));
+                        bright = fmin(bright, image_sample(img, a.W, a.H, xo, yo));
                         edge = bright - dark >= a.min_contrast;      // it only falls from here on
                     }
                 }
@@ -219,17 +183,16 @@ hipError_t quads_enqueue_write(hipStream_t s, const QuadArgs& a) {
 
 namespace {
 
-int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
-               const int64_t* offsets, const double* xy, double min_side, double max_side, double max_side_ratio, double offset,
-               int samples, double min_contrast, int cap, int32_t* count_out, int32_t* flags_out, int32_t* idx_out, double* quads_out) {
+int quads_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, const int64_t* offsets, const double* xy, double min_side, double max_side,
+               double max_side_ratio, double offset, int samples, double min_contrast, int cap, int32_t* count_out, int32_t* flags_out,
+               int32_t* idx_out, double* quads_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
     if (const char* what = quads_bad_params(min_side, max_side, max_side_ratio, offset, samples, min_contrast, cap)) return bad(what);
-    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
-    if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
-    if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
+    if (const char* what = b.bad()) return bad(what);
+    const int n_img = b.n_img;
     if (n_img == 0) return CCAL_OK;
-    if (!images || !offsets || !count_out || !flags_out || !idx_out) return bad("NULL argument");
+    if (!b.images || !offsets || !count_out || !flags_out || !idx_out) return bad("NULL argument");
     if (check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
     if (offsets[n_img] > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 points");
     for (int k = 0; k < n_img; ++k)
@@ -240,20 +203,17 @@ int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtyp
     if (offsets[n_img] == 0) return CCAL_OK;
 
     // chunks of whole images: as many as keep the chunk's images (host call), points and work arrays within the limit, at least one
-    const size_t ni = (size_t)n_img, img_bytes = (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height;
     static_assert(kQuadPerPointBytes == 2 * sizeof(double) + (kQuadMaxOut + 3) * sizeof(int32_t), "xy | adj | deg, cnt, base");
-    const std::vector<size_t> cut = quad_chunk_cuts(offsets, ni, quad_per_image_bytes(images_on_device, img_bytes), quad_chunk_bytes());
-    size_t max_img = 0, max_pts = 0;
-    for (size_t c = 0; c + 1 < cut.size(); ++c) {
-        max_img = std::max(max_img, cut[c + 1] - cut[c]);
-        max_pts = std::max(max_pts, (size_t)(offsets[cut[c + 1]] - offsets[cut[c]]));
-    }
+    const ImageChunks plan = image_chunks(offsets, (size_t)n_img, b.staged_bytes(1) + kQuadPerImageBytes, kQuadPerPointBytes,
+                                          test_chunk_bytes("CCAL_TEST_QUADS_CHUNK_BYTES", kQuadChunkBytes));
+    const std::vector<size_t>& cut = plan.cut;
+    const size_t max_img = plan.max_img, max_pts = plan.max_rows;
 
     // one block for the largest chunk: offsets, row offsets | images (host call) | points | lists, degrees, counts, bases
     CallBlock blk(ctx);
     const auto s_off = blk.add<int64_t>(max_img + 1);
     const auto s_rowoff = blk.add<int64_t>(max_img + 1);
-    const auto s_img = blk.add<char>(images_on_device ? 0 : img_bytes * max_img);
+    const auto s_img = blk.add<char>(b.staged_bytes(max_img));
     const auto s_xy = blk.add<double>(2 * max_pts);
     const auto s_adj = blk.add<int32_t>(kQuadMaxOut * max_pts);
     const auto s_deg = blk.add<int32_t>(max_pts);
@@ -264,7 +224,7 @@ int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtyp
     QuadArgs a = {};
     a.off = blk.at(s_off); a.rowoff = blk.at(s_rowoff); a.xy = blk.at(s_xy);
     a.adj = blk.at(s_adj); a.deg = blk.at(s_deg); a.cnt = blk.at(s_cnt); a.base = blk.at(s_base);
-    a.W = width; a.H = height;
+    a.W = b.width; a.H = b.height;
     quads_set_params(a, min_side, max_side, max_side_ratio, offset, samples, min_contrast, cap);
     std::vector<int32_t> h_deg(max_pts), h_cnt(max_pts), h_base(max_pts), h_idx;
     std::vector<int64_t> rowoff(max_img + 1);
@@ -275,11 +235,10 @@ int quads_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtyp
         const size_t at = (size_t)offsets[k0], np = (size_t)(offsets[k0 + m] - offsets[k0]);
         if (!np) continue;
         a.n_img = (int32_t)m; a.p0 = offsets[k0]; a.n = (int64_t)np;
-        a.img = images_on_device ? (const void*)(static_cast<const char*>(images) + k0 * img_bytes) : (const void*)blk.at(s_img);
         blk.upload(s_off, offsets + k0, m + 1);
-        if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
+        a.img = b.chunk(blk, s_img, k0, m);
         blk.upload(s_xy, xy + 2 * at, 2 * np);
-        if (blk.ok()) blk.note(quads_enqueue_count(ctx->stream, dtype, a));
+        if (blk.ok()) blk.note(quads_enqueue_count(ctx->stream, b.dtype, a));
         blk.download(h_deg.data(), a.deg, np);
         blk.download(h_cnt.data(), a.cnt, np);
         if (blk.ok()) blk.note(hipStreamSynchronize(ctx->stream));
@@ -341,8 +300,8 @@ int ccal_propose_quads_batch(ccal_ctx* ctx, int dtype, int width, int height, in
                              double min_contrast, int cap, int32_t* count_out, int32_t* flags_out, int32_t* idx_out, double* quads_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return quads_call(ctx, "ccal_propose_quads_batch", false, dtype, width, height, n_img, images, offsets, xy, min_side, max_side,
-                      max_side_ratio, offset, samples, min_contrast, cap, count_out, flags_out, idx_out, quads_out);
+    return quads_call(ctx, "ccal_propose_quads_batch", GreyBatch{ dtype, width, height, n_img, images, false }, offsets, xy, min_side,
+                      max_side, max_side_ratio, offset, samples, min_contrast, cap, count_out, flags_out, idx_out, quads_out);
     CCAL_API_CATCH(ctx)
 }
 
@@ -351,8 +310,8 @@ int ccal_propose_quads_dev(ccal_ctx* ctx, int dtype, int width, int height, int 
                            double min_contrast, int cap, int32_t* count_out, int32_t* flags_out, int32_t* idx_out, double* quads_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return quads_call(ctx, "ccal_propose_quads_dev", true, dtype, width, height, n_img, images_dev, offsets, xy, min_side, max_side,
-                      max_side_ratio, offset, samples, min_contrast, cap, count_out, flags_out, idx_out, quads_out);
+    return quads_call(ctx, "ccal_propose_quads_dev", GreyBatch{ dtype, width, height, n_img, images_dev, true }, offsets, xy, min_side,
+                      max_side, max_side_ratio, offset, samples, min_contrast, cap, count_out, flags_out, idx_out, quads_out);
     CCAL_API_CATCH(ctx)
 }
 

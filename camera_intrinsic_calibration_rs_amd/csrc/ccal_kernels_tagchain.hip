@@ -17,32 +17,16 @@
 // Comparisons and conversions only: no sum or product whose rounding a yardstick would have to follow.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 #include "ccal_call.hpp"
+#include "ccal_image_device.hpp"
 #include "ccal_tagchain_plan.hpp"
 
 namespace ccal {
 
 constexpr int kMergeLds = 2048;               // kept points held in LDS: 16 KB
 constexpr size_t kChainChunkBytes = (size_t)256 << 20;    // the block one chunk should need: larger batches go image chunk by chunk
-// the second library only (-DCCAL_TEST_HOOKS): CCAL_TEST_TAGCHAIN_CHUNK_BYTES replaces the limit, so that a test cuts a small batch
-// into chunks (tests/test_gpu_detect_tags.py); read on every call
-inline size_t chain_chunk_bytes() {
-#ifdef CCAL_TEST_HOOKS
-    if (const char* e = std::getenv("CCAL_TEST_TAGCHAIN_CHUNK_BYTES")) return (size_t)std::strtoull(e, nullptr, 10);
-#endif
-    return kChainChunkBytes;
-}
-
-// producer and consumer are lanes of the same wavefront: its memory operations execute in order, this keeps the compiler from
-// moving accesses across the hand-off
-__device__ __forceinline__ void chain_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ int chain_span(const int64_t* off, int k, int cap) {
     const int64_t m = off[k + 1] - off[k];
@@ -61,11 +45,7 @@ __global__ __launch_bounds__(64) void k_chain_offsets(const int32_t* __restrict_
     for (int b0 = 0; b0 < n; b0 += 64) {
         const int i = b0 + lane;
         const int32_t c = i < n ? min(max(count[i], 0), cap) : 0;
-        int32_t inc = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int32_t o = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += o;
-        }
+        const int32_t inc = wave_scan_inclusive(c, lane);
         if (i < n) off[i + 1] = carry + inc;
         carry += __shfl(inc, 63, 64);
     }
@@ -103,7 +83,7 @@ __global__ __launch_bounds__(64) void k_chain_merge(const MergeArgs a) {
                     if (nk < kMergeLds) { kx[nk] = cx; ky[nk] = cy; }
                 }
                 ++nk;
-                chain_wave_sync();                       // the next candidate's test reads this point
+                wave_handoff();                       // the next candidate's test reads this point
             }
         }
     }
@@ -131,11 +111,7 @@ __global__ __launch_bounds__(64) void k_chain_quad_scan(const int64_t* __restric
         const int i = b0 + lane;
         const int32_t c = i < m ? cnt[first + i] : 0;
         cut = cut || (i < m && deg[first + i] > CCAL_QUAD_MAX_OUT_EDGES);
-        int32_t inc = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int32_t o = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += o;
-        }
+        const int32_t inc = wave_scan_inclusive(c, lane);
         if (i < m) base[first + i] = carry + inc - c;
         carry += __shfl(inc, 63, 64);
     }
@@ -167,7 +143,7 @@ __global__ __launch_bounds__(64) void k_chain_select(const SelectArgs a) {
         if (i < q) win[i] = ok && !beaten ? 1 : 0;
         n_ok += __popcll(__ballot(ok));
     }
-    chain_wave_sync();
+    wave_handoff();
     int count = 0;
     for (int i0 = 0; i0 < q; i0 += 64) {
         const int i = i0 + lane;
@@ -207,8 +183,8 @@ struct ChainOut {
     int32_t* count; int32_t* id; int32_t* rot; int32_t* hamming; double* corners; double* margin; int32_t* flags; int32_t* stats;
 };
 
-int tagchain_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
-                  int d, const uint64_t* codes, int n_codes, const ccal_detect_tags_opts* o, const ChainOut& out) {
+int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, const uint64_t* codes, int n_codes,
+                  const ccal_detect_tags_opts* o, const ChainOut& out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
     if (!o) return bad("NULL options");
@@ -218,36 +194,35 @@ int tagchain_call(ccal_ctx* ctx, const char* where, bool images_on_device, int d
     if (!(o->merge_radius >= 0.0) || !std::isfinite(o->merge_radius)) return bad("merge_radius negative or not finite");
     if (const char* what = quads_bad_params(o->min_side, o->max_side, o->max_side_ratio, o->offset, o->edge_samples, o->edge_min_contrast,
                                             o->quad_cap)) return bad(what);
-    if (const char* what = tags_bad_params(d, o->border, nullptr, n_codes, o->cell_samples, o->tag_min_contrast, o->max_border_errors,
-                                           o->max_hamming)) return bad(what);
+    if (const char* what = tags_bad_params(d, o->border, n_codes, o->cell_samples, o->tag_min_contrast, o->max_border_errors, o->max_hamming))
+        return bad(what);
     if (o->tag_cap < 1) return bad("tag_cap < 1");
-    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
-    if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
-    if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
-    if (const char* what = tags_bad_params(d, o->border, codes, n_codes, o->cell_samples, o->tag_min_contrast, o->max_border_errors,
-                                           o->max_hamming)) return bad(what);
-    if (n_img == 0) return CCAL_OK;
-    if (!images || !codes || !out.count || !out.id || !out.rot || !out.hamming || !out.corners || !out.flags) return bad("NULL argument");
+    if (const char* what = b.bad()) return bad(what);
+    if (const char* what = tags_bad_codes(d, codes, n_codes)) return bad(what);
+    if (b.n_img == 0) return CCAL_OK;
+    if (!b.images || !codes || !out.count || !out.id || !out.rot || !out.hamming || !out.corners || !out.flags) return bad("NULL argument");
 
-    const size_t ni = (size_t)n_img, tag_cap = (size_t)o->tag_cap;
+    const int dtype = b.dtype, width = b.width, height = b.height;
+    const size_t ni = (size_t)b.n_img, tag_cap = (size_t)o->tag_cap;
     std::fill(out.count, out.count + ni, 0);
     std::fill(out.flags, out.flags + ni, 0);
     if (out.stats) std::fill(out.stats, out.stats + 4 * ni, 0);
     const ChainShape sh = chain_shape((size_t)width, (size_t)height, dtype == CCAL_PIX_U16 ? 2 : 1, (size_t)o->step, (size_t)o->nms_radius,
                                       (size_t)o->cand_cap, (size_t)o->quad_cap, tag_cap, (size_t)n_codes);
     if (!sh.slots) return CCAL_OK;                        // no domain: nothing to launch
-    const size_t C = sh.cand, Q = sh.quads, T = sh.tags, img_bytes = sh.img_bytes;
-    const size_t nc = chain_images_per_chunk(ni, chain_per_image_bytes(images_on_device, sh), chain_chunk_bytes());
+    const size_t C = sh.cand, Q = sh.quads, T = sh.tags, dh = (size_t)sh.dom.dh;
+    const size_t nc = chain_images_per_chunk(ni, chain_per_image_bytes(b.on_device, sh),
+                                             test_chunk_bytes("CCAL_TEST_TAGCHAIN_CHUNK_BYTES", kChainChunkBytes));
 
     // one block for the largest chunk.  The doubles the kernels write before they read lie together: one poison covers them.
     CallBlock blk(ctx);
     const auto s_codes = blk.add<unsigned long long>((size_t)n_codes);
-    const auto s_img = blk.add<char>(images_on_device ? 0 : img_bytes * nc);
+    const auto s_img = blk.add<char>(b.staged_bytes(nc));
     const auto s_pix = blk.add<int32_t>(sh.slots * nc);
     const auto s_rmax = blk.add<long long>(nc);
     const auto s_hess = blk.add<int32_t>(3 * sh.slots * nc);
     const auto s_resp = blk.add<int64_t>(sh.slots * nc);
-    const auto s_rowoff = blk.add<int32_t>(sh.dh * nc);
+    const auto s_rowoff = blk.add<int32_t>(dh * nc);
     const auto s_count = blk.add<int32_t>(nc);
     const auto s_candoff = blk.add<int64_t>(nc + 1);
     const auto s_oxy = blk.add<int32_t>(2 * C * nc);
@@ -290,8 +265,7 @@ int tagchain_call(ccal_ctx* ctx, const char* where, bool images_on_device, int d
     DetectArgs da = {};
     da.W = width; da.H = height; da.s = o->step; da.r = o->nms_radius; da.rel_q10 = o->rel_q10; da.cap = o->cand_cap;
     da.min_response = o->min_response;
-    da.d0 = o->step + 2; da.dw = (int32_t)sh.dw; da.dh = (int32_t)sh.dh;
-    da.nbx = (da.dw + da.r) / (da.r + 1); da.nby = (da.dh + da.r) / (da.r + 1);
+    da.d0 = sh.dom.d0; da.dw = sh.dom.dw; da.dh = sh.dom.dh; da.nbx = sh.dom.nbx; da.nby = sh.dom.nby;
     da.pix = blk.at(s_pix); da.hess = blk.at(s_hess); da.resp = blk.at(s_resp); da.rmax = blk.at(s_rmax);
     da.rowoff = blk.at(s_rowoff); da.count = blk.at(s_count); da.imgoff = blk.at(s_candoff);
     da.oxy = blk.at(s_oxy); da.ohess = blk.at(s_ohess); da.oresp = blk.at(s_oresp);
@@ -331,10 +305,8 @@ int tagchain_call(ccal_ctx* ctx, const char* where, bool images_on_device, int d
     for (size_t k0 = 0; k0 < ni && blk.ok(); k0 += nc) {
         const size_t m = std::min(nc, ni - k0);
         da.n = ca.n_img = ma.n_img = qa.n_img = ta.n_img = sa.n_img = (int32_t)m;
-        const void* img = images_on_device ? (const void*)(static_cast<const char*>(images) + k0 * img_bytes) : (const void*)blk.at(s_img);
-        da.img = ca.img = qa.img = ta.img = img;
         blk.poison(s_xy, s_tmargin);                      // the test hook's NaN over the doubles the kernels write before they read
-        if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
+        da.img = ca.img = qa.img = ta.img = b.chunk(blk, s_img, k0, m);
         std::fill(h_kept.begin(), h_kept.end(), 0); std::fill(h_qcount.begin(), h_qcount.end(), 0);
         std::fill(h_qflags.begin(), h_qflags.end(), 0); std::fill(h_ntags.begin(), h_ntags.end(), 0); std::fill(h_nok.begin(), h_nok.end(), 0);
 
@@ -431,7 +403,7 @@ int ccal_detect_tags_batch(ccal_ctx* ctx, int dtype, int width, int height, int 
                            int32_t* hamming_out, double* corners_out, double* margin_out, int32_t* flags_out, int32_t* stats_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return tagchain_call(ctx, "ccal_detect_tags_batch", false, dtype, width, height, n_img, images, d, codes, n_codes, opts,
+    return tagchain_call(ctx, "ccal_detect_tags_batch", GreyBatch{ dtype, width, height, n_img, images, false }, d, codes, n_codes, opts,
                          ChainOut{ count_out, id_out, rot_out, hamming_out, corners_out, margin_out, flags_out, stats_out });
     CCAL_API_CATCH(ctx)
 }
@@ -441,7 +413,7 @@ int ccal_detect_tags_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_
                          int32_t* hamming_out, double* corners_out, double* margin_out, int32_t* flags_out, int32_t* stats_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return tagchain_call(ctx, "ccal_detect_tags_dev", true, dtype, width, height, n_img, images_dev, d, codes, n_codes, opts,
+    return tagchain_call(ctx, "ccal_detect_tags_dev", GreyBatch{ dtype, width, height, n_img, images_dev, true }, d, codes, n_codes, opts,
                          ChainOut{ count_out, id_out, rot_out, hamming_out, corners_out, margin_out, flags_out, stats_out });
     CCAL_API_CATCH(ctx)
 }

@@ -17,9 +17,10 @@
 // no-op, the clamp stays as the guard.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <vector>
 #include "ccal_call.hpp"
+#include "ccal_image_device.hpp"
+#include "ccal_image_plan.hpp"
 
 namespace ccal {
 
@@ -28,25 +29,8 @@ constexpr int kTagMaxSide = 12;               // n = d + 2 border <= 12: at most
 constexpr int kTagCellChunks = 3;             // cells per lane
 constexpr int kTagFamChunk = 512;             // codes staged at a time: 4 KB of LDS
 constexpr size_t kTagChunkBytes = (size_t)256 << 20;      // the block one launch should need: larger batches go image chunk by chunk
-// the second library only (-DCCAL_TEST_HOOKS): CCAL_TEST_TAGS_CHUNK_BYTES replaces the limit, so that a test cuts a small batch
-// into chunks (tests/test_gpu_tags.py); read on every call
-inline size_t tag_chunk_bytes() {
-#ifdef CCAL_TEST_HOOKS
-    if (const char* e = std::getenv("CCAL_TEST_TAGS_CHUNK_BYTES")) return (size_t)std::strtoull(e, nullptr, 10);
-#endif
-    return kTagChunkBytes;
-}
 
 // TagArgs: ccal_internal.hpp
-
-// floor and fraction of one coordinate, the two neighbour indices clamped to [0, n - 1]
-__device__ __forceinline__ void tag_tap(double x, int32_t n, int32_t& i0, int32_t& i1, double& ax) {
-    const double f = floor(x);
-    ax = x - f;
-    const double hi = (double)(n - 1);
-    i0 = (int32_t)fmin(fmax(f, 0.0), hi);            // NaN: fmax gives 0
-    i1 = min(i0 + 1, n - 1);
-}
 
 __device__ __forceinline__ double tag_wave_min(double v) {
     for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
@@ -73,14 +57,7 @@ __global__ __launch_bounds__(64 * kTagWaves) void k_decode_tags(const TagArgs a)
     bool matching = false;                               // wave-uniform: the quad has passed the border test
 
     if (have) {
-        // the image of quad q0 + g: the last k with off[k] <= q0 + g (images without quads are stepped over)
-        const int64_t gq = a.q0 + g;
-        int lo_k = 0, hi_k = a.n_img;
-        while (hi_k - lo_k > 1) {
-            const int mid = lo_k + ((hi_k - lo_k) >> 1);
-            if (a.off[mid] <= gq) lo_k = mid; else hi_k = mid;
-        }
-        const T* img = static_cast<const T*>(a.img) + (int64_t)lo_k * W * H;
+        const T* img = static_cast<const T*>(a.img) + (int64_t)image_of_row(a.off, a.n_img, a.q0 + g) * W * H;
         for (int i = 0; i < 4; ++i) { qx[i] = a.quads[8 * g + 2 * i]; qy[i] = a.quads[8 * g + 2 * i + 1]; }
 
         // 1. the map of the unit square onto the quad
@@ -111,17 +88,7 @@ __global__ __launch_bounds__(64 * kTagWaves) void k_decode_tags(const TagArgs a)
                         // false for NaN; +-inf fail one of the two sides
                         const bool ok = w > 0.0 && w <= 1.79769313486231570815e308 && x >= 0.0 && x <= x_hi && y >= 0.0 && y <= y_hi;
                         inside = inside && ok;
-                        if (ok) {
-                            int32_t x0, x1, y0, y1;
-                            double ax, ay;
-                            tag_tap(x, W, x0, x1, ax);
-                            tag_tap(y, H, y0, y1, ay);
-                            const T* r0 = img + (int64_t)y0 * W;
-                            const T* r1 = img + (int64_t)y1 * W;
-                            const double p00 = (double)r0[x0], p01 = (double)r0[x1], p10 = (double)r1[x0], p11 = (double)r1[x1];
-                            const double top = p00 + ax * (p01 - p00), bot = p10 + ax * (p11 - p10);
-                            acc += top + ay * (bot - top);
-                        }
+                        if (ok) acc += image_sample(img, W, H, x, y);
                     }
                 }
                 val[ch] = acc / ss;
@@ -218,9 +185,8 @@ __global__ __launch_bounds__(64 * kTagWaves) void k_decode_tags(const TagArgs a)
     }
 }
 
-// codes == nullptr: the ranges alone (the entry points check them before the image arguments, the table after)
-const char* tags_bad_params(int d, int border, const uint64_t* codes, int n_codes, int samples, double min_contrast, int max_border_errors,
-                            int max_hamming) {
+// the ranges, and the table on its own: the entry points check the ranges before the image arguments, the table after
+const char* tags_bad_params(int d, int border, int n_codes, int samples, double min_contrast, int max_border_errors, int max_hamming) {
     if (d < 3 || d > 8) return "d outside 3 .. 8";
     if (border < 1 || border > 2) return "border outside 1 .. 2";
     if (n_codes < 1) return "n_codes < 1";
@@ -228,6 +194,10 @@ const char* tags_bad_params(int d, int border, const uint64_t* codes, int n_code
     if (!(min_contrast >= 0.0) || !std::isfinite(min_contrast)) return "min_contrast negative or not finite";
     if (max_border_errors < 0) return "max_border_errors < 0";
     if (max_hamming < 0 || max_hamming > d * d) return "max_hamming outside 0 .. d * d";
+    return nullptr;
+}
+
+const char* tags_bad_codes(int d, const uint64_t* codes, int n_codes) {       // d and n_codes in range; codes == nullptr: nothing to test
     if (codes && d * d < 64)                              // at d = 8 every uint64 is a code: nothing to test, and no shift by 64
         for (int i = 0; i < n_codes; ++i)
             if (codes[i] >> (d * d)) return "a code of more than d * d bits";
@@ -244,46 +214,32 @@ hipError_t tags_enqueue(hipStream_t s, int dtype, const TagArgs& a) {
 
 namespace {
 
-int tags_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype, int width, int height, int n_img, const void* images,
-              const int64_t* offsets, const double* quads, int d, int border, const uint64_t* codes, int n_codes, int samples,
-              double min_contrast, int max_border_errors, int max_hamming, int32_t* reason_out, int32_t* id_out, int32_t* rot_out,
-              int32_t* hamming_out, double* corners_out, uint64_t* code_out, double* margin_out) {
+int tags_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, const int64_t* offsets, const double* quads, int d, int border,
+              const uint64_t* codes, int n_codes, int samples, double min_contrast, int max_border_errors, int max_hamming,
+              int32_t* reason_out, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out, double* corners_out, uint64_t* code_out, double* margin_out) {
     char msg[160];
     auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
-    if (const char* what = tags_bad_params(d, border, nullptr, n_codes, samples, min_contrast, max_border_errors, max_hamming)) return bad(what);
-    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad("dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16");
-    if (width <= 0 || height <= 0 || n_img < 0) return bad("a size is not positive");
-    if ((int64_t)width * height > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 pixels in an image");
-    if (const char* what = tags_bad_params(d, border, codes, n_codes, samples, min_contrast, max_border_errors, max_hamming)) return bad(what);
+    if (const char* what = tags_bad_params(d, border, n_codes, samples, min_contrast, max_border_errors, max_hamming)) return bad(what);
+    if (const char* what = b.bad()) return bad(what);
+    if (const char* what = tags_bad_codes(d, codes, n_codes)) return bad(what);
+    const int n_img = b.n_img;
     if (n_img == 0) return CCAL_OK;
-    if (!images || !offsets || !codes || !reason_out || !id_out || !rot_out || !hamming_out) return bad("NULL argument");
+    if (!b.images || !offsets || !codes || !reason_out || !id_out || !rot_out || !hamming_out) return bad("NULL argument");
     if (check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
     if (offsets[n_img] > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 quads");
     if (offsets[n_img] == 0) return CCAL_OK;
     if (!quads) return bad("NULL argument");
     // chunks of whole images: as many as keep the chunk's images (host call), quads and outputs within the limit, at least one
-    const size_t ni = (size_t)n_img, img_bytes = (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height;
-    const size_t per_quad = 8 * sizeof(double) + 4 * sizeof(int32_t) + 8 * sizeof(double) + sizeof(uint64_t) + sizeof(double);
-    const size_t limit = tag_chunk_bytes();
-    std::vector<size_t> cut(1, 0);                        // chunk c holds the images cut[c] .. cut[c + 1] - 1
-    size_t max_img = 0, max_quads = 0;
-    for (size_t k0 = 0; k0 < ni;) {
-        size_t k1 = k0, bytes = 0;
-        do {
-            bytes += (images_on_device ? 0 : img_bytes) + 8 + (size_t)(offsets[k1 + 1] - offsets[k1]) * per_quad;
-            ++k1;
-        } while (k1 < ni && bytes + (images_on_device ? 0 : img_bytes) + 8 + (size_t)(offsets[k1 + 1] - offsets[k1]) * per_quad <= limit);
-        cut.push_back(k1);
-        max_img = std::max(max_img, k1 - k0);
-        max_quads = std::max(max_quads, (size_t)(offsets[k1] - offsets[k0]));
-        k0 = k1;
-    }
+    const ImageChunks plan = image_chunks(offsets, (size_t)n_img, b.staged_bytes(1) + kTagPerImageBytes, kTagPerQuadBytes,
+                                          test_chunk_bytes("CCAL_TEST_TAGS_CHUNK_BYTES", kTagChunkBytes));
+    const std::vector<size_t>& cut = plan.cut;
+    const size_t max_img = plan.max_img, max_quads = plan.max_rows;
 
     // one block for the largest chunk: family | offsets | images (host call) | quads | corners, margin | code | reason, id, rot, hamming
     CallBlock blk(ctx);
     const auto s_codes = blk.add<unsigned long long>((size_t)n_codes);
     const auto s_off = blk.add<int64_t>(max_img + 1);
-    const auto s_img = blk.add<char>(images_on_device ? 0 : img_bytes * max_img);
+    const auto s_img = blk.add<char>(b.staged_bytes(max_img));
     const auto s_quads = blk.add<double>(8 * max_quads);
     const auto s_corners = blk.add<double>(8 * max_quads);
     const auto s_margin = blk.add<double>(max_quads);
@@ -298,7 +254,7 @@ int tags_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype
     a.off = blk.at(s_off); a.quads = blk.at(s_quads); a.codes = blk.at(s_codes);
     a.reason = blk.at(s_reason); a.id = blk.at(s_id); a.rot = blk.at(s_rot); a.hamming = blk.at(s_ham);
     a.corners = blk.at(s_corners); a.code = blk.at(s_code); a.margin = blk.at(s_margin);
-    a.W = width; a.H = height; a.d = d; a.border = border; a.n_codes = n_codes; a.S = samples;
+    a.W = b.width; a.H = b.height; a.d = d; a.border = border; a.n_codes = n_codes; a.S = samples;
     a.max_border = max_border_errors; a.max_hamming = max_hamming; a.min_contrast = min_contrast;
     blk.upload(s_codes, codes, (size_t)n_codes);
 
@@ -307,12 +263,11 @@ int tags_call(ccal_ctx* ctx, const char* where, bool images_on_device, int dtype
         const size_t at = (size_t)offsets[k0], nq = (size_t)(offsets[k0 + m] - offsets[k0]);
         if (!nq) continue;
         a.n_img = (int32_t)m; a.q0 = offsets[k0]; a.n = (int64_t)nq;
-        a.img = images_on_device ? (const void*)(static_cast<const char*>(images) + k0 * img_bytes) : (const void*)blk.at(s_img);
         blk.poison(s_corners, s_margin);                 // the test hook's NaN over the doubles the kernel writes and never reads
         blk.upload(s_off, offsets + k0, m + 1);
-        if (!images_on_device) blk.upload(s_img, static_cast<const char*>(images) + k0 * img_bytes, img_bytes * m);
+        a.img = b.chunk(blk, s_img, k0, m);
         blk.upload(s_quads, quads + 8 * at, 8 * nq);
-        if (blk.ok()) blk.note(tags_enqueue(ctx->stream, dtype, a));
+        if (blk.ok()) blk.note(tags_enqueue(ctx->stream, b.dtype, a));
         blk.download(reason_out + at, a.reason, nq);
         blk.download(id_out + at, a.id, nq);
         blk.download(rot_out + at, a.rot, nq);
@@ -337,8 +292,8 @@ int ccal_decode_tags_batch(ccal_ctx* ctx, int dtype, int width, int height, int 
                            int32_t* hamming_out, double* corners_out, uint64_t* code_out, double* margin_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return tags_call(ctx, "ccal_decode_tags_batch", false, dtype, width, height, n_img, images, offsets, quads, d, border, codes, n_codes,
-                     samples, min_contrast, max_border_errors, max_hamming, reason_out, id_out, rot_out, hamming_out, corners_out,
+    return tags_call(ctx, "ccal_decode_tags_batch", GreyBatch{ dtype, width, height, n_img, images, false }, offsets, quads, d, border, codes,
+                     n_codes, samples, min_contrast, max_border_errors, max_hamming, reason_out, id_out, rot_out, hamming_out, corners_out,
                      code_out, margin_out);
     CCAL_API_CATCH(ctx)
 }
@@ -349,8 +304,8 @@ int ccal_decode_tags_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_
                          int32_t* hamming_out, double* corners_out, uint64_t* code_out, double* margin_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return tags_call(ctx, "ccal_decode_tags_dev", true, dtype, width, height, n_img, images_dev, offsets, quads, d, border, codes, n_codes,
-                     samples, min_contrast, max_border_errors, max_hamming, reason_out, id_out, rot_out, hamming_out, corners_out,
+    return tags_call(ctx, "ccal_decode_tags_dev", GreyBatch{ dtype, width, height, n_img, images_dev, true }, offsets, quads, d, border, codes,
+                     n_codes, samples, min_contrast, max_border_errors, max_hamming, reason_out, id_out, rot_out, hamming_out, corners_out,
                      code_out, margin_out);
     CCAL_API_CATCH(ctx)
 }

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include "ccal_image_plan.hpp"
 
 namespace ccal {
 
@@ -23,7 +24,7 @@ constexpr size_t kChainQuadsPerPoint = 512;      // 8^3 chains start at a point
 
 struct ChainShape {
     size_t img_bytes = 0;          // one image
-    size_t dw = 0, dh = 0;         // the detector's domain; 0 x 0: none, the call has nothing to launch
+    DetectDomain dom;              // the detector's domain; dw == 0: none, the call has nothing to launch
     size_t slots = 0;              // its (r+1) x (r+1) blocks = the most candidates an image can have
     size_t cand = 0, quads = 0, tags = 0;        // rows per image: the caps, each cut to what can occur
 };
@@ -32,10 +33,9 @@ inline ChainShape chain_shape(size_t width, size_t height, size_t itemsize, size
                               size_t tag_cap, size_t n_codes) {
     ChainShape s;
     s.img_bytes = itemsize * width * height;
-    const size_t d0 = step + 2;
-    if (width <= 2 * d0 || height <= 2 * d0) return s;
-    s.dw = width - 2 * d0; s.dh = height - 2 * d0;
-    s.slots = ((s.dw + r) / (r + 1)) * ((s.dh + r) / (r + 1));
+    s.dom = detect_domain((int)width, (int)height, (int)step, (int)r);
+    if (!s.dom.dw) return s;
+    s.slots = s.dom.slots();
     s.cand = std::min(cand_cap, s.slots);
     s.quads = std::min(quad_cap, kChainQuadsPerPoint * s.cand);
     s.tags = std::min(tag_cap, std::min(s.quads, n_codes));          // an image's tags have distinct ids
@@ -43,7 +43,7 @@ inline ChainShape chain_shape(size_t width, size_t height, size_t itemsize, size
 }
 
 inline size_t chain_per_image_bytes(bool images_on_device, const ChainShape& s) {
-    return (images_on_device ? 0 : s.img_bytes) + s.slots * kChainPerSlotBytes + s.dh * 4 + s.cand * kChainPerCandBytes +
+    return (images_on_device ? 0 : s.img_bytes) + s.slots * kChainPerSlotBytes + (size_t)s.dom.dh * 4 + s.cand * kChainPerCandBytes +
            s.quads * kChainPerQuadBytes + s.tags * kChainPerTagBytes + kChainPerImageBytes;
 }
 

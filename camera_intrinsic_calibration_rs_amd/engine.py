@@ -307,19 +307,15 @@ class Context:
                 int(max_iterations), float(eps), _ip(status), _ip(iters), _dp(lam))
         if rc != _ffi.OK:
             raise CcalError(rc, where, self.last_error())
-        cut = [(int(offs[k]), int(offs[k + 1])) for k in range(n_img)]
-        return tuple([arr[a:b] for a, b in cut] for arr in (out_xy, status, iters, lam))
+        return _per_image(offs, n_img, (out_xy, status, iters, lam))
 
     def refine_corners_batch(self, images, xy_list, half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3):
         """Every coarse corner of a batch of grey images moved onto the grey-level saddle, all in one launch.  images: [n][H][W],
         uint8 or uint16; xy_list: one array [n_i, 2] of (x, y) starts per image.  Returns (xy_list, status_list, iters_list,
         lambda_min_list), per image: positions [n_i, 2], status [n_i] int32 - _ffi.OK, ERR_NO_CONVERGENCE (the last iterate),
         ERR_NOT_PD or NO_RESULT (the position as given) -, updates made [n_i], corner strength [n_i] (NaN: nothing evaluated)."""
-        images, dtype, channels = check_images(images, True)
-        if channels != 1:
-            raise ValueError("refine_corners_batch: single-channel images [n][H][W]")
-        n_img, H, W = images.shape[:3]
-        return self._corners(self.lib.ccal_refine_corners_batch, "ccal_refine_corners_batch", images.ctypes.data, dtype, W, H, n_img,
+        images, batch = _grey_batch(images, "refine_corners_batch")
+        return self._corners(self.lib.ccal_refine_corners_batch, "ccal_refine_corners_batch", *batch,
                              xy_list, half_win, max_iterations, eps)
 
     def refine_corners_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, xy_list, half_win: int = 5,
@@ -363,11 +359,8 @@ class Context:
         (xy int32 [k, 2], hess int32 [k, 3] = (hxx, hyy, hxy), response int64 [k], count) in row-major order of (y, x), with
         k = min(count, max_per_image).  min_response scales with the square of the image contrast; no useful value has been measured
         (as for refine_corners_batch's lambda_min), the default 1 screens only flat and edge-only neighbourhoods."""
-        images, dtype, channels = check_images(images, True)
-        if channels != 1:
-            raise ValueError("detect_corners_batch: single-channel images [n][H][W]")
-        n_img, H, W = images.shape[:3]
-        return self._detect(self.lib.ccal_detect_corners_batch, "ccal_detect_corners_batch", images.ctypes.data, dtype, W, H, n_img,
+        images, batch = _grey_batch(images, "detect_corners_batch")
+        return self._detect(self.lib.ccal_detect_corners_batch, "ccal_detect_corners_batch", *batch,
                             step, nms_radius, min_response, rel_threshold, max_per_image)
 
     def detect_corners_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, step: int = 1, nms_radius: int = 5,
@@ -382,10 +375,7 @@ class Context:
               max_border_errors, max_hamming):
         if len(quads_list) != n_img:
             raise ValueError(f"{where}: one array of quads per image")
-        d = int(round(max(float(family_bits), 0.0) ** 0.5))
-        if d * d != int(family_bits):
-            raise ValueError(f"{where}: family_bits is not a square")
-        codes = np.ascontiguousarray(np.asarray([int(c) for c in codes], dtype=np.uint64))
+        d, codes = _family(where, family_bits, codes)
         offs, quads = _pack(quads_list, 8)
         n = int(offs[-1])
         m = max(n, 1)
@@ -399,8 +389,7 @@ class Context:
                 _ip(reason), _ip(tag_id), _ip(rot), _ip(hamming), _dp(corners), code.ctypes.data_as(up), _dp(margin))
         if rc != _ffi.OK:
             raise CcalError(rc, where, self.last_error())
-        cut = [(int(offs[k]), int(offs[k + 1])) for k in range(n_img)]
-        return tuple([arr[a:b] for a, b in cut] for arr in (reason, tag_id, rot, hamming, corners, code, margin))
+        return _per_image(offs, n_img, (reason, tag_id, rot, hamming, corners, code, margin))
 
     def decode_tags_batch(self, images, quads_list, family_bits: int, codes, border: int = 1, samples: int = 3,
                           min_contrast: float = 20.0, max_border_errors: int = 0, max_hamming: int = 2):
@@ -411,11 +400,8 @@ class Context:
         Returns (reason, id, rot, hamming, corners, code, margin), each a list with one array per image: reason [n_i] int32
         (_ffi.TAG_OK, TAG_OUTSIDE, TAG_LOW_CONTRAST, TAG_BORDER, TAG_NO_CODE), id / rot / hamming [n_i] int32 (-1 unless TAG_OK),
         corners [n_i, 4, 2] in the tag's canonical order (NaN unless TAG_OK), code [n_i] uint64 as read, margin [n_i]."""
-        images, dtype, channels = check_images(images, True)
-        if channels != 1:
-            raise ValueError("decode_tags_batch: single-channel images [n][H][W]")
-        n_img, H, W = images.shape[:3]
-        return self._tags(self.lib.ccal_decode_tags_batch, "ccal_decode_tags_batch", images.ctypes.data, dtype, W, H, n_img, quads_list,
+        images, batch = _grey_batch(images, "decode_tags_batch")
+        return self._tags(self.lib.ccal_decode_tags_batch, "ccal_decode_tags_batch", *batch, quads_list,
                           family_bits, codes, border, samples, min_contrast, max_border_errors, max_hamming)
 
     def decode_tags_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, quads_list, family_bits: int, codes,
@@ -462,11 +448,8 @@ class Context:
         (idx int32 [m, 4] - the corners' indices into the image's points -, quads f64 [m, 4, 2] - their coordinates, ready for
         decode_tags_batch -, count, flags) in lexicographic order of the indices, with m = min(count, max_per_image); bit 0 of flags
         (_ffi.QUAD_FLAG_CUT): a point had more than 8 out-edges, proposals may be missing."""
-        images, dtype, channels = check_images(images, True)
-        if channels != 1:
-            raise ValueError("propose_quads_batch: single-channel images [n][H][W]")
-        n_img, H, W = images.shape[:3]
-        return self._quads(self.lib.ccal_propose_quads_batch, "ccal_propose_quads_batch", images.ctypes.data, dtype, W, H, n_img, xy_list,
+        images, batch = _grey_batch(images, "propose_quads_batch")
+        return self._quads(self.lib.ccal_propose_quads_batch, "ccal_propose_quads_batch", *batch, xy_list,
                            min_side, max_side, max_side_ratio, offset, samples, min_contrast, max_per_image)
 
     def propose_quads_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, xy_list, min_side: float = 20.0,
@@ -484,10 +467,7 @@ class Context:
                      max_tags):
         if not np.isfinite(rel_threshold):
             raise ValueError(f"{where}: rel_threshold is not finite")
-        d = int(round(max(float(family_bits), 0.0) ** 0.5))
-        if d * d != int(family_bits):
-            raise ValueError(f"{where}: family_bits is not a square")
-        codes = np.ascontiguousarray(np.asarray([int(c) for c in codes], dtype=np.uint64))
+        d, codes = _family(where, family_bits, codes)
         if max_side is None:
             max_side = max(int(width), int(height)) / 2.0
         if offset is None:
@@ -532,11 +512,8 @@ class Context:
         rot [m], hamming [m], corners f64 [m, 4, 2] in the tag's canonical order, margin [m], count, flags, stats int32 [4]) in
         ascending id, m = min(count, max_tags); flags: _ffi.TAGS_FLAG_*; stats = candidates found, points after the merge, quads
         found, decodable quads before the selection."""
-        images, dtype, channels = check_images(images, True)
-        if channels != 1:
-            raise ValueError("detect_tags_batch: single-channel images [n][H][W]")
-        n_img, H, W = images.shape[:3]
-        return self._detect_tags(self.lib.ccal_detect_tags_batch, "ccal_detect_tags_batch", images.ctypes.data, dtype, W, H, n_img,
+        images, batch = _grey_batch(images, "detect_tags_batch")
+        return self._detect_tags(self.lib.ccal_detect_tags_batch, "ccal_detect_tags_batch", *batch,
                                  family_bits, codes, step, nms_radius, min_response, rel_threshold, max_candidates, half_win,
                                  max_iterations, eps, merge_radius, min_side, max_side, max_side_ratio, offset, edge_samples,
                                  edge_min_contrast, max_quads, border, cell_samples, tag_min_contrast, max_border_errors, max_hamming,
@@ -569,6 +546,30 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def _grey_batch(images, who: str):
+    """The image arguments of an image stage's host call: the checked array (the caller keeps it alive over the call) and
+    (pointer, dtype code, width, height, n_img) as the stage's private method takes them."""
+    images, dtype, channels = check_images(images, True)
+    if channels != 1:
+        raise ValueError(f"{who}: single-channel images [n][H][W]")
+    n_img, H, W = images.shape[:3]
+    return images, (images.ctypes.data, dtype, W, H, n_img)
+
+
+def _family(where: str, family_bits, codes):
+    """(d, the code table as a contiguous uint64 array) of a tag family of family_bits = d * d bits."""
+    d = int(round(max(float(family_bits), 0.0) ** 0.5))
+    if d * d != int(family_bits):
+        raise ValueError(f"{where}: family_bits is not a square")
+    return d, np.ascontiguousarray(np.asarray([int(c) for c in codes], dtype=np.uint64))
+
+
+def _per_image(offs, n_img: int, arrays):
+    """Flat outputs cut back per image: for each array the list of its n_img views."""
+    cut = [(int(offs[k]), int(offs[k + 1])) for k in range(n_img)]
+    return tuple([arr[a:b] for a, b in cut] for arr in arrays)
 
 
 def check_maps(xmap, ymap):

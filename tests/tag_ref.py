@@ -442,6 +442,12 @@ def batch_case():
     return _case("three images", np.stack([a, np.full_like(a, 9), b]), [qa, np.zeros((0, 4, 2)), reps], 6, 1, codes, 3, 20.0, 0, 1)
 
 
+# tests/test_gpu_tags.py::test_a_batch_cut_into_chunks on batch_case() (three 76 800-byte images with 60, 0 and 140 quads): the chunk
+# limits for the host call (pixels count) and the _dev call (they do not) - 1 byte: an image per chunk; the second: the images (0, 1)
+# and (2) - the first two together, the third alone.  tests/test_quads_plan_cpu.py holds the library's planner to exactly these groupings.
+CHUNK_LIMITS_HOST, CHUNK_LIMITS_DEV, CHUNK_GROUPS = (1, 200000), (1, 20000), (0, 2, 3)
+
+
 @functools.lru_cache(maxsize=None)
 def rendered_cases():
     """The end-to-end frames with their true quads moved by up to 0.3 px per coordinate: general projective maps over antialiased,

@@ -3,7 +3,7 @@ tests/detect_ref.py, the numpy int64 yardstick of the rule stated in include/cca
 
 Bounds.  The rule is integer arithmetic and its outputs are decisions, so counts, positions, Hessians and responses are compared
 with np.array_equal: no tolerance anywhere but the end-to-end test, whose positions pass through the f64 refinement (1e-9 px, the
-suite's bound for f64 against f64).  Images are 6 x 6 up to 160 x 160; every case takes well under a second."""
+suite's bound for f64 against f64).  Images are 6 x 6 up to 160 x 160, and one of 40 x 600; every case takes well under a second."""
 import ctypes as C
 import os
 import sys
@@ -70,6 +70,8 @@ def parity_images(dtype, s):
         "domain 2 x 2": (rng.integers(0, 256, (3, side + 2, side + 2)) * scale).astype(dtype),
         "domain 1 x 40": (rng.integers(0, 256, (2, side + 40, side + 1)) * scale).astype(dtype),
         "no domain": (rng.integers(0, 256, (2, 40, side)) * scale).astype(dtype),
+        # more than 512 domain rows: k_detect_rows scans 256 rows per round and carries the count from round to round
+        "40 x 600": (rng.integers(0, 256, (600, 40)) * scale).astype(dtype)[None],
     }
     if dtype == np.uint16:
         out["extreme 3 x 3"] = ref.extreme_blocks()[None]
@@ -91,6 +93,9 @@ def test_parity(gpu_ctx, dtype, s, r):
             assert n == loose == 0
         if name.startswith(("grid", "67")):
             assert loose >= n > 0
+        if name.startswith("40 x 600"):                     # the input cannot go stale: candidates in each of the three rounds of rows
+            rows = ref.detect(imgs[0], s, r, 1, 102, 4096)["xy"][:, 1] - (s + 2)
+            assert set((rows // 256).tolist()) == {0, 1, 2}, name
 
 
 @pytest.mark.parametrize("s", [1, 4])

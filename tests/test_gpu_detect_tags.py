@@ -195,6 +195,26 @@ def test_a_mixed_batch_image_by_image(gpu_ctx):
     assert b"".join(bits(back, k) for k in range(len(imgs) - 1, -1, -1)) == b"".join(bits(whole, k) for k in range(len(imgs)))
 
 
+def test_more_images_than_two_rounds_of_the_offset_scan(gpu_ctx):
+    """k_chain_offsets scans the per-image counts 64 images per round and carries the sum from round to round.  129 images - the four
+    frames in turn, image 64 a blank one - make two carries and a zero count on the first lane of a round.  Image k's bits are those
+    of its frame in the four-frame call, which is held to the staged chain."""
+    four_imgs = frames(np.uint8)
+    o = ref.opts(np.uint8)
+    four = raw_detect(gpu_ctx, four_imgs, o)
+    check_against_staged(four, staged(gpu_ctx, four_imgs, o, key=("frames", "uint8", 5)), o["tag_cap"], "four frames")
+    imgs = np.ascontiguousarray(four_imgs[np.arange(129) % 4])
+    imgs[64] = 0
+    got = raw_detect(gpu_ctx, imgs, o)
+    assert got["rc"] == _ffi.OK
+    for k in range(129):
+        if k != 64:
+            assert bits(got, k) == bits(four, k % 4), k
+    assert got["count"][64] == 0 and got["flags"][64] == 0 and (got["stats"][64] == 0).all()
+    assert all((got[key][64] == SENT_I).all() for key in ("id", "rot", "hamming"))
+    assert (got["corners"][64] == SENT_F).all() and (got["margin"][64] == SENT_F).all()
+
+
 def test_no_images_and_images_without_a_domain_are_valid(gpu_ctx):
     o = ref.opts()
     for fn in (gpu_ctx.lib.ccal_detect_tags_batch, gpu_ctx.lib.ccal_detect_tags_dev):

@@ -162,16 +162,23 @@ def test_optional_outputs_may_be_null(gpu_ctx):
 def test_a_batch_cut_into_chunks(dev_ctx, gpu_ctx, monkeypatch, limit):
     """The library runs a batch whose block would exceed 256 MB in chunks of whole images.  The second library reads the limit from
     CCAL_TEST_TAGS_CHUNK_BYTES (tests only): 1 byte - every image a chunk of its own, the one without quads skipped -, and 200 000
-    bytes - the first two 77 KB images together, the third alone.  Host and device entry: the product's bits."""
+    bytes - the first two 77 KB images together, the third alone.  The _dev call's chunks do not hold the pixels: at 200 000 bytes it
+    would take the three images at once, so it gets the limit that cuts it the same way (20 000 bytes: tag_ref.CHUNK_LIMITS_DEV).
+    That the limits cut the batch exactly so is held on the CPU (tests/test_quads_plan_cpu.py).  Host and device entry: the
+    product's bits."""
     import torch
     case = ref.batch_case()
     whole = raw_decode(gpu_ctx, case)
     check_against_yardstick(whole, case)
-    monkeypatch.setenv("CCAL_TEST_TAGS_CHUNK_BYTES", str(limit))
+    which = ref.CHUNK_LIMITS_HOST.index(limit)
     raw = torch.from_numpy(case["images"].copy()).cuda()
     torch.cuda.synchronize()
-    for got in (raw_decode(dev_ctx, case), raw_decode(dev_ctx, case, fn=dev_ctx.lib.ccal_decode_tags_dev, ptr=raw.data_ptr())):
-        assert got["rc"] == _ffi.OK and bits(got) == bits(whole)
+    monkeypatch.setenv("CCAL_TEST_TAGS_CHUNK_BYTES", str(ref.CHUNK_LIMITS_HOST[which]))
+    got = raw_decode(dev_ctx, case)
+    assert got["rc"] == _ffi.OK and bits(got) == bits(whole)
+    monkeypatch.setenv("CCAL_TEST_TAGS_CHUNK_BYTES", str(ref.CHUNK_LIMITS_DEV[which]))
+    got = raw_decode(dev_ctx, case, fn=dev_ctx.lib.ccal_decode_tags_dev, ptr=raw.data_ptr())
+    assert got["rc"] == _ffi.OK and bits(got) == bits(whole)
 
 
 # ---- 3. the _dev entry ----------------------------------------------------------------------------------------------------------------
