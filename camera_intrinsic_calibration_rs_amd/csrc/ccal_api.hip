@@ -1,5 +1,5 @@
 // C ABI of the engine (include/ccal.h): context, problem residency, mode E entry points,
-// constraints, validation.  The solver loop lives in ccal_solver.hip.
+// constraints, validation.  The solver loop lives in ccal_solver.hip, its workspaces in ccal_solver_ws.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

@@ -1,5 +1,5 @@
 // Device-resident optimizer state, the decision rule shared by both device loops, and the argument blocks of the
-// single-camera fast path (ccal_kernels_fused.hip, driven by solve_fused() in ccal_solver.hip).
+// single-camera fast path (ccal_kernels_fused.hip, driven by FusedJob in ccal_solver.hip).
 //
 // One GROUP of launches = one evaluation + one reduced system + ONE all-reduce + one decision/solve, for Gauss-Newton
 // and for Levenberg-Marquardt alike:
@@ -339,7 +339,7 @@ __device__ __forceinline__ void gen_et_compact(const double* ept, double* ec) {
             ec[18 + 3 * b + m] = ept[6 * (6 + b) + m]; ec[27 + 3 * b + m] = ept[6 * (6 + b) + 3 + m];
         }
 }
-// rows of partial sums up to which k_head adds them up itself (session-sized problems: <= 1 280 frames); see solve_fused
+// rows of partial sums up to which k_head adds them up itself (session-sized problems: <= 1 280 frames); see FusedJob::enqueue
 constexpr int kHeadReduceRows = 40;
 // red / partial rows of the single-camera path: [A_dir (K1 x K1) | Y^T Y (K1 x K1) | mc_pose | failed pose blocks]
 __host__ __device__ constexpr int fused_red_size(int K) { return 2 * (K + 1) * (K + 1) + 2; }

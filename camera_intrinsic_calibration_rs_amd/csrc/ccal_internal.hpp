@@ -10,6 +10,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/ccal.h"
@@ -64,7 +65,7 @@ struct ccal_ctx {
     int n_problems = 0;
     bool destroy_requested = false;
     // ccal_solve_batch: the host thread that drives this context's stream while the caller's thread drives another one
-    // (created on first use, joined when the context is freed; ccal_solver.hip)
+    // (created on first use, joined when the context is freed; ccal_solver_many.hip)
     struct ccal_ctx_worker* worker = nullptr;
     // ccal_solve_batch, session sizes: the argument blocks of a batch's problems, one launch per step for all of them
     // (k_gram1v_batch reads the table on the device; h_: its pinned staging) - blocks of the context's allocator, grown on demand, released with the context
@@ -139,7 +140,7 @@ inline void ctx_stream_put(ccal_ctx* ctx, hipStream_t s) {
 // Test hook of the second library (-DCCAL_TEST_HOOKS): with CCAL_TEST_POISON_ALLOC=1 fill a freshly allocated (or cache-reused) block
 // of DOUBLES with 0xFF bytes - a quiet NaN - before the library's own clears and uploads, so that a result depending on memory nobody
 // wrote turns into NaN (tests/test_gpu_poison.py).  Never called on indices, offsets, counters, flags or DevState.  Defined out of
-// line in ccal_solver.hip, which each library compiles itself; hidden, so that each library calls its own.  The product's is empty.
+// line in ccal_solver_ws.hip, which each library compiles itself; hidden, so that each library calls its own.  The product's is empty.
 __attribute__((visibility("hidden"))) hipError_t test_poison_f64(ccal_ctx* ctx, void* p, size_t bytes, bool host, hipStream_t s);
 // A persistent block as its plan describes it: from the context's allocator, the test hook's NaN over its slices of doubles, then ONE
 // clear of the slices that must start as zeros - on the context's stream (it does not synchronise with the null stream), in front of every use
@@ -281,15 +282,16 @@ struct ccal_problem {
     catch (...) { ccal::note_error((ctx_expr), "unknown C++ exception"); return CCAL_ERR_HIP; }
 
 // A HIP call of a function that returns a ccal_status: on failure the context's message is "<the call>: <HIP's text>" and the
-// function returns CCAL_ERR_HIP.
-#define HIP_TRY(ctx, expr)                                                                         \
+// function returns CCAL_ERR_HIP (HIP_TRY_RET: `ret`, for a function whose return value carries something else as well).
+#define HIP_TRY_RET(ctx, expr, ret)                                                                \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess) {                                                                    \
             (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
-            return CCAL_ERR_HIP;                                                                   \
+            return ret;                                                                            \
         }                                                                                          \
     } while (0)
+#define HIP_TRY(ctx, expr) HIP_TRY_RET(ctx, expr, CCAL_ERR_HIP)
 
 namespace ccal {
 inline void note_error(ccal_ctx* ctx, const char* msg) noexcept {
@@ -330,7 +332,15 @@ hipError_t launch_eval(const ccal_problem* p, int cam, const KArgs& a, hipStream
 hipError_t launch_reproj_err(const ccal_problem* p, int cam, const KArgs& a, hipStream_t s);
 // ccal_rccl.hip: in-place sum over the ranks of an ncclComm_t, ordered on the stream; returns a ccal_status
 int rccl_allreduce_sum(ccal_ctx* ctx, void* comm, double* buf, size_t count, hipStream_t st);
-// ccal_solver.hip: wait for the early-exit groups a finished solve left in the stream (no-op if there are none)
+// A finished solve may leave early-exit groups in its stream (`flag`: a workspace's tail_pending); they publish into the workspace's
+// pinned status word, so whoever uses it next waits for them first.  No-op when the flag is down.
+__attribute__((visibility("hidden"))) inline int drain_tail(ccal_ctx* ctx, hipStream_t st, bool& flag) {
+    if (!flag) return CCAL_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    flag = false;
+    return CCAL_OK;
+}
+// ccal_solver_ws.hip: the same for both workspaces of a problem, on its context's stream
 int drain_pending_groups(ccal_problem* p);
 // ccal_kernels_stats.hip
 // ccal_problem::d_scratch, grown on demand and kept between calls, as its two users cut it:
@@ -409,15 +419,48 @@ void inproc_set_timeout(InprocComm* c, double seconds); // host rendezvous: how 
 void* inproc_rank_handle(InprocComm* c, int rank);      // ccal_problem::peer of that rank
 int inproc_parity(const void* rank_handle);             // which of its two sum buffers the rank's next collective uses
 int inproc_post(void* rank_handle, const double* device_buf, size_t count, void* hip_stream, PeerView* out);   // 0 = ok
-// a context's persistent helper thread (ccal_solver.hip; created on first use): run fn on it / wait until it has finished
+// a context's persistent helper thread (ccal_solver_many.hip; created on first use): run fn on it / wait until it has finished
 void ctx_worker_submit(ccal_ctx* ctx, std::function<void()> fn);
 void ctx_worker_wait(ccal_ctx* ctx);
+// One call over several contexts: fn(i) for i = 1 .. n - 1 on ctx[i]'s helper thread, `here` - fn(0) unless the caller has another body
+// for its own thread - on the calling one; back when all have finished.  If a helper cannot be made (std::thread throws), `on_failure`
+// runs - the sharded solve releases the ranks already started from their rendezvous with the one that will never come - what was
+// handed out finishes, and the exception goes on to the caller.  fn must not throw.
+template <class Fn, class Here, class OnFailure>
+void ctx_fan_out(ccal_ctx* const* ctx, int n, Fn&& fn, Here&& here, OnFailure&& on_failure) {
+    int started = 0;
+    try { for (int i = 1; i < n; ++i) { ctx_worker_submit(ctx[i], [&fn, i] { fn(i); }); started = i; } }
+    catch (...) { on_failure(); for (int i = 1; i <= started; ++i) ctx_worker_wait(ctx[i]); throw; }
+    here();
+    for (int i = 1; i < n; ++i) ctx_worker_wait(ctx[i]);
+}
+template <class Fn>
+void ctx_fan_out(ccal_ctx* const* ctx, int n, Fn&& fn) { ctx_fan_out(ctx, n, fn, [&fn] { fn(0); }, [] {}); }
+// a spinning host thread's pause between two looks
+__attribute__((visibility("hidden"))) inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    asm volatile("yield" ::: "memory");
+#else
+    std::this_thread::yield();
+#endif
+}
+// fn() -> ccal_status on a thread no exception may leave: its code, or the exception's, with the reason in the context (ctx may be NULL)
+template <class Fn>
+int guarded(ccal_ctx* ctx, const char* where, Fn&& fn) noexcept {
+    try { return fn(); }
+    catch (const std::bad_alloc&) { note_error(ctx, "out of host memory"); return CCAL_ERR_NO_MEMORY; }
+    catch (...) { note_error(ctx, where); return CCAL_ERR_HIP; }
+}
+// the report of a call that ended without the solver's verdict
+__attribute__((visibility("hidden"))) inline void blank_report(ccal_report* rep, int rc) { if (rep) { *rep = ccal_report{}; rep->status = rc; } }
 // why the last ccal_ctx_create / ccal_multi_create* on this thread failed (ccal_create_last_error)
 void note_create_error(const std::string& msg) noexcept;
 // ccal_rccl.hip: communicators of one process, one per device (ncclCommInitAll); abort = ncclCommAbort
 int rccl_comm_init_all(const int* devices, int n, void** comms_out, std::string* err);
 void rccl_comm_abort(void* comm);
-// ccal_solver.hip: n shards of ONE problem (distinct contexts, a transport set on every shard), each driven by a host
+// ccal_solver_many.hip: n shards of ONE problem (distinct contexts, a transport set on every shard), each driven by a host
 // thread of its own; `inproc` (may be NULL) is aborted when a rank fails
 int solve_sharded_run(ccal_problem** shards, int n, const ccal_solver_opts* o, double* intr_io, double* const* poses_io,
                       double* extr_io, ccal_report* rep, InprocComm* inproc);

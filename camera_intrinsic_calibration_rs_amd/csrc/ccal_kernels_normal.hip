@@ -254,7 +254,7 @@ hipError_t launch_gram_dev_all(const ccal_problem* p, const DevState* st, hipStr
     return hipSuccess;
 }
 
-// ragged frames: the launch's list sorted by corner count and its bins, when normal_ws_ensure_general planned them (ccal_solver.hip)
+// ragged frames: the launch's list sorted by corner count and its bins, when normal_ws_ensure_general planned them (ccal_solver_ws.hip)
 static void set_gen_bins(FusedArgs& fa, const NormalWs* w, int slot) {
     const GramBins& gb = w->gen_bins[slot];
     if (gb.n_bins <= 0 || !w->d_gen_sorted[slot]) return;

@@ -56,13 +56,6 @@ struct InprocComm {
     double timeout_s = 600.0;
 };
 
-static inline void relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#else
-    std::this_thread::yield();
-#endif
-}
 // wait until rank q has posted collective number `call`.  Spins ~50 us (the peers of a step arrive within microseconds of each
 // other), then sleeps on the condition variable in 200-us slices.  false: aborted (by a peer, or by this rank after `timeout_s`).
 static bool inproc_wait_posted(InprocComm* c, int q, uint64_t call) {
@@ -71,7 +64,7 @@ static bool inproc_wait_posted(InprocComm* c, int q, uint64_t call) {
     for (long spins = 1;; ++spins) {
         if (pq.load(std::memory_order_acquire) >= call) return !c->abort.load(std::memory_order_acquire);
         if (c->abort.load(std::memory_order_acquire)) return false;
-        if (spins & 0xFF) { relax(); continue; }
+        if (spins & 0xFF) { cpu_relax(); continue; }
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (c->timeout_s > 0 && el > c->timeout_s) { inproc_abort(c); return false; }
         if (el > 50e-6) {
@@ -211,16 +204,6 @@ static void multi_free(ccal_multi* m) {
     delete m;
 }
 static int mfail(ccal_multi* m, int code, const std::string& msg) { if (m) { try { m->err = msg; } catch (...) { } } return code; }
-// run fn(i) for every shard: shard 0 on the caller's thread, the others on their contexts' persistent helper threads (the ones
-// ccal_multi_solve / ccal_solve_batch use: created on first use, asleep on a condition variable in between)
-template <class F>
-static void for_each_shard(ccal_multi* m, int n, F&& fn) {
-    int started = 0;
-    try { for (int i = 1; i < n; ++i) { ctx_worker_submit(m->ctx[(size_t)i], [&fn, i] { fn(i); }); started = i; } }
-    catch (...) { for (int i = 1; i <= started; ++i) ctx_worker_wait(m->ctx[(size_t)i]); throw; }
-    fn(0);
-    for (int i = 1; i < n; ++i) ctx_worker_wait(m->ctx[(size_t)i]);
-}
 // why the last ccal_ctx_create / ccal_multi_create* of this thread failed (there is no handle to ask)
 static thread_local std::string t_create_err;
 namespace ccal { void note_create_error(const std::string& msg) noexcept { try { t_create_err = msg; } catch (...) { } } }
@@ -466,7 +449,7 @@ int ccal_multi_init_poses(ccal_multi_problem* mp, const double* intr, int min_po
     std::vector<std::vector<double>> po((size_t)n);
     std::vector<std::vector<int32_t>> nu((size_t)n);
     for (int r = 0; r < n; ++r) { po[(size_t)r].assign(std::max<size_t>(mp->obs_of[(size_t)r].size(), 1) * 6, 0.0); nu[(size_t)r].assign(std::max<size_t>(mp->obs_of[(size_t)r].size(), 1), 0); }
-    for_each_shard(mp->m, n, [&](int r) { rc[(size_t)r] = ccal_init_poses(mp->shard[(size_t)r], intr, min_points, po[(size_t)r].data(), nu[(size_t)r].data()); });
+    ctx_fan_out(mp->m->ctx.data(), n, [&](int r) { rc[(size_t)r] = ccal_init_poses(mp->shard[(size_t)r], intr, min_points, po[(size_t)r].data(), nu[(size_t)r].data()); });
     for (int r = 0; r < n; ++r) {
         if (rc[(size_t)r] != CCAL_OK) return mfail(mp->m, rc[(size_t)r], ccal_last_error(mp->m->ctx[(size_t)r]));
         const std::vector<int32_t>& obs = mp->obs_of[(size_t)r];
@@ -491,7 +474,7 @@ int ccal_multi_validation(ccal_multi_problem* mp, int cam, const double* intr, c
     std::vector<double*> d_part((size_t)n, nullptr);       // slices of the shards' own scratch blocks (nothing to free)
     std::vector<int64_t> cnt((size_t)n, 0);
     std::vector<int> rc((size_t)n, CCAL_OK);
-    for_each_shard(m, n, [&](int r) {
+    ctx_fan_out(m->ctx.data(), n, [&](int r) {
         ccal_problem* p = mp->shard[(size_t)r];
         rc[(size_t)r] = reprojection_errors_dev(p, intr, poses ? poses + 6 * (size_t)mp->first[(size_t)r] : nullptr, extr);
         if (rc[(size_t)r] == CCAL_OK && camera_errors_device(p, cam, p->d_err, &d_part[(size_t)r], &cnt[(size_t)r], p->ctx->stream) != hipSuccess) {
@@ -539,7 +522,7 @@ int ccal_multi_reprojection_errors(ccal_multi_problem* mp, const double* intr, c
     std::vector<int> rc((size_t)n, CCAL_OK);
     std::vector<std::vector<double>> part((size_t)n);
     for (int r = 0; r < n; ++r) part[(size_t)r].assign((size_t)std::max<int64_t>(ccal_num_corners(mp->shard[(size_t)r]), 1), 0.0);
-    for_each_shard(mp->m, n, [&](int r) {
+    ctx_fan_out(mp->m->ctx.data(), n, [&](int r) {
         rc[(size_t)r] = ccal_reprojection_errors(mp->shard[(size_t)r], intr, poses ? poses + 6 * (size_t)mp->first[(size_t)r] : nullptr, extr, part[(size_t)r].data());
     });
     for (int r = 0; r < n; ++r) {

@@ -239,11 +239,19 @@ struct SchurArgs {
     const DevState* st;                        // device-resident loop: Gram set and lambda come from the state
 };
 
-
+// the workspaces (ccal_solver_ws.hip)
 void normal_ws_destroy(ccal_problem* p);
 int normal_ws_ensure(ccal_problem* p);          // sizes, column table, camera step: allocate on first use
 int normal_ws_ensure_general(ccal_problem* p);  // + the general (multi-camera) loop's buffers
+__attribute__((visibility("hidden"))) int fused_ws_ensure(ccal_problem* p);           // + the single-camera loop's (after normal_ws_ensure)
 int normal_upload_cols(ccal_problem* p);        // bounds / fixed flags -> device
+__attribute__((visibility("hidden"))) void build_cols(const ccal_problem* p, ColInfo* cols);        // [CCAL_KMAX]: the reduced system's columns, bounds and fixed flags in
+__attribute__((visibility("hidden"))) void caller_columns(const ccal_problem* p, int* ext);         // [K]: reduced-system column -> the same parameter's column in the caller's order
+// Session-sized solves (poses up to this many bytes: 2 048 frames) move their parameters without a copy operation: k_unpack1
+// reads the caller's poses from pinned host memory, the k_head that finishes the solve writes the result there.  Larger
+// problems stage through device copies (a kernel reading / writing half a megabyte across the bus one wavefront wide would
+// cost more than the DMA it saves).
+constexpr size_t kZeroCopyBytes = 96 * 1024;
 
 // launchers (ccal_kernels_normal.hip).  Host-driven form: `cand` / gbuf / lambda select parameter set, G buffer and
 // damping.  Device-resident form (st != NULL, *_dev): set 0 = (p->d_*, G[w->cur]), set 1 = (p->d_*_c, G[w->cur ^ 1]),

@@ -145,6 +145,66 @@ def test_a_failing_member_of_a_lockstep_group_does_not_take_its_neighbours_down(
         p.close()
 
 
+def _assert_same_as_alone(alone, reps, results):
+    """the file's comparison: verdict, iteration count and accept / reject sequence equal, costs and parameters to 1e-11"""
+    def same(a, b):
+        np.testing.assert_allclose(a, b, rtol=1e-11, atol=1e-13)
+    for (i0, p0, e0, r0), rep, (i1, p1, e1) in zip(alone, reps, results):
+        assert (rep.status, rep.iterations, rep.lm_accepted, rep.lm_rejected) == (r0.status, r0.iterations, r0.lm_accepted, r0.lm_rejected)
+        same(rep.final_cost, r0.final_cost); same(rep.initial_cost, r0.initial_cost)
+        same(i1, i0); same(p1, p0); same(e1, e0)
+
+
+@pytest.mark.parametrize("method", [_ffi.METHOD_GN, _ffi.METHOD_LM])
+def test_a_context_with_lockstep_members_and_a_problem_of_its_own(method):
+    """Context A holds two members of a lockstep group AND a rig that takes the per-context path; context B holds the group's third
+    member.  The members on A share one stream - the group's own when A comes first, another one when the order is reversed and B's
+    is the group's - and A's rig is solved on the caller's thread behind the group, never by A's helper thread."""
+    sps = [synth.make_problem(40, "eucm", seed=51), synth.make_problem(60, "eucm", seed=52, outlier_frac=0.02),
+           synth.make_problem(20, "eucm", n_cams=2, seed=53), synth.make_problem(50, "eucm", seed=54)]
+    a, b = Context(0), Context(0)
+    probs = [Problem.from_synth(c, s) for c, s in zip((a, a, a, b), sps)]
+    for p in probs:
+        p.apply_reference_bounds()
+    opts = default_opts(method)
+    alone = [p.solve(s.intr0, s.poses0, s.extr0, opts=opts) for p, s in zip(probs, sps)]
+    starts = [(s.intr0, s.poses0, s.extr0) for s in sps]
+    reps, res = Problem.solve_batch(probs, opts, starts=starts)
+    _assert_same_as_alone(alone, reps, res)
+    reps, res = Problem.solve_batch(probs[::-1], opts, starts=starts[::-1])          # the group's first context is B
+    _assert_same_as_alone(alone[::-1], reps, res)
+    for p, s in zip(probs, sps):                                                         # device-resident form
+        p.upload_params(s.intr0, s.poses0, s.extr0)
+    reps, none = Problem.solve_batch(probs, opts)
+    assert none is None
+    _assert_same_as_alone(alone, reps, [p.download_params() for p in probs])
+    for p in probs:
+        p.close()
+
+
+@pytest.mark.parametrize("method", [_ffi.METHOD_GN, _ffi.METHOD_LM])
+def test_members_sent_back_by_the_group_are_solved_on_their_own(method, monkeypatch):
+    """The plan groups by size, model and lane mapping; whether a problem's workspace takes single-launch groups at all is known
+    only once it is prepared.  With the second library's CCAL_FUSE_ELIM=0 (read when the workspace is made: the separate elimination
+    launch) three problems are planned as one group, every one of them is sent back and solved on its own behind the group - with
+    the results of solving it alone, and again in a second batch."""
+    lib = _ffi.load_legacy()
+    sps = [synth.make_problem(60, "eucm", seed=60 + i) for i in range(3)]
+    probs = [Problem.from_synth(Context(0, lib=lib), s) for s in sps]
+    for p in probs:
+        p.apply_reference_bounds()
+    opts = default_opts(method)
+    monkeypatch.setenv("CCAL_FUSE_ELIM", "0")
+    alone = [p.solve(s.intr0, s.poses0, s.extr0, opts=opts) for p, s in zip(probs, sps)]      # workspaces (and the choice) made under the switch
+    starts = [(s.intr0, s.poses0, s.extr0) for s in sps]
+    for _ in range(2):
+        reps, res = Problem.solve_batch(probs, opts, starts=starts)
+        _assert_same_as_alone(alone, reps, res)
+    monkeypatch.delenv("CCAL_FUSE_ELIM")
+    for p in probs:
+        p.close()
+
+
 def test_batch_argument_checks():
     sp = synth.make_problem(10, "eucm")
     ctx = Context(0)

@@ -4,7 +4,7 @@ The GPU parity tests elsewhere run on device memory that happens to be clean (fr
 session's contexts hand out blocks that earlier tests filled with plausible numbers): a kernel that reads a slice nobody wrote
 goes unseen there.  Here each case runs on a FRESH context of the second library (libccal_hip_legacy.so, -DCCAL_TEST_HOOKS) with
 CCAL_TEST_POISON_ALLOC=1: every block of doubles the library allocates - fresh or handed back by the context's block cache - is
-filled with 0xFF bytes (a quiet NaN) before the library's own clears and uploads (test_poison_f64, csrc/ccal_solver.hip).  A result
+filled with 0xFF bytes (a quiet NaN) before the library's own clears and uploads (test_poison_f64, csrc/ccal_solver_ws.hip).  A result
 that depends on what was in memory before turns into NaN or a wrong verdict.  Each case must
 
   * equal the oracle at the suite's tolerances: |dr| <= 1e-10, |dJ| <= 1e-11 max(1, |J|), S / b 1e-9 of their largest entry, cost
@@ -216,7 +216,7 @@ def test_mode_e_errors_and_validation(oracle, model, n_cams, frames):
     ("ragged10000", (GN, LM)),      # the benchmark's ragged workload: k_gram2i<..., SORTED=true> over the folded table
 ], ids=["session600", "ocv5_300", "ragged2500", "spread3000", "ragged10000"])
 def test_single_camera_solve(oracle, key, methods):
-    """Single-camera solves of every size class (csrc/ccal_solver.hip: kZeroCopyBytes = 96 KB = 2 048 frames of poses,
+    """Single-camera solves of every size class (csrc/ccal_normal.hpp: kZeroCopyBytes = 96 KB = 2 048 frames of poses,
     kSpreadBytes = 256 KB = 5 461 frames; FusedJob::begin chooses single-launch groups or the three-launch form) against the
     oracle on poisoned memory."""
     sp = _case(key)
@@ -305,7 +305,7 @@ def test_build_normal(oracle, key):
 # ---- rigs: the general loop -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key", ["rig2", "rig_schurq", "rig_mixed"])
 def test_rig_solve(oracle, key):
-    """The general loop (solve_general: k_gram1v / k_gram2g records, k_schur, k_reduce, k_backsub): a two-camera rig of one model
+    """The general loop (GeneralJob, csrc/ccal_solver.hip: k_gram1v / k_gram2g records, k_schur, k_reduce, k_backsub): a two-camera rig of one model
     (one merged Gram launch), the k_schurq rig with holes in G, and the ragged KB4 + EUCM rig: 5 464 observation frames, more than
     the 4 000 up to which the Gram kernels' prologue forms the candidate poses, so the separate k_backsub launch runs
     (ccal_solver.hip: gen_backsub).  GN and LM."""
