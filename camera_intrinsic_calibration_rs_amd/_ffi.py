@@ -82,6 +82,20 @@ class DetectTagsOpts(C.Structure):          # ccal_detect_tags_opts: every field
 # bits of ccal_detect_tags_*'s flags_out: an out-edge list was cut; more candidates than cand_cap, quads than quad_cap, tags than tag_cap
 TAGS_FLAG_CUT, TAGS_FLAG_CAND_CAP, TAGS_FLAG_QUAD_CAP, TAGS_FLAG_TAG_CAP = 1, 2, 4, 8
 
+
+class DetectCheckerboardsOpts(C.Structure):          # ccal_detect_checkerboards_opts: every field is the stage parameter of that name
+    _fields_ = [
+        ("step", C.c_int32), ("nms_radius", C.c_int32), ("min_response", C.c_int64), ("rel_q10", C.c_int32), ("cand_cap", C.c_int32),
+        ("half_win", C.c_int32), ("max_iterations", C.c_int32), ("eps", C.c_double),
+        ("cols", C.c_int32), ("rows", C.c_int32), ("reserved_", C.c_int64),
+    ]
+
+
+# the checkerboard assembly's limits (CCAL_BOARD_*) and the bits of its flags_out: more candidates than cand_cap (the fused call
+# only), more than BOARD_MAX_KEPT rows kept after the screen - no board
+BOARD_MIN_SIDE, BOARD_MAX_SIDE, BOARD_MAX_ROWS, BOARD_MAX_KEPT = 2, 20, 4096, 512
+BOARD_FLAG_CAND_CAP, BOARD_FLAG_KEPT_LIMIT = 1, 2
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 LIB_PATH = os.environ.get("CCAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libccal_hip.so")
@@ -212,6 +226,12 @@ SYMBOLS = [
                                          _ip, _ip, _ip, _ip, _dp, _dp, _ip, _ip]),
     ("ccal_detect_tags_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _up, C.c_int, C.POINTER(DetectTagsOpts),
                                        _ip, _ip, _ip, _ip, _dp, _dp, _ip, _ip]),
+    # from pixels to detections: a complete checkerboard from corner candidates; images to boards in one device-resident call
+    ("ccal_assemble_checkerboards_batch", C.c_int, [_vp, C.c_int, _lp, _dp, _dp, C.c_int, C.c_int, _ip, _dp, _ip, _ip, _ip]),
+    ("ccal_detect_checkerboards_batch", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(DetectCheckerboardsOpts),
+                                                  _ip, _dp, _ip, _ip]),
+    ("ccal_detect_checkerboards_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(DetectCheckerboardsOpts),
+                                                _ip, _dp, _ip, _ip]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

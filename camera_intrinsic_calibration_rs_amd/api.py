@@ -31,6 +31,7 @@ meaning and error behaviour), driving the HIP engine through the C ABI.
   the same up to the tags, in one device-resident call                  detect_tags (detect_aprilgrid(fused=True))
   a detector for plain checkerboards (the reference's tag detector is in the absent aprilgrid crate)
                                                                         detect_checkerboard, assemble_checkerboard
+  the same in one device-resident call                                  detect_checkerboard(fused=True)
   (util::try_init_camera / init_and_calibrate_one_camera, src/util.rs:107-159, 831-911: the glue over these pieces is
    not here yet - see README, "From detections alone")
 
@@ -979,16 +980,35 @@ def _full_window(cell: Dict[Tuple[int, int], int], cols: int, rows: int) -> Opti
 
 def detect_checkerboard_points(images, pattern: Tuple[int, int], square_size: float, step: int = 1, nms_radius: int = 5,
                                rel_threshold: float = 0.1, half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3,
-                               min_response: int = 1, max_per_image: int = 4096,
-                               ctx: Optional[Context] = None) -> List[Optional[Dict[int, Tuple[float, float]]]]:
-    """detect_checkerboard without the FrameFeature wrapping: per image {id: (x, y)} in f64, or None."""
+                               min_response: int = 1, max_per_image: int = 4096, ctx: Optional[Context] = None,
+                               fused: bool = False) -> List[Optional[Dict[int, Tuple[float, float]]]]:
+    """detect_checkerboard without the FrameFeature wrapping: per image {id: (x, y)} in f64, or None.
+    fused=True: detector, refinement and assembly as ONE device-resident call (ccal_detect_checkerboards_batch; pattern sides
+    2 .. 20, max_per_image at most 4096); the assembly follows the rule stated in include/ccal.h, which is assemble_checkerboard's
+    method with every operation spelled out.  An image that keeps more than 512 candidates after the strength screen is beyond the
+    device rule's limit and goes through the staged chain alone, so the limit does not show here."""
     if len(images) == 0:
         return []
     imgs = [np.asarray(im) for im in images]
     if any(im.ndim != 2 or im.shape != imgs[0].shape or im.dtype != imgs[0].dtype for im in imgs):
         raise ValueError("detect_checkerboard: single-channel images [H][W] of one size and type")
     stack, _, _ = check_images(np.stack(imgs), True)
+    cols, rows = int(pattern[0]), int(pattern[1])
+    if fused and (not (_ffi.BOARD_MIN_SIDE <= cols <= _ffi.BOARD_MAX_SIDE and _ffi.BOARD_MIN_SIDE <= rows <= _ffi.BOARD_MAX_SIDE)
+                  or not float(square_size) > 0.0):
+        raise ValueError("detect_checkerboard: fused: pattern (cols, rows) in 2 .. 20 each, square_size > 0")
+    if fused and not 1 <= int(max_per_image) <= _ffi.BOARD_MAX_ROWS:
+        raise ValueError("detect_checkerboard: fused: max_per_image in 1 .. 4096")
     c = _ctx(ctx)
+    if fused:
+        got = c.detect_checkerboards_batch(stack, cols, rows, step, nms_radius, min_response, rel_threshold, max_per_image, half_win,
+                                           max_iterations, eps)
+        out = [{i: (float(x), float(y)) for i, (x, y) in enumerate(xy)} if found else None for found, xy, _, _ in got]
+        for k, (_, _, flags, _) in enumerate(got):
+            if flags & _ffi.BOARD_FLAG_KEPT_LIMIT:
+                out[k] = detect_checkerboard_points([stack[k]], pattern, square_size, step, nms_radius, rel_threshold, half_win,
+                                                    max_iterations, eps, min_response, max_per_image, c)[0]
+        return out
     found = c.detect_corners_batch(stack, step, nms_radius, min_response, rel_threshold, max_per_image)
     xy, status, _, _ = c.refine_corners_batch(stack, [f[0].astype(np.float64) for f in found], half_win, max_iterations, eps)
     out: List[Optional[Dict[int, Tuple[float, float]]]] = []
@@ -1000,7 +1020,8 @@ def detect_checkerboard_points(images, pattern: Tuple[int, int], square_size: fl
 
 def detect_checkerboard(images, pattern: Tuple[int, int], square_size: float, step: int = 1, nms_radius: int = 5,
                         rel_threshold: float = 0.1, half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3,
-                        min_response: int = 1, max_per_image: int = 4096, ctx: Optional[Context] = None) -> List[Optional[FrameFeature]]:
+                        min_response: int = 1, max_per_image: int = 4096, ctx: Optional[Context] = None,
+                        fused: bool = False) -> List[Optional[FrameFeature]]:
     """From images alone to detections of a plain checkerboard of pattern = (cols, rows) inner corners: the integer saddle detector
     over all images in one call (ccal_detect_corners_batch), the sub-pixel refinement of its candidates (refine_corners' rule;
     corners whose status is not CCAL_OK are dropped), then assemble_checkerboard per image.  images: grey [H][W] each, uint8 or
@@ -1008,10 +1029,14 @@ def detect_checkerboard(images, pattern: Tuple[int, int], square_size: float, st
     (p2d stored as f32 like the reference's FeaturePoint, p3d = (c * square_size, r * square_size, 0) for id = r * cols + c), or
     None where no complete board was found - partial boards are not returned.  The labelling's symmetry: assemble_checkerboard.
     min_response scales with the square of the image contrast; as for refine_corners' min_lambda no useful value has been measured
-    here, and the default 1 screens only flat and edge-only neighbourhoods (rel_threshold does the work)."""
+    here, and the default 1 screens only flat and edge-only neighbourhoods (rel_threshold does the work).
+    fused=True runs the same chain as ONE call that keeps every intermediate on the device (detect_checkerboard_points states its
+    limits); the positions are the same refined corners, and the assembly's decisions are the host function's on every input of
+    the tests (its closed forms can round differently from the host's eigen-solver in the last bit).  The default is the staged
+    chain above."""
     cols = int(pattern[0])
     pts = detect_checkerboard_points(images, pattern, square_size, step, nms_radius, rel_threshold, half_win, max_iterations, eps,
-                                     min_response, max_per_image, ctx)
+                                     min_response, max_per_image, ctx, fused)
     out: List[Optional[FrameFeature]] = []
     for k, found in enumerate(pts):
         if found is None:

@@ -568,4 +568,8 @@ struct SelectArgs {
     int32_t n_img, cap, rows;           // cap: the most quads of one image (the walk's clamp); rows: tags stored per image
 };
 hipError_t tagchain_enqueue_select(hipStream_t s, const SelectArgs& a);
+// the chain's two plain links, which ccal_detect_checkerboards_* (ccal_kernels_board.hip) shares: off[k + 1] = the sum over i <= k of
+// min(count[i], cap), off[0] = 0; and n stored int32 values as f64
+hipError_t tagchain_enqueue_offsets(hipStream_t s, const int32_t* count, size_t cap, size_t n, int64_t* off);
+hipError_t tagchain_enqueue_starts(hipStream_t s, const int32_t* in, double* out, int64_t n);
 }  // namespace ccal

@@ -172,12 +172,17 @@ hipError_t tagchain_enqueue_select(hipStream_t s, const SelectArgs& a) {
     return hipGetLastError();
 }
 
-namespace {
-
-hipError_t enqueue_offsets(hipStream_t s, const int32_t* count, size_t cap, size_t n, int64_t* off) {
+hipError_t tagchain_enqueue_offsets(hipStream_t s, const int32_t* count, size_t cap, size_t n, int64_t* off) {
     hipLaunchKernelGGL(k_chain_offsets, dim3(1), dim3(64), 0, s, count, (int32_t)cap, (int32_t)n, off);
     return hipGetLastError();
 }
+
+hipError_t tagchain_enqueue_starts(hipStream_t s, const int32_t* in, double* out, int64_t n) {
+    hipLaunchKernelGGL(k_chain_starts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
+    return hipGetLastError();
+}
+
+namespace {
 
 struct ChainOut {
     int32_t* count; int32_t* id; int32_t* rot; int32_t* hamming; double* corners; double* margin; int32_t* flags; int32_t* stats;
@@ -312,7 +317,7 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
 
         // 1. candidates, their offsets and stored rows; the host learns the counts
         if (blk.ok()) blk.note(detect_enqueue_find(st, dtype, da));
-        if (blk.ok()) blk.note(enqueue_offsets(st, da.count, C, m, blk.at(s_candoff)));
+        if (blk.ok()) blk.note(tagchain_enqueue_offsets(st, da.count, C, m, blk.at(s_candoff)));
         if (blk.ok()) blk.note(detect_enqueue_emit(st, da));
         blk.download(h_count.data(), da.count, m);
         if (blk.ok()) blk.note(hipStreamSynchronize(st));
@@ -322,11 +327,10 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
         // 2. - 5. starts, refinement, rounding and merge, the points' compact layout; the host learns the kept counts
         if (n_cand) {
             ca.n = (int64_t)n_cand;
-            hipLaunchKernelGGL(k_chain_starts, dim3((unsigned)((2 * n_cand + 255) / 256)), dim3(256), 0, st, da.oxy, ca.xy, (int64_t)(2 * n_cand));
-            blk.launched();
+            blk.note(tagchain_enqueue_starts(st, da.oxy, ca.xy, (int64_t)(2 * n_cand)));
             if (blk.ok()) blk.note(corners_enqueue(st, dtype, ca));
             if (blk.ok()) blk.note(tagchain_enqueue_merge(st, ma));
-            if (blk.ok()) blk.note(enqueue_offsets(st, ma.kept, C, m, blk.at(s_ptoff)));
+            if (blk.ok()) blk.note(tagchain_enqueue_offsets(st, ma.kept, C, m, blk.at(s_ptoff)));
             if (blk.ok()) {
                 hipLaunchKernelGGL(k_chain_compact, dim3((unsigned)((C + 255) / 256), (unsigned)m), dim3(256), 0, st, ma.off, blk.at(s_ptoff),
                                    ma.out, blk.at(s_pxy), (int32_t)C);
@@ -347,7 +351,7 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
                                    blk.at(s_qflags), (int32_t)C);
                 blk.launched();
             }
-            if (blk.ok()) blk.note(enqueue_offsets(st, blk.at(s_qcount), Q, m, blk.at(s_quadoff)));
+            if (blk.ok()) blk.note(tagchain_enqueue_offsets(st, blk.at(s_qcount), Q, m, blk.at(s_quadoff)));
             blk.download(h_qcount.data(), blk.at(s_qcount), m);
             blk.download(h_qflags.data(), blk.at(s_qflags), m);
             if (blk.ok()) blk.note(hipStreamSynchronize(st));

@@ -534,6 +534,70 @@ class Context:
                                  edge_min_contrast, max_quads, border, cell_samples, tag_min_contrast, max_border_errors, max_hamming,
                                  max_tags)
 
+    # -- from pixels to detections: complete checkerboards (ccal_assemble_checkerboards_batch, ccal_kernels_board.hip) ---------------
+    def assemble_checkerboards_batch(self, xy_list, hess_list, cols: int, rows: int):
+        """The corner candidates of every image of a batch ordered into a complete cols x rows checkerboard, all images in one call,
+        by the rule stated at ccal_assemble_checkerboards_batch in include/ccal.h.  xy_list: one array [n_i, 2] of refined (x, y)
+        per image; hess_list: one array [n_i, 3] of (hxx, hyy, hxy) per image as the detector returns them.  Returns one tuple per
+        image: (found, xy f64 [cols * rows, 2] in id order, idx int32 [cols * rows] - the image's row of each corner -, flags,
+        stats int32 [4] = rows kept, attempts that found a board, the winner's seed rank and pair); xy and idx are None without a
+        board.  flags: _ffi.BOARD_FLAG_KEPT_LIMIT - more than 512 rows kept after the screen, no board."""
+        where = "ccal_assemble_checkerboards_batch"
+        if len(xy_list) != len(hess_list):
+            raise ValueError(f"{where}: one array of Hessians per array of positions")
+        n_img = len(xy_list)
+        (offs, xy), (offs_h, hess) = _pack(xy_list, 2), _pack(hess_list, 3)
+        if not np.array_equal(offs, offs_h):
+            raise ValueError(f"{where}: one Hessian per position")
+        m, nw = max(n_img, 1), max(int(cols) * int(rows), 1)
+        found = np.full(m, -2, dtype=np.int32); flags = np.full(m, -2, dtype=np.int32); stats = np.full((m, 4), -2, dtype=np.int32)
+        oxy = np.full((m, nw, 2), np.nan); idx = np.full((m, nw), -2, dtype=np.int32)
+        rc = self.lib.ccal_assemble_checkerboards_batch(self.handle, n_img, _lp(offs), _dp(xy), _dp(hess), int(cols), int(rows),
+                                                        _ip(found), _dp(oxy), _ip(idx), _ip(flags), _ip(stats))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        return [(int(found[k]), oxy[k].copy() if found[k] else None, idx[k].copy() if found[k] else None, int(flags[k]), stats[k].copy())
+                for k in range(n_img)]
+
+    def _detect_boards(self, fn, where, ptr, dtype, width, height, n_img, cols, rows, step, nms_radius, min_response, rel_threshold,
+                       max_candidates, half_win, max_iterations, eps):
+        if not np.isfinite(rel_threshold):
+            raise ValueError(f"{where}: rel_threshold is not finite")
+        o = _ffi.DetectCheckerboardsOpts(
+            step=int(step), nms_radius=int(nms_radius), min_response=int(min_response), rel_q10=int(round(1024.0 * float(rel_threshold))),
+            cand_cap=int(max_candidates), half_win=int(half_win), max_iterations=int(max_iterations), eps=float(eps),
+            cols=int(cols), rows=int(rows))
+        m, nw = max(int(n_img), 1), max(int(cols) * int(rows), 1)
+        found = np.zeros(m, dtype=np.int32); flags = np.zeros(m, dtype=np.int32); stats = np.zeros((m, 4), dtype=np.int32)
+        oxy = np.full((m, nw, 2), np.nan)
+        rc = fn(self.handle, int(dtype), int(width), int(height), int(n_img), C.c_void_p(ptr), C.byref(o), _ip(found), _dp(oxy),
+                _ip(flags), _ip(stats))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+        return [(int(found[k]), oxy[k].copy() if found[k] else None, int(flags[k]), stats[k].copy()) for k in range(int(n_img))]
+
+    def detect_checkerboards_batch(self, images, cols: int, rows: int, step: int = 1, nms_radius: int = 5, min_response: int = 1,
+                                   rel_threshold: float = 0.1, max_candidates: int = 4096, half_win: int = 5, max_iterations: int = 30,
+                                   eps: float = 1e-3):
+        """From a batch of grey images to the complete cols x rows checkerboard in each, in ONE call that keeps every intermediate
+        on the device: detector, refinement, the CCAL_OK corners with their Hessians, assembly - by the rule stated at
+        ccal_detect_checkerboards_batch in include/ccal.h.  images: [n][H][W], uint8 or uint16; the other parameters are the stages'
+        (detect_corners_batch, refine_corners_batch; max_candidates at most 4096).  Returns one tuple per image: (found, xy f64
+        [cols * rows, 2] in id order or None, flags, stats int32 [4] as assemble_checkerboards_batch); flags:
+        _ffi.BOARD_FLAG_CAND_CAP, _ffi.BOARD_FLAG_KEPT_LIMIT."""
+        images, batch = _grey_batch(images, "detect_checkerboards_batch")
+        return self._detect_boards(self.lib.ccal_detect_checkerboards_batch, "ccal_detect_checkerboards_batch", *batch, cols, rows,
+                                   step, nms_radius, min_response, rel_threshold, max_candidates, half_win, max_iterations, eps)
+
+    def detect_checkerboards_dev(self, images_ptr: int, dtype: int, width: int, height: int, n_img: int, cols: int, rows: int,
+                                 step: int = 1, nms_radius: int = 5, min_response: int = 1, rel_threshold: float = 0.1,
+                                 max_candidates: int = 4096, half_win: int = 5, max_iterations: int = 30, eps: float = 1e-3):
+        """detect_checkerboards_batch over an image block that is already on the device (a device pointer to [n_img][height][width]
+        of dtype _ffi.PIX_U8 / PIX_U16, its writes complete or enqueued on the context's stream); the results are host arrays."""
+        return self._detect_boards(self.lib.ccal_detect_checkerboards_dev, "ccal_detect_checkerboards_dev", images_ptr, dtype, width,
+                                   height, n_img, cols, rows, step, nms_radius, min_response, rel_threshold, max_candidates, half_win,
+                                   max_iterations, eps)
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first

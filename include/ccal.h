@@ -911,6 +911,111 @@ int ccal_detect_tags_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_
                          double* corners_out /* [n_img][tag_cap][4][2] */, double* margin_out /* [n_img][tag_cap] or NULL */,
                          int32_t* flags_out /* [n_img] */, int32_t* stats_out /* [n_img][4] or NULL */);
 
+/* ---- from pixels to detections: a complete checkerboard from corner candidates ----------------------------------------------------
+ * The corner candidates of an image - refined positions and the detector's Hessians - ordered into a plain checkerboard of
+ * cols x rows inner corners, all images of a batch at once; and the chain from images to boards in one device-resident call.
+ * tests/board_ref.py is the numpy f64 yardstick of the rule below; the board unit is compiled without fused multiply-adds, and its
+ * outputs equal the yardstick's to the bit.  Every operation is an IEEE f64 + - * / or sqrt, rounded on its own, in the order
+ * written; |v| of a 2-vector is sqrt(vx vx + vy vy).
+ *
+ * Limits: cols, rows in CCAL_BOARD_MIN_SIDE .. CCAL_BOARD_MAX_SIDE (2 .. 20); at most CCAL_BOARD_MAX_ROWS (4096) input rows per
+ * image; at most CCAL_BOARD_MAX_KEPT (512) rows kept after the screen - an image over that limit gets flag bit 1
+ * (CCAL_BOARD_FLAG_KEPT_LIMIT) and no board, never a partial result.  Positions must be small enough that the squares of their
+ * differences do not overflow.
+ *
+ * Per image, rows i = 0 .. m - 1 of (x, y) and (hxx, hyy, hxy) - hxy is four times the mixed derivative, as the detector stores it:
+ *   1 screen   R = hxy hxy - (16 hxx) hyy.  A row is usable when x, y and R are finite and R > 0.  Fewer than cols * rows
+ *              usable rows: no board, 0 rows kept.  Rank the usable rows by (R descending, i ascending); t = 0.5 R of the row of rank
+ *              cols rows - 1; the usable rows with R >= t are kept.
+ *   2 order    the n kept rows sorted by (y, x, i) ascending: the slots 0 .. n - 1 everything below speaks of.
+ *   3 edges    per slot b = hxy / 4, mu = 0.5 (hxx + hyy), dl = 0.5 (hxx - hyy), r = sqrt(dl dl + b b), l1 = mu + r, l0 = mu - r;
+ *              v = (dl + r, b) when dl >= 0, else (b, r - dl); v = v / |v| ((1, 0) when |v| is not > 0); w = (-vy, vx);
+ *              A = sqrt(max(l1, 0)), B = sqrt(max(-l0, 0)); d1 = B v + A w, d2 = B v + (-A) w, each divided by max(|d|, 1e-300):
+ *              the two zero-curvature directions of [[hxx, b], [b, hyy]].  The four directions of a slot are d1, d2, -d1, -d2.
+ *   4 links    for slots a != b: e = P[b] - P[a], dist = |e|, u = e / dist; cos(a, k, b) = d_k(a).x ux + d_k(a).y uy for k = 0, 1
+ *              and its negative for k = 2, 3.  b is seen from a along k when dist > 0, cos(a, k, b) > 0.9, some cos(b, k', a) > 0.9
+ *              (u turns its sign exactly) and the polarities are opposite: (hxx_a hxx_b + hyy_a hyy_b) + (2 b_a) b_b < 0.
+ *              link[a][k] = the nearest such b, the lower slot on equal distances, or none.
+ *   5 attempts seeds in (R descending, slot ascending) order - the seed rank -, for each the edge pairs (kb, kc) = (0, 1), (0, 3),
+ *              (2, 1), (2, 3) in that order; an attempt exists when link[s][kb] and link[s][kc] exist and differ.
+ *   6 grow     the lattice starts as s at cell (0, 0), link[s][kb] at (1, 0), link[s][kc] at (0, 1).  A sweep visits, in ascending
+ *              (i, j), the empty cells with |i|, |j| <= cols + rows that had a filled 4-neighbour when the sweep began; a cell
+ *              filled earlier in the sweep is seen by the predictions of the later ones.  The prediction of cell (i, j): for the
+ *              steps (di, dj) = (1, 0), (0, 1), (-1, 0), (0, -1), with p1 = (i - di, j - dj) and p2 = (i - 2 di, j - 2 dj) both
+ *              filled: 2 P[p1] - P[p2] with span |P[p1] - P[p2]|; then for (di, dj) = (1, 1), (1, -1), (-1, 1), (-1, -1), with
+ *              p1 = (i - di, j), p2 = (i, j - dj), p3 = (i - di, j - dj) all filled: (P[p1] + P[p2]) - P[p3] with span the smaller
+ *              of |P[p1] - P[p3]|, |P[p2] - P[p3]|.  The stencils that apply are summed in that order, coordinate by coordinate,
+ *              the sum divided by their number; the span is the smallest.  No stencil: the cell stays empty.  The cell takes the
+ *              slot q not in the lattice with d = |P[q] - prediction| <= 0.3 span whose polarity is opposite to that of every
+ *              filled 4-neighbour of the cell, the smallest d, the lower slot on equal d.  Sweeps repeat until one fills nothing.
+ *   7 settle   up to three rounds over the filled cells in ascending (i, j): the cell is emptied and its slot freed, step 6's
+ *              choice is made for it (its own slot when there is none); a round that changes nothing is the last.
+ *   8 window   over the box of the filled cells: the cols x rows and rows x cols windows in which every cell is filled.  The
+ *              attempt finds a board when there is exactly one.  The FIRST attempt in (seed rank, pair) order that does is the
+ *              winner; every attempt is run and counted whatever the others do.
+ *   9 label    G[j][i] = the window, h x w.  With o = P[G[0][0]], ec = P[G[0][1]] - o, er = P[G[1][0]] - o: when
+ *              ec.x er.y - ec.y er.x < 0 the window is mirrored in i.  Of the turns A[r][c] = G[r][c], G[c][w-1-r],
+ *              G[h-1-r][w-1-c], G[h-1-c][r] those of shape rows x cols are admissible; the one whose A[0][0] is smallest in
+ *              (y, x) wins, the earlier on a tie.  Corner id = r cols + c is A[r][c]; its board point is (c, r) squares.
+ * The method is that of the Python layer's assemble_checkerboard, which states the reasons; a partial board gives none.
+ *
+ * ccal_assemble_checkerboards_batch: all arrays are host pointers.  offsets [n_img + 1] (offsets[0] == 0, no decrease); xy
+ * [offsets[n_img]][2]; hess [offsets[n_img]][3].  Per image k: found_out[k] = 0 / 1; xy_out [n_img][cols rows][2] = the positions
+ * in id order, copies of the input; idx_out [n_img][cols rows] (NULL: not wanted) = the image's row index of each; flags_out[k]
+ * (bit 1 only); stats_out [n_img][4] (NULL: not wanted) = rows kept, attempts that found a board, the winner's seed rank and pair
+ * (-1, -1 without a winner).  The xy_out and idx_out rows of an image without a board are not written.
+ *
+ * ccal_detect_checkerboards_batch / _dev: images in, boards out, nothing coming back between the stages.  Images as above.  Every
+ * field of ccal_detect_checkerboards_opts is the stage parameter of that name and has its range, cand_cap in 1 .. 4096; there are no
+ * defaults (the Python layer's: step 1, nms_radius 5, min_response 1, rel_q10 102, cand_cap 4096; half_win 5, max_iterations 30,
+ * eps 1e-3).  Per image:
+ *   1 candidates  ccal_detect_corners_* with (step, nms_radius, min_response, rel_q10): the first min(count, cand_cap) in row-major order.
+ *   2 starts      the integer (x, y) of each stored candidate as f64.
+ *   3 refine      ccal_refine_corners_* with (half_win, max_iterations, eps) on those starts.
+ *   4 rows        the corners with status CCAL_OK in candidate order, each with its candidate's Hessian as f64.
+ *   5 assemble    the rule above with (cols, rows).
+ * Outputs per image k: found_out[k]; xy_out [n_img][cols rows][2] in f64 as refined, before any rounding to f32, not written
+ * without a board; flags_out[k]: bit 0 (CCAL_BOARD_FLAG_CAND_CAP) more candidates than cand_cap, bit 1 the kept limit; stats_out
+ * [n_img][4] (NULL: not wanted) as above.
+ * All three are pure functions of an image's rows (of the image and the options): the outputs do not depend on the image's place
+ * in the batch, on what else is in it, on how the library cuts the batch into chunks or on the run.  No atomics; every order is an
+ * index order.  The _dev form takes a device pointer to the images (the output of ccal_remap_dev on this context's stream, or a
+ * block whose writes are complete); everything else stays a host array.  All return when the outputs are written.
+ * CCAL_ERR_INVALID_ARG, nothing launched or written: cols or rows outside 2 .. 20, n_img < 0, offsets that decrease or do not start
+ * at 0, more than 4096 rows in an image, opts NULL, a field outside its stage's range, cand_cap outside 1 .. 4096, a dtype other
+ * than the two, width, height <= 0, more than 2^31 - 1 pixels in an image, a NULL required pointer (with n_img > 0: offsets, xy and
+ * hess when there is a row, images, found_out, xy_out, flags_out).  n_img == 0 is valid. */
+#define CCAL_BOARD_MIN_SIDE 2
+#define CCAL_BOARD_MAX_SIDE 20
+#define CCAL_BOARD_MAX_ROWS 4096
+#define CCAL_BOARD_MAX_KEPT 512
+#define CCAL_BOARD_FLAG_CAND_CAP 1
+#define CCAL_BOARD_FLAG_KEPT_LIMIT 2
+int ccal_assemble_checkerboards_batch(ccal_ctx* ctx, int n_img, const int64_t* offsets /* [n_img + 1] */, const double* xy,
+                                      const double* hess, int cols, int rows, int32_t* found_out /* [n_img] */,
+                                      double* xy_out /* [n_img][cols*rows][2] */, int32_t* idx_out /* [n_img][cols*rows] or NULL */,
+                                      int32_t* flags_out /* [n_img] */, int32_t* stats_out /* [n_img][4] or NULL */);
+typedef struct {
+    /* detector */
+    int32_t step, nms_radius;
+    int64_t min_response;
+    int32_t rel_q10, cand_cap;
+    /* refinement */
+    int32_t half_win, max_iterations;
+    double eps;
+    /* assembly */
+    int32_t cols, rows;
+    int64_t reserved_;
+} ccal_detect_checkerboards_opts;
+int ccal_detect_checkerboards_batch(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images,
+                                    const ccal_detect_checkerboards_opts* opts, int32_t* found_out /* [n_img] */,
+                                    double* xy_out /* [n_img][cols*rows][2] */, int32_t* flags_out /* [n_img] */,
+                                    int32_t* stats_out /* [n_img][4] or NULL */);
+int ccal_detect_checkerboards_dev(ccal_ctx* ctx, int dtype, int width, int height, int n_img, const void* images_dev,
+                                  const ccal_detect_checkerboards_opts* opts, int32_t* found_out /* [n_img] */,
+                                  double* xy_out /* [n_img][cols*rows][2] */, int32_t* flags_out /* [n_img] */,
+                                  int32_t* stats_out /* [n_img][4] or NULL */);
+
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
                              double* err_out /* [n_corners] Euclidean px error */);
