@@ -3,6 +3,7 @@
 //   CallPlan   the slices in order and the total - plain arithmetic, no context and no HIP call (ccal_plan.hpp)
 //   CallBlock  the plan, the block and a sticky hipError_t: after the first failure every step is a no-op and finish() reports it;
 //              the destructor drains the stream before the block goes back to the context's cache, on every way out
+//   BadArg     the way out of an entry point on a bad argument, with the call's name in the message
 //   check_offsets  the argument check of a batched call's CSR offsets, with the call's name in the message
 //   GreyBatch  the image arguments of the image stages' calls: their check, an image's bytes, the device pointer to a chunk's images
 //   test_chunk_bytes  the tests' way to make those calls cut a small batch into chunks
@@ -21,18 +22,20 @@ inline int hip_fail(ccal_ctx* ctx, const char* where, hipError_t e) {
     try { ctx->err = std::string(where) + ": " + hipGetErrorString(e); } catch (...) { }
     return CCAL_ERR_HIP;
 }
+// an entry point's way out on a bad argument: bad("what") is CCAL_ERR_INVALID_ARG with "<where>: <what>" as the context's message
+struct BadArg {
+    ccal_ctx* ctx; const char* where;
+    int operator()(const char* what) const { char msg[160]; snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); }
+};
 
 // offsets[0] == 0, then over the n problems offsets[0 .. n]: no decrease and, with max_span > 0 (2^24, what the kernels index a
 // problem by), no problem of more points.  CCAL_OK, or CCAL_ERR_INVALID_ARG with "<where>: <name>..." as the context's message.
 inline int check_offsets(ccal_ctx* ctx, const char* where, const char* name, const int64_t* offsets, size_t n, int64_t max_span) {
-    const char* bad = offsets[0] != 0 ? "%s: %s[0] != 0" : nullptr;
+    const char* bad = offsets[0] != 0 ? "[0] != 0" : nullptr;
     for (size_t i = 0; i < n && !bad; ++i)
         if (offsets[i + 1] < offsets[i] || (max_span > 0 && offsets[i + 1] - offsets[i] > max_span))
-            bad = max_span > 0 ? "%s: %s must not decrease, at most 2^24 points in a problem" : "%s: %s must not decrease";
-    if (!bad) return CCAL_OK;
-    char msg[160];
-    snprintf(msg, sizeof msg, bad, where, name);
-    return fail(ctx, CCAL_ERR_INVALID_ARG, msg);
+            bad = max_span > 0 ? " must not decrease, at most 2^24 points in a problem" : " must not decrease";
+    return bad ? BadArg{ ctx, where }((std::string(name) + bad).c_str()) : CCAL_OK;
 }
 
 class CallBlock : public CallPlan {

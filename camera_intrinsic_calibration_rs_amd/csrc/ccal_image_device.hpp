@@ -1,5 +1,5 @@
 // What the kernels of the image stages share (ccal_kernels_detect / corners / quads / tags / tagchain / board.hip): the f64 bilinear sample,
-// the row-to-image search over CSR offsets, the hand-off between lanes of one wavefront and the wavefront's int32 scan.  Header only,
+// the row-to-image search over CSR offsets and an image's clamped span of them, the hand-off between lanes of one wavefront and the wavefront's int32 scan.  Header only,
 // every function forced inline: the code follows the flags of the unit that includes it (-ffp-contract=off for quads, tags and board, fast
 // for the others - csrc/Makefile), so there is no translation unit of its own.
 #pragma once
@@ -34,6 +34,12 @@ __device__ __forceinline__ int image_of_row(const int64_t* off, int n_img, int64
         if (off[mid] <= g) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// the rows of image k of a CSR batch that a walk may visit: off[k + 1] - off[k], clamped to 0 .. cap, the size its arrays were given
+__device__ __forceinline__ int csr_span(const int64_t* off, int k, int cap) {
+    const int64_t m = off[k + 1] - off[k];
+    return (int)(m < 0 ? 0 : (m > (int64_t)cap ? (int64_t)cap : m));
 }
 
 // floor and fraction of one coordinate, the two neighbour indices clamped to [0, n - 1]

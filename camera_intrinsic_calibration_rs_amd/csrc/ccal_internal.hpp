@@ -469,6 +469,8 @@ int solve_sharded_run(ccal_problem** shards, int n, const ccal_solver_opts* o, d
 // Each stage's argument block, its parameter check (the message of the first range missed, or nullptr) and its launch sequence live
 // in the stage's own translation unit, which keeps its compiler flags; the stage's entry points and ccal_detect_tags_*
 // (ccal_kernels_tagchain.hip) enqueue through the same routines.  A routine only enqueues on `s` and returns hipGetLastError().
+// Where DetectArgs and a chain's CornerArgs are filled, and the front both chains run per chunk (images to refined candidates):
+// ccal_chain_front.hpp, host only.
 // ccal_kernels_detect.hip
 struct DetectArgs {
     const void* img;                    // [n][H][W] of T

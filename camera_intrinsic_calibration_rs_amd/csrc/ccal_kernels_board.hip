@@ -19,21 +19,16 @@
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include "ccal_call.hpp"
+#include "ccal_chain_front.hpp"
 #include "ccal_image_device.hpp"
-#include "ccal_tagchain_plan.hpp"
 
 namespace ccal {
 
-constexpr int kBoardMaxRows = CCAL_BOARD_MAX_ROWS, kBoardMaxKept = CCAL_BOARD_MAX_KEPT;
+constexpr int kBoardMaxRows = CCAL_BOARD_MAX_ROWS;     // kBoardMaxKept and the bytes per row: ccal_tagchain_plan.hpp
 constexpr int kBoardMinSide = CCAL_BOARD_MIN_SIDE, kBoardMaxSide = CCAL_BOARD_MAX_SIDE;
-constexpr size_t kBoardChunkBytes = (size_t)256 << 20;    // the block one chunk should need: larger batches go image chunk by chunk
 constexpr double kBoardCone = 0.9, kBoardWeak = 0.5, kBoardReach = 0.3;
 constexpr int kBoardNew = 0x4000, kBoardNone = 0x7fffffff;
 static_assert(kBoardMaxKept <= 512, "a lane's candidates are the bits of one byte; an index and the sweep's mark share an int16");
-// device bytes per input row (xy 16, Hessian 24 or 12, response 8, kept index 4, status 4 in the chain) and per kept-row slot
-// (position 16, M 24, response 8, directions 32, input row 4, links 16, seed 4, attempt bits 4)
-constexpr size_t kBoardPerRowBytes = 56, kBoardPerKeptBytes = 108, kBoardPerImageBytes = 64;
 
 struct BoardArgs {
     const int64_t* off;                 // [n_img + 1]: image k owns the rows [off[k], off[k + 1]) of xy, hess / hess_i, status, resp, kidx
@@ -58,11 +53,6 @@ struct BoardArgs {
     int32_t n_img, cols, rows, row_cap, K;
     int32_t per;                        // blocks per image of the launch (k_board_link, k_board_grow)
 };
-
-__device__ __forceinline__ int board_span(const int64_t* off, int k, int cap) {
-    const int64_t m = off[k + 1] - off[k];
-    return (int)(m < 0 ? 0 : (m > (int64_t)cap ? (int64_t)cap : m));
-}
 
 __device__ __forceinline__ void board_hess(const BoardArgs& a, int64_t row, double& hxx, double& hyy, double& hxy) {
     if (a.hess) { hxx = a.hess[3 * row]; hyy = a.hess[3 * row + 1]; hxy = a.hess[3 * row + 2]; }
@@ -91,7 +81,7 @@ __device__ __forceinline__ void board_directions(double a, double c, double b, d
 __global__ __launch_bounds__(64) void k_board_screen(const BoardArgs a) {
     const int k = blockIdx.x, lane = threadIdx.x;
     const int64_t first = a.off[k];
-    const int m = board_span(a.off, k, a.row_cap);
+    const int m = csr_span(a.off, k, a.row_cap);
     const int n_want = a.cols * a.rows;
     const double* xy = a.xy + 2 * first;
     double* resp = a.resp + first;
@@ -477,6 +467,39 @@ __global__ __launch_bounds__(64) void k_board_final(const BoardArgs a) {
 
 namespace {
 
+// The assembly's slices of a call's block, added as ints | doubles like the front's (ccal_chain_front.hpp) so that the doubles the kernels
+// write before they read lie together, resp .. oxy; rows: a chunk's input rows, mi: its images.  h_*: the host's side of a chunk.
+struct BoardSlices {
+    Slice<int32_t> kidx, orig, link, seed; Slice<uint8_t> hit; Slice<int32_t> kept, found, flags, stats, oidx;
+    Slice<double> resp, P, M, R, D, oxy;
+    size_t rows = 0, K = 0, mi = 0, nw = 0;
+    std::vector<int32_t> h_kept, h_found, h_flags, h_stats, h_idx; std::vector<double> h_xy;
+    void add_ints(CallBlock& blk, size_t rows_, size_t K_, size_t mi_, size_t nw_, bool with_idx) {
+        rows = rows_; K = K_; mi = mi_; nw = nw_;
+        kidx = blk.add<int32_t>(rows);
+        orig = blk.add<int32_t>(K * mi); link = blk.add<int32_t>(4 * K * mi); seed = blk.add<int32_t>(K * mi); hit = blk.add<uint8_t>(4 * K * mi);
+        kept = blk.add<int32_t>(mi); found = blk.add<int32_t>(mi); flags = blk.add<int32_t>(mi); stats = blk.add<int32_t>(4 * mi);
+        if (with_idx) oidx = blk.add<int32_t>(nw * mi);
+        h_kept.resize(mi); h_found.resize(mi); h_flags.resize(mi); h_stats.resize(4 * mi); h_idx.resize(with_idx ? nw * mi : 0); h_xy.resize(2 * nw * mi);
+    }
+    void add_doubles(CallBlock& blk) {
+        resp = blk.add<double>(rows);
+        P = blk.add<double>(2 * K * mi); M = blk.add<double>(3 * K * mi); R = blk.add<double>(K * mi); D = blk.add<double>(4 * K * mi);
+        oxy = blk.add<double>(2 * nw * mi);
+    }
+    BoardArgs args(const CallBlock& blk, int cols, int rows_) const {       // the caller sets off, xy, hess or hess_i, status, row_cap, n_img
+        BoardArgs a = {};
+        a.resp = blk.at(resp); a.kidx = blk.at(kidx);
+        a.P = blk.at(P); a.M = blk.at(M); a.R = blk.at(R); a.D = blk.at(D); a.orig = blk.at(orig); a.link = blk.at(link);
+        a.seed = blk.at(seed); a.hit = blk.at(hit); a.kept = blk.at(kept); a.found = blk.at(found); a.flags = blk.at(flags);
+        a.stats = blk.at(stats); a.oxy = blk.at(oxy); a.oidx = blk.at(oidx);
+        a.cols = cols; a.rows = rows_; a.K = (int32_t)K;
+        return a;
+    }
+};
+
+struct BoardsOut { int32_t* found; double* xy; int32_t* idx; int32_t* flags; int32_t* stats; };       // idx, stats: or NULL
+
 // screen; the host learns the kept counts; links, attempts, the board - sized by the largest kept count within the limit
 // h_kept: room for a.n_img counts.  Leaves the stream synchronised after the screen only.
 void board_run(CallBlock& blk, hipStream_t st, BoardArgs& a, std::vector<int32_t>& h_kept) {
@@ -499,19 +522,40 @@ void board_run(CallBlock& blk, hipStream_t st, BoardArgs& a, std::vector<int32_t
     if (blk.ok()) { hipLaunchKernelGGL(k_board_final, dim3((unsigned)m), dim3(64), lds, st, a); blk.launched(); }
 }
 
+// The boards of the chunk's images, which are the caller's k0 ..: down, the stream synchronised, and found, stats, xy and idx into
+// the caller's arrays - xy and idx only where there is a board.  The flags stay in h.h_flags: the caller decides how they go out.
+bool board_fetch(CallBlock& blk, hipStream_t st, const BoardArgs& a, BoardSlices& h, size_t k0, const BoardsOut& out) {
+    const size_t m = (size_t)a.n_img, nw = (size_t)a.cols * (size_t)a.rows;
+    blk.download(h.h_found.data(), a.found, m);
+    blk.download(h.h_flags.data(), a.flags, m);
+    blk.download(h.h_stats.data(), a.stats, 4 * m);
+    blk.download(h.h_xy.data(), a.oxy, 2 * nw * m);
+    blk.download(a.oidx ? h.h_idx.data() : nullptr, a.oidx, nw * m);
+    if (blk.ok()) blk.note(hipStreamSynchronize(st));
+    if (!blk.ok()) return false;
+    for (size_t i = 0; i < m; ++i) {
+        const size_t k = k0 + i;
+        out.found[k] = h.h_found[i];
+        if (out.stats) std::memcpy(out.stats + 4 * k, h.h_stats.data() + 4 * i, 4 * sizeof(int32_t));
+        if (!h.h_found[i]) continue;
+        std::memcpy(out.xy + 2 * nw * k, h.h_xy.data() + 2 * nw * i, 2 * nw * sizeof(double));
+        if (out.idx) std::memcpy(out.idx + nw * k, h.h_idx.data() + nw * i, nw * sizeof(int32_t));
+    }
+    return true;
+}
+
 const char* board_bad_pattern(int cols, int rows) {
-    if (cols < kBoardMinSide || cols > kBoardMaxSide || rows < kBoardMinSide || rows > kBoardMaxSide) return "cols, rows outside 2 .. 20";
-    return nullptr;
+    const bool bad = cols < kBoardMinSide || cols > kBoardMaxSide || rows < kBoardMinSide || rows > kBoardMaxSide;
+    return bad ? "cols, rows outside 2 .. 20" : nullptr;
 }
 
 int assemble_call(ccal_ctx* ctx, const char* where, int n_img, const int64_t* offsets, const double* xy, const double* hess, int cols,
-                  int rows, int32_t* found_out, double* xy_out, int32_t* idx_out, int32_t* flags_out, int32_t* stats_out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+                  int rows, const BoardsOut& out) {
+    const BadArg bad{ ctx, where };
     if (const char* what = board_bad_pattern(cols, rows)) return bad(what);
     if (n_img < 0) return bad("n_img < 0");
     if (n_img == 0) return CCAL_OK;
-    if (!offsets || !found_out || !xy_out || !flags_out) return bad("NULL argument");
+    if (!offsets || !out.found || !out.xy || !out.flags) return bad("NULL argument");
     if (check_offsets(ctx, where, "offsets", offsets, (size_t)n_img, 0)) return CCAL_ERR_INVALID_ARG;
     size_t most = 0;
     for (int k = 0; k < n_img; ++k) most = std::max(most, (size_t)(offsets[k + 1] - offsets[k]));
@@ -521,190 +565,87 @@ int assemble_call(ccal_ctx* ctx, const char* where, int n_img, const int64_t* of
     const size_t ni = (size_t)n_img, nw = (size_t)cols * (size_t)rows;
     const size_t K = std::max<size_t>(std::min(most, (size_t)kBoardMaxKept), 1);
     const ImageChunks plan = image_chunks(offsets, ni, K * kBoardPerKeptBytes + nw * 20 + kBoardPerImageBytes, kBoardPerRowBytes,
-                                          test_chunk_bytes("CCAL_TEST_BOARD_CHUNK_BYTES", kBoardChunkBytes));
+                                          test_chunk_bytes("CCAL_TEST_BOARD_CHUNK_BYTES", kChainChunkBytes));
     const size_t mi = plan.max_img, mr = plan.max_rows;
 
     CallBlock blk(ctx);
     const auto s_off = blk.add<int64_t>(mi + 1);
     const auto s_hess = blk.add<double>(3 * mr);           // uploaded, like s_xy: not poisoned
     const auto s_xy = blk.add<double>(2 * mr);
-    const auto s_kidx = blk.add<int32_t>(mr);
-    const auto s_orig = blk.add<int32_t>(K * mi);
-    const auto s_link = blk.add<int32_t>(4 * K * mi);
-    const auto s_seed = blk.add<int32_t>(K * mi);
-    const auto s_hit = blk.add<uint8_t>(4 * K * mi);
-    const auto s_kept = blk.add<int32_t>(mi);
-    const auto s_found = blk.add<int32_t>(mi);
-    const auto s_flags = blk.add<int32_t>(mi);
-    const auto s_stats = blk.add<int32_t>(4 * mi);
-    const auto s_oidx = blk.add<int32_t>(nw * mi);
-    const auto s_resp = blk.add<double>(mr);               // the doubles the kernels write before they read, from here on
-    const auto s_P = blk.add<double>(2 * K * mi);
-    const auto s_M = blk.add<double>(3 * K * mi);
-    const auto s_R = blk.add<double>(K * mi);
-    const auto s_D = blk.add<double>(4 * K * mi);
-    const auto s_oxy = blk.add<double>(2 * nw * mi);
+    BoardSlices bs;
+    bs.add_ints(blk, mr, K, mi, nw, true);
+    bs.add_doubles(blk);                                   // the doubles the kernels write before they read
     if (!blk.alloc()) return blk.finish(where);
 
-    BoardArgs a = {};
-    a.off = blk.at(s_off); a.xy = blk.at(s_xy); a.hess = blk.at(s_hess); a.resp = blk.at(s_resp); a.kidx = blk.at(s_kidx);
-    a.P = blk.at(s_P); a.M = blk.at(s_M); a.R = blk.at(s_R); a.D = blk.at(s_D); a.orig = blk.at(s_orig); a.link = blk.at(s_link);
-    a.seed = blk.at(s_seed); a.hit = blk.at(s_hit); a.kept = blk.at(s_kept); a.found = blk.at(s_found); a.flags = blk.at(s_flags);
-    a.stats = blk.at(s_stats); a.oxy = blk.at(s_oxy); a.oidx = blk.at(s_oidx);
-    a.cols = cols; a.rows = rows; a.row_cap = kBoardMaxRows; a.K = (int32_t)K;
-
+    BoardArgs a = bs.args(blk, cols, rows);
+    a.off = blk.at(s_off); a.xy = blk.at(s_xy); a.hess = blk.at(s_hess); a.row_cap = kBoardMaxRows;
     hipStream_t st = ctx->stream;
     std::vector<int64_t> h_off(mi + 1);
-    std::vector<int32_t> h_kept(mi), h_found(mi), h_flags(mi), h_stats(4 * mi), h_idx(nw * mi);
-    std::vector<double> h_xy(2 * nw * mi);
     for (size_t c = 0; c + 1 < plan.cut.size() && blk.ok(); ++c) {
         const size_t k0 = plan.cut[c], m = plan.cut[c + 1] - k0;
         const size_t at = (size_t)offsets[k0], nr = (size_t)(offsets[k0 + m] - offsets[k0]);
         for (size_t i = 0; i <= m; ++i) h_off[i] = offsets[k0 + i] - offsets[k0];
         a.n_img = (int32_t)m;
-        blk.poison(s_resp, s_oxy);
+        blk.poison(bs.resp, bs.oxy);
         blk.upload(s_off, h_off.data(), m + 1);
         blk.upload(s_xy, xy + 2 * at, 2 * nr);
         blk.upload(s_hess, hess + 3 * at, 3 * nr);
         if (!blk.ok()) break;
-        board_run(blk, st, a, h_kept);
-        blk.download(h_found.data(), a.found, m);
-        blk.download(h_flags.data(), a.flags, m);
-        blk.download(h_stats.data(), a.stats, 4 * m);
-        blk.download(h_xy.data(), a.oxy, 2 * nw * m);
-        blk.download(h_idx.data(), a.oidx, nw * m);
-        if (blk.ok()) blk.note(hipStreamSynchronize(st));
-        if (!blk.ok()) break;
-        for (size_t i = 0; i < m; ++i) {
-            const size_t k = k0 + i;
-            found_out[k] = h_found[i]; flags_out[k] = h_flags[i];
-            if (stats_out) std::memcpy(stats_out + 4 * k, h_stats.data() + 4 * i, 4 * sizeof(int32_t));
-            if (!h_found[i]) continue;
-            std::memcpy(xy_out + 2 * nw * k, h_xy.data() + 2 * nw * i, 2 * nw * sizeof(double));
-            if (idx_out) std::memcpy(idx_out + nw * k, h_idx.data() + nw * i, nw * sizeof(int32_t));
-        }
+        board_run(blk, st, a, bs.h_kept);
+        if (!board_fetch(blk, st, a, bs, k0, out)) break;
+        std::copy(bs.h_flags.begin(), bs.h_flags.begin() + m, out.flags + k0);          // the assembly's flags are the image's
     }
     return blk.finish(where);
 }
 
-struct BoardsOut { int32_t* found; double* xy; int32_t* flags; int32_t* stats; };
-
 int detect_boards_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, const ccal_detect_checkerboards_opts* o, const BoardsOut& out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    const BadArg bad{ ctx, where };
+    char buf[40];
     if (!o) return bad("NULL options");
-    if (const char* what = detect_bad_params(o->step, o->nms_radius, o->min_response, o->rel_q10, o->cand_cap)) return bad(what);
-    if (o->cand_cap > kBoardMaxRows) return bad("cand_cap outside 1 .. 4096");
-    if (const char* what = corners_bad_params(o->half_win, o->max_iterations, o->eps)) return bad(what);
+    const FrontParams fp = FrontParams::of(*o);
+    if (const char* what = front_bad_params(fp, kBoardMaxRows, buf)) return bad(what);
     if (const char* what = board_bad_pattern(o->cols, o->rows)) return bad(what);
     if (const char* what = b.bad()) return bad(what);
     if (b.n_img == 0) return CCAL_OK;
     if (!b.images || !out.found || !out.xy || !out.flags) return bad("NULL argument");
 
-    const int dtype = b.dtype, width = b.width, height = b.height;
     const size_t ni = (size_t)b.n_img, nw = (size_t)o->cols * (size_t)o->rows;
     std::fill(out.found, out.found + ni, 0);
     std::fill(out.flags, out.flags + ni, 0);
-    if (out.stats)
+    if (out.stats)                                        // what an image that never reaches the assembly reports
         for (size_t k = 0; k < ni; ++k) { out.stats[4 * k] = out.stats[4 * k + 1] = 0; out.stats[4 * k + 2] = out.stats[4 * k + 3] = -1; }
-    const ChainShape sh = chain_shape((size_t)width, (size_t)height, dtype == CCAL_PIX_U16 ? 2 : 1, (size_t)o->step, (size_t)o->nms_radius,
-                                      (size_t)o->cand_cap, 1, 1, 1);
+    const ChainShape sh = chain_shape((size_t)b.width, (size_t)b.height, b.dtype == CCAL_PIX_U16 ? 2 : 1, (size_t)o->step,
+                                      (size_t)o->nms_radius, (size_t)o->cand_cap, 1, 1, 1);
     if (!sh.slots) return CCAL_OK;                        // no domain: nothing to launch
-    const size_t C = sh.cand, dh = (size_t)sh.dom.dh, K = std::min(C, (size_t)kBoardMaxKept);
-    const size_t per_image = (b.on_device ? 0 : sh.img_bytes) + sh.slots * kChainPerSlotBytes + dh * 4 + C * (28 + kBoardPerRowBytes) +
-                             K * kBoardPerKeptBytes + nw * 16 + kBoardPerImageBytes;
-    const size_t nc = chain_images_per_chunk(ni, per_image, test_chunk_bytes("CCAL_TEST_BOARD_CHUNK_BYTES", kBoardChunkBytes));
+    const size_t C = sh.cand, K = std::min(C, (size_t)kBoardMaxKept);
+    const size_t nc = chain_images_per_chunk(ni, board_chain_per_image_bytes(b.on_device, sh, nw),
+                                             test_chunk_bytes("CCAL_TEST_BOARD_CHUNK_BYTES", kChainChunkBytes));
 
     CallBlock blk(ctx);
-    const auto s_img = blk.add<char>(b.staged_bytes(nc));
-    const auto s_pix = blk.add<int32_t>(sh.slots * nc);
-    const auto s_rmax = blk.add<long long>(nc);
-    const auto s_hess = blk.add<int32_t>(3 * sh.slots * nc);
-    const auto s_resp = blk.add<int64_t>(sh.slots * nc);
-    const auto s_rowoff = blk.add<int32_t>(dh * nc);
-    const auto s_count = blk.add<int32_t>(nc);
-    const auto s_candoff = blk.add<int64_t>(nc + 1);
-    const auto s_oxy = blk.add<int32_t>(2 * C * nc);
-    const auto s_ohess = blk.add<int32_t>(3 * C * nc);
-    const auto s_oresp = blk.add<int64_t>(C * nc);
-    const auto s_status = blk.add<int32_t>(C * nc);
-    const auto s_iters = blk.add<int32_t>(C * nc);
-    const auto s_kidx = blk.add<int32_t>(C * nc);
-    const auto s_orig = blk.add<int32_t>(K * nc);
-    const auto s_link = blk.add<int32_t>(4 * K * nc);
-    const auto s_seed = blk.add<int32_t>(K * nc);
-    const auto s_hit = blk.add<uint8_t>(4 * K * nc);
-    const auto s_kept = blk.add<int32_t>(nc);
-    const auto s_found = blk.add<int32_t>(nc);
-    const auto s_flags = blk.add<int32_t>(nc);
-    const auto s_stats = blk.add<int32_t>(4 * nc);
-    const auto s_xy = blk.add<double>(2 * C * nc);        // the doubles the kernels write before they read, from here on
-    const auto s_lam = blk.add<double>(C * nc);
-    const auto s_bresp = blk.add<double>(C * nc);
-    const auto s_P = blk.add<double>(2 * K * nc);
-    const auto s_M = blk.add<double>(3 * K * nc);
-    const auto s_R = blk.add<double>(K * nc);
-    const auto s_D = blk.add<double>(4 * K * nc);
-    const auto s_bxy = blk.add<double>(2 * nw * nc);
+    ChainFront front; BoardSlices bs;
+    front.add_ints(blk, b, sh.dom, C, nc);
+    bs.add_ints(blk, C * nc, K, nc, nw, false);
+    front.add_doubles(blk);                               // the doubles the kernels write before they read, from here on
+    bs.add_doubles(blk);
     if (!blk.alloc()) return blk.finish(where);
 
-    DetectArgs da = {};
-    da.W = width; da.H = height; da.s = o->step; da.r = o->nms_radius; da.rel_q10 = o->rel_q10; da.cap = o->cand_cap;
-    da.min_response = o->min_response;
-    da.d0 = sh.dom.d0; da.dw = sh.dom.dw; da.dh = sh.dom.dh; da.nbx = sh.dom.nbx; da.nby = sh.dom.nby;
-    da.pix = blk.at(s_pix); da.hess = blk.at(s_hess); da.resp = blk.at(s_resp); da.rmax = blk.at(s_rmax);
-    da.rowoff = blk.at(s_rowoff); da.count = blk.at(s_count); da.imgoff = blk.at(s_candoff);
-    da.oxy = blk.at(s_oxy); da.ohess = blk.at(s_ohess); da.oresp = blk.at(s_oresp);
-    CornerArgs ca = {};
-    ca.off = blk.at(s_candoff); ca.xy = blk.at(s_xy); ca.status = blk.at(s_status); ca.iters = blk.at(s_iters); ca.lam = blk.at(s_lam);
-    ca.W = width; ca.H = height; ca.h = o->half_win; ca.max_it = o->max_iterations; ca.eps = o->eps;
-    BoardArgs a = {};
-    a.off = blk.at(s_candoff); a.xy = blk.at(s_xy); a.hess_i = blk.at(s_ohess); a.status = blk.at(s_status);
-    a.resp = blk.at(s_bresp); a.kidx = blk.at(s_kidx);
-    a.P = blk.at(s_P); a.M = blk.at(s_M); a.R = blk.at(s_R); a.D = blk.at(s_D); a.orig = blk.at(s_orig); a.link = blk.at(s_link);
-    a.seed = blk.at(s_seed); a.hit = blk.at(s_hit); a.kept = blk.at(s_kept); a.found = blk.at(s_found); a.flags = blk.at(s_flags);
-    a.stats = blk.at(s_stats); a.oxy = blk.at(s_bxy); a.oidx = nullptr;
-    a.cols = o->cols; a.rows = o->rows; a.row_cap = (int32_t)C; a.K = (int32_t)K;
-
+    front.bind(blk, b, sh.dom, fp);
+    BoardArgs a = bs.args(blk, o->cols, o->rows);
+    a.off = front.ca.off; a.xy = front.ca.xy; a.hess_i = front.da.ohess; a.status = front.ca.status; a.row_cap = (int32_t)C;
     hipStream_t st = ctx->stream;
-    std::vector<int32_t> h_count(nc), h_kept(nc), h_found(nc), h_flags(nc), h_stats(4 * nc);
-    std::vector<double> h_xy(2 * nw * nc);
+    std::vector<int32_t> h_count(nc);
     for (size_t k0 = 0; k0 < ni && blk.ok(); k0 += nc) {
         const size_t m = std::min(nc, ni - k0);
-        da.n = ca.n_img = a.n_img = (int32_t)m;
-        blk.poison(s_xy, s_bxy);                          // the test hook's NaN over the doubles the kernels write before they read
-        da.img = ca.img = b.chunk(blk, s_img, k0, m);
-
-        // 1. candidates, their offsets and stored rows; the host learns the counts
-        if (blk.ok()) blk.note(detect_enqueue_find(st, dtype, da));
-        if (blk.ok()) blk.note(tagchain_enqueue_offsets(st, da.count, C, m, blk.at(s_candoff)));
-        if (blk.ok()) blk.note(detect_enqueue_emit(st, da));
-        blk.download(h_count.data(), da.count, m);
-        if (blk.ok()) blk.note(hipStreamSynchronize(st));
+        a.n_img = (int32_t)m;
+        blk.poison(front.xy, bs.oxy);                     // the test hook's NaN over the doubles the kernels write before they read
+        // 1. - 3. candidates and their counts, starts, refinement; 4. - 5. the CCAL_OK corners with their Hessians into the assembly
+        const size_t n_cand = front.run(blk, st, b, k0, m, h_count);
         if (!blk.ok()) break;
-        size_t n_cand = 0;
-        for (size_t i = 0; i < m; ++i) n_cand += std::min((size_t)std::max(h_count[i], 0), C);
         for (size_t i = 0; i < m; ++i) out.flags[k0 + i] = h_count[i] > o->cand_cap ? CCAL_BOARD_FLAG_CAND_CAP : 0;
         if (!n_cand) continue;
-
-        // 2. - 5. starts, refinement, the CCAL_OK corners with their Hessians into the assembly; the boards come back
-        ca.n = (int64_t)n_cand;
-        blk.note(tagchain_enqueue_starts(st, da.oxy, ca.xy, (int64_t)(2 * n_cand)));
-        if (blk.ok()) blk.note(corners_enqueue(st, dtype, ca));
-        if (!blk.ok()) break;
-        board_run(blk, st, a, h_kept);
-        blk.download(h_found.data(), a.found, m);
-        blk.download(h_flags.data(), a.flags, m);
-        blk.download(h_stats.data(), a.stats, 4 * m);
-        blk.download(h_xy.data(), a.oxy, 2 * nw * m);
-        if (blk.ok()) blk.note(hipStreamSynchronize(st));
-        if (!blk.ok()) break;
-        for (size_t i = 0; i < m; ++i) {
-            const size_t k = k0 + i;
-            out.found[k] = h_found[i]; out.flags[k] |= h_flags[i];
-            if (out.stats) std::memcpy(out.stats + 4 * k, h_stats.data() + 4 * i, 4 * sizeof(int32_t));
-            if (h_found[i]) std::memcpy(out.xy + 2 * nw * k, h_xy.data() + 2 * nw * i, 2 * nw * sizeof(double));
-        }
+        board_run(blk, st, a, bs.h_kept);
+        if (!board_fetch(blk, st, a, bs, k0, out)) break;
+        for (size_t i = 0; i < m; ++i) out.flags[k0 + i] |= bs.h_flags[i];          // the assembly's flags beside the chain's own
     }
     return blk.finish(where);
 }
@@ -721,8 +662,8 @@ int ccal_assemble_checkerboards_batch(ccal_ctx* ctx, int n_img, const int64_t* o
                                       int32_t* stats_out) {
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    return assemble_call(ctx, "ccal_assemble_checkerboards_batch", n_img, offsets, xy, hess, cols, rows, found_out, xy_out, idx_out,
-                         flags_out, stats_out);
+    return assemble_call(ctx, "ccal_assemble_checkerboards_batch", n_img, offsets, xy, hess, cols, rows,
+                         BoardsOut{ found_out, xy_out, idx_out, flags_out, stats_out });
     CCAL_API_CATCH(ctx)
 }
 
@@ -732,7 +673,7 @@ int ccal_detect_checkerboards_batch(ccal_ctx* ctx, int dtype, int width, int hei
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
     return detect_boards_call(ctx, "ccal_detect_checkerboards_batch", GreyBatch{ dtype, width, height, n_img, images, false }, opts,
-                              BoardsOut{ found_out, xy_out, flags_out, stats_out });
+                              BoardsOut{ found_out, xy_out, nullptr, flags_out, stats_out });
     CCAL_API_CATCH(ctx)
 }
 
@@ -742,7 +683,7 @@ int ccal_detect_checkerboards_dev(ccal_ctx* ctx, int dtype, int width, int heigh
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
     return detect_boards_call(ctx, "ccal_detect_checkerboards_dev", GreyBatch{ dtype, width, height, n_img, images_dev, true }, opts,
-                              BoardsOut{ found_out, xy_out, flags_out, stats_out });
+                              BoardsOut{ found_out, xy_out, nullptr, flags_out, stats_out });
     CCAL_API_CATCH(ctx)
 }
 

@@ -111,8 +111,7 @@ namespace {
 
 int corners_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, const int64_t* offsets, double* xy_io, int half_win, int max_iterations,
                  double eps, int32_t* status_out, int32_t* iters_out, double* lambda_min_out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    const BadArg bad{ ctx, where };
     if (const char* what = corners_bad_params(half_win, max_iterations, eps)) return bad(what);
     if (const char* what = b.bad()) return bad(what);
     const int n_img = b.n_img;

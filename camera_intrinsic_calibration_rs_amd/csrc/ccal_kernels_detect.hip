@@ -16,16 +16,14 @@
 #include <algorithm>
 #include <cstring>
 #include <vector>
-#include "ccal_call.hpp"
+#include "ccal_chain_front.hpp"
 #include "ccal_image_device.hpp"
-#include "ccal_image_plan.hpp"
 
 namespace ccal {
 
 constexpr int kDetTile = 32;                  // the tile's side in domain pixels
 constexpr int kDetThreads = 256;
 constexpr int kDetMaxStep = 4, kDetMaxRadius = 15;
-constexpr size_t kDetChunkBytes = (size_t)256 << 20;      // the workspace one block should hold: larger batches go in chunks
 constexpr int64_t kDetNone = INT64_MIN;       // R of a pixel outside the domain: it never competes
 
 // DetectArgs: ccal_internal.hpp
@@ -223,8 +221,7 @@ namespace {
 
 int detect_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int step, int nms_radius, int64_t min_response, int rel_q10, int cap,
                 int32_t* count_out, int32_t* xy_out, int32_t* hess_out, int64_t* response_out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    const BadArg bad{ ctx, where };
     if (const char* what = detect_bad_params(step, nms_radius, min_response, rel_q10, cap)) return bad(what);
     if (const char* what = b.bad()) return bad(what);
     const int n_img = b.n_img;
@@ -238,30 +235,15 @@ int detect_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int step, 
     }
     const size_t nb = dm.slots(), dh = (size_t)dm.dh, rows_cap = std::min<size_t>((size_t)cap, nb);
     const size_t per_image = nb * 24 + dh * 4 + rows_cap * 24 + b.staged_bytes(1) + 64;
-    const size_t limit = test_chunk_bytes("CCAL_TEST_DETECT_CHUNK_BYTES", kDetChunkBytes);
-    const size_t nc = std::min<size_t>(std::min<size_t>((size_t)n_img, 65535), std::max<size_t>(limit / per_image, 1));
+    const size_t nc = chain_images_per_chunk((size_t)n_img, per_image, test_chunk_bytes("CCAL_TEST_DETECT_CHUNK_BYTES", kChainChunkBytes));
 
     // one block for the largest chunk: images (host call) | slots | rows, counts, offsets | the stored rows
     CallBlock blk(ctx);
-    const auto s_img = blk.add<char>(b.staged_bytes(nc));
-    const auto s_pix = blk.add<int32_t>(nb * nc);
-    const auto s_rmax = blk.add<long long>(nc);
-    const auto s_hess = blk.add<int32_t>(3 * nb * nc);
-    const auto s_resp = blk.add<int64_t>(nb * nc);
-    const auto s_rowoff = blk.add<int32_t>(dh * nc);
-    const auto s_count = blk.add<int32_t>(nc);
-    const auto s_imgoff = blk.add<int64_t>(nc + 1);
-    const auto s_oxy = blk.add<int32_t>(2 * rows_cap * nc);
-    const auto s_ohess = blk.add<int32_t>(3 * rows_cap * nc);
-    const auto s_oresp = blk.add<int64_t>(rows_cap * nc);
+    DetectSlices sl;
+    sl.add(blk, b, dm, rows_cap, nc);
     if (!blk.alloc()) return blk.finish(where);
 
-    DetectArgs a = {};
-    a.W = b.width; a.H = b.height; a.s = step; a.r = nms_radius; a.rel_q10 = rel_q10; a.cap = cap; a.min_response = min_response;
-    a.d0 = dm.d0; a.dw = dm.dw; a.dh = dm.dh; a.nbx = dm.nbx; a.nby = dm.nby;
-    a.pix = blk.at(s_pix); a.hess = blk.at(s_hess); a.resp = blk.at(s_resp); a.rmax = blk.at(s_rmax);
-    a.rowoff = blk.at(s_rowoff); a.count = blk.at(s_count); a.imgoff = blk.at(s_imgoff);
-    a.oxy = blk.at(s_oxy); a.ohess = blk.at(s_ohess); a.oresp = blk.at(s_oresp);
+    DetectArgs a = sl.args(blk, b, dm, step, nms_radius, min_response, rel_q10, cap);
     std::vector<int64_t> imgoff(nc + 1);
     std::vector<int32_t> h_xy, h_hess;
     std::vector<int64_t> h_resp;
@@ -269,9 +251,9 @@ int detect_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int step, 
     for (size_t k0 = 0; k0 < (size_t)n_img && blk.ok(); k0 += nc) {
         const size_t m = std::min(nc, (size_t)n_img - k0);
         a.n = (int32_t)m;
-        blk.poison(s_hess, s_resp);                    // the test hook's 0xFF over what the kernels write before they read it:
-        blk.poison(s_oxy, s_oresp);                    // the slots' payload and the stored rows (not the indices, counts and offsets)
-        a.img = b.chunk(blk, s_img, k0, m);
+        blk.poison(sl.hess, sl.resp);                  // the test hook's 0xFF over what the kernels write before they read it:
+        blk.poison(sl.oxy, sl.oresp);                  // the slots' payload and the stored rows (not the indices, counts and offsets)
+        a.img = b.chunk(blk, sl.img, k0, m);
         if (blk.ok()) blk.note(detect_enqueue_find(ctx->stream, b.dtype, a));
         blk.download(count_out + k0, a.count, m);
         if (blk.ok()) blk.note(hipStreamSynchronize(ctx->stream));
@@ -280,7 +262,7 @@ int detect_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int step, 
         for (size_t i = 0; i < m; ++i) imgoff[i + 1] = imgoff[i] + std::min<int64_t>(count_out[k0 + i], (int64_t)rows_cap);
         const size_t total = (size_t)imgoff[m];
         if (!total) continue;
-        blk.upload(s_imgoff, imgoff.data(), m + 1);
+        blk.upload(sl.imgoff, imgoff.data(), m + 1);
         if (blk.ok()) blk.note(detect_enqueue_emit(ctx->stream, a));
         h_xy.resize(2 * total); h_hess.resize(3 * total);
         if (response_out) h_resp.resize(total);

@@ -186,8 +186,7 @@ namespace {
 int quads_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, const int64_t* offsets, const double* xy, double min_side, double max_side,
                double max_side_ratio, double offset, int samples, double min_contrast, int cap, int32_t* count_out, int32_t* flags_out,
                int32_t* idx_out, double* quads_out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    const BadArg bad{ ctx, where };
     if (const char* what = quads_bad_params(min_side, max_side, max_side_ratio, offset, samples, min_contrast, cap)) return bad(what);
     if (const char* what = b.bad()) return bad(what);
     const int n_img = b.n_img;

@@ -1,6 +1,6 @@
 // From images to named tags in one call (ccal_detect_tags_batch / _dev): the four stages - detector, refinement, proposer, decoder -
 // chained on the device by the rule stated at the entry points in include/ccal.h.  The stages' kernels are the ones their own entry
-// points launch (detect_enqueue_*, corners_enqueue, quads_enqueue_*, tags_enqueue: ccal_internal.hpp); this unit holds the links:
+// points launch (ccal_internal.hpp), detector and refinement through the front shared with the board chain (ccal_chain_front.hpp); the links:
 //   k_chain_starts     the detector's stored int32 rows to the refinement's f64 starts, same compact layout
 //   k_chain_merge      one wavefront per image: the corners with status CCAL_OK, in candidate order, each rounded through f32 and tested
 //                      against the points kept so far - the lanes stride the kept list, one __any decides.  The greedy order is
@@ -19,19 +19,12 @@
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include "ccal_call.hpp"
+#include "ccal_chain_front.hpp"
 #include "ccal_image_device.hpp"
-#include "ccal_tagchain_plan.hpp"
 
 namespace ccal {
 
 constexpr int kMergeLds = 2048;               // kept points held in LDS: 16 KB
-constexpr size_t kChainChunkBytes = (size_t)256 << 20;    // the block one chunk should need: larger batches go image chunk by chunk
-
-__device__ __forceinline__ int chain_span(const int64_t* off, int k, int cap) {
-    const int64_t m = off[k + 1] - off[k];
-    return (int)(m < 0 ? 0 : (m > (int64_t)cap ? (int64_t)cap : m));
-}
 
 __global__ __launch_bounds__(256) void k_chain_starts(const int32_t* __restrict__ in, double* __restrict__ out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -55,7 +48,7 @@ __global__ __launch_bounds__(64) void k_chain_merge(const MergeArgs a) {
     __shared__ float kx[kMergeLds], ky[kMergeLds];
     const int k = blockIdx.x, lane = threadIdx.x;
     const int64_t first = a.off[k];
-    const int m = chain_span(a.off, k, a.cap);
+    const int m = csr_span(a.off, k, a.cap);
     double* out = a.out + 2 * first;
     int nk = 0;
     for (int b0 = 0; b0 < m; b0 += 64) {
@@ -94,7 +87,7 @@ __global__ __launch_bounds__(64) void k_chain_merge(const MergeArgs a) {
 __global__ __launch_bounds__(256) void k_chain_compact(const int64_t* __restrict__ src_off, const int64_t* __restrict__ dst_off,
                                                        const double* __restrict__ src, double* __restrict__ dst, int32_t cap) {
     const int k = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= chain_span(dst_off, k, cap)) return;
+    if (j >= csr_span(dst_off, k, cap)) return;
     const int64_t s = src_off[k] + j, d = dst_off[k] + j;
     dst[2 * d] = src[2 * s]; dst[2 * d + 1] = src[2 * s + 1];
 }
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(64) void k_chain_quad_scan(const int64_t* __restric
                                                         int32_t* __restrict__ qcount, int32_t* __restrict__ qflags, int32_t cap) {
     const int k = blockIdx.x, lane = threadIdx.x;
     const int64_t first = off[k];
-    const int m = chain_span(off, k, cap);
+    const int m = csr_span(off, k, cap);
     int32_t carry = 0;                                   // at most 32768 * 8^3 = 2^24
     bool cut = false;
     for (int b0 = 0; b0 < m; b0 += 64) {
@@ -122,7 +115,7 @@ __global__ __launch_bounds__(64) void k_chain_quad_scan(const int64_t* __restric
 __global__ __launch_bounds__(64) void k_chain_select(const SelectArgs a) {
     const int k = blockIdx.x, lane = threadIdx.x;
     const int64_t first = a.off[k];
-    const int q = chain_span(a.off, k, a.cap);
+    const int q = csr_span(a.off, k, a.cap);
     const int32_t* reason = a.reason + first; const int32_t* id = a.id + first; const int32_t* ham = a.hamming + first;
     const double* margin = a.margin + first;
     int32_t* win = a.win + first;
@@ -190,12 +183,11 @@ struct ChainOut {
 
 int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, const uint64_t* codes, int n_codes,
                   const ccal_detect_tags_opts* o, const ChainOut& out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    const BadArg bad{ ctx, where };
+    char buf[40];
     if (!o) return bad("NULL options");
-    if (const char* what = detect_bad_params(o->step, o->nms_radius, o->min_response, o->rel_q10, o->cand_cap)) return bad(what);
-    if (o->cand_cap > (int32_t)kQuadMaxPoints) return bad("cand_cap outside 1 .. 32768");
-    if (const char* what = corners_bad_params(o->half_win, o->max_iterations, o->eps)) return bad(what);
+    const FrontParams fp = FrontParams::of(*o);
+    if (const char* what = front_bad_params(fp, (int32_t)kQuadMaxPoints, buf)) return bad(what);
     if (!(o->merge_radius >= 0.0) || !std::isfinite(o->merge_radius)) return bad("merge_radius negative or not finite");
     if (const char* what = quads_bad_params(o->min_side, o->max_side, o->max_side_ratio, o->offset, o->edge_samples, o->edge_min_contrast,
                                             o->quad_cap)) return bad(what);
@@ -215,26 +207,15 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
     const ChainShape sh = chain_shape((size_t)width, (size_t)height, dtype == CCAL_PIX_U16 ? 2 : 1, (size_t)o->step, (size_t)o->nms_radius,
                                       (size_t)o->cand_cap, (size_t)o->quad_cap, tag_cap, (size_t)n_codes);
     if (!sh.slots) return CCAL_OK;                        // no domain: nothing to launch
-    const size_t C = sh.cand, Q = sh.quads, T = sh.tags, dh = (size_t)sh.dom.dh;
+    const size_t C = sh.cand, Q = sh.quads, T = sh.tags;
     const size_t nc = chain_images_per_chunk(ni, chain_per_image_bytes(b.on_device, sh),
                                              test_chunk_bytes("CCAL_TEST_TAGCHAIN_CHUNK_BYTES", kChainChunkBytes));
 
     // one block for the largest chunk.  The doubles the kernels write before they read lie together: one poison covers them.
     CallBlock blk(ctx);
     const auto s_codes = blk.add<unsigned long long>((size_t)n_codes);
-    const auto s_img = blk.add<char>(b.staged_bytes(nc));
-    const auto s_pix = blk.add<int32_t>(sh.slots * nc);
-    const auto s_rmax = blk.add<long long>(nc);
-    const auto s_hess = blk.add<int32_t>(3 * sh.slots * nc);
-    const auto s_resp = blk.add<int64_t>(sh.slots * nc);
-    const auto s_rowoff = blk.add<int32_t>(dh * nc);
-    const auto s_count = blk.add<int32_t>(nc);
-    const auto s_candoff = blk.add<int64_t>(nc + 1);
-    const auto s_oxy = blk.add<int32_t>(2 * C * nc);
-    const auto s_ohess = blk.add<int32_t>(3 * C * nc);
-    const auto s_oresp = blk.add<int64_t>(C * nc);
-    const auto s_status = blk.add<int32_t>(C * nc);
-    const auto s_iters = blk.add<int32_t>(C * nc);
+    ChainFront front;
+    front.add_ints(blk, b, sh.dom, C, nc);
     const auto s_kept = blk.add<int32_t>(nc);
     const auto s_ptoff = blk.add<int64_t>(nc + 1);
     const auto s_adj = blk.add<int32_t>(CCAL_QUAD_MAX_OUT_EDGES * C * nc);
@@ -256,8 +237,7 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
     const auto s_tid = blk.add<int32_t>(T * nc);
     const auto s_trot = blk.add<int32_t>(T * nc);
     const auto s_tham = blk.add<int32_t>(T * nc);
-    const auto s_xy = blk.add<double>(2 * C * nc);        // the doubles, from here on
-    const auto s_lam = blk.add<double>(C * nc);
+    front.add_doubles(blk);                               // the doubles, from here on
     const auto s_mxy = blk.add<double>(2 * C * nc);
     const auto s_pxy = blk.add<double>(2 * C * nc);
     const auto s_oquads = blk.add<double>(8 * Q * nc);
@@ -267,18 +247,9 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
     const auto s_tmargin = blk.add<double>(T * nc);
     if (!blk.alloc()) return blk.finish(where);
 
-    DetectArgs da = {};
-    da.W = width; da.H = height; da.s = o->step; da.r = o->nms_radius; da.rel_q10 = o->rel_q10; da.cap = o->cand_cap;
-    da.min_response = o->min_response;
-    da.d0 = sh.dom.d0; da.dw = sh.dom.dw; da.dh = sh.dom.dh; da.nbx = sh.dom.nbx; da.nby = sh.dom.nby;
-    da.pix = blk.at(s_pix); da.hess = blk.at(s_hess); da.resp = blk.at(s_resp); da.rmax = blk.at(s_rmax);
-    da.rowoff = blk.at(s_rowoff); da.count = blk.at(s_count); da.imgoff = blk.at(s_candoff);
-    da.oxy = blk.at(s_oxy); da.ohess = blk.at(s_ohess); da.oresp = blk.at(s_oresp);
-    CornerArgs ca = {};
-    ca.off = blk.at(s_candoff); ca.xy = blk.at(s_xy); ca.status = blk.at(s_status); ca.iters = blk.at(s_iters); ca.lam = blk.at(s_lam);
-    ca.W = width; ca.H = height; ca.h = o->half_win; ca.max_it = o->max_iterations; ca.eps = o->eps;
+    front.bind(blk, b, sh.dom, fp);
     MergeArgs ma = {};
-    ma.off = blk.at(s_candoff); ma.xy = blk.at(s_xy); ma.status = blk.at(s_status); ma.out = blk.at(s_mxy); ma.kept = blk.at(s_kept);
+    ma.off = front.ca.off; ma.xy = front.ca.xy; ma.status = front.ca.status; ma.out = blk.at(s_mxy); ma.kept = blk.at(s_kept);
     ma.cap = (int32_t)C; ma.radius = o->merge_radius;
     QuadArgs qa = {};
     qa.off = blk.at(s_ptoff); qa.xy = blk.at(s_pxy); qa.adj = blk.at(s_adj); qa.deg = blk.at(s_deg); qa.cnt = blk.at(s_cnt);
@@ -301,35 +272,21 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
     hipStream_t st = ctx->stream;
     std::vector<int32_t> h_count(nc), h_kept(nc), h_qcount(nc), h_qflags(nc), h_ntags(nc), h_nok(nc), h_id(T * nc), h_rot(T * nc), h_ham(T * nc);
     std::vector<double> h_corners(8 * T * nc), h_margin(out.margin ? T * nc : 0);
-    auto total_of = [](const std::vector<int32_t>& v, size_t m, size_t cap) {
-        size_t t = 0;
-        for (size_t i = 0; i < m; ++i) t += std::min((size_t)std::max(v[i], 0), cap);
-        return t;
-    };
 
     for (size_t k0 = 0; k0 < ni && blk.ok(); k0 += nc) {
         const size_t m = std::min(nc, ni - k0);
-        da.n = ca.n_img = ma.n_img = qa.n_img = ta.n_img = sa.n_img = (int32_t)m;
-        blk.poison(s_xy, s_tmargin);                      // the test hook's NaN over the doubles the kernels write before they read
-        da.img = ca.img = qa.img = ta.img = b.chunk(blk, s_img, k0, m);
-        std::fill(h_kept.begin(), h_kept.end(), 0); std::fill(h_qcount.begin(), h_qcount.end(), 0);
-        std::fill(h_qflags.begin(), h_qflags.end(), 0); std::fill(h_ntags.begin(), h_ntags.end(), 0); std::fill(h_nok.begin(), h_nok.end(), 0);
+        ma.n_img = qa.n_img = ta.n_img = sa.n_img = (int32_t)m;
+        blk.poison(front.xy, s_tmargin);                  // the test hook's NaN over the doubles the kernels write before they read
+        for (auto* v : { &h_kept, &h_qcount, &h_qflags, &h_ntags, &h_nok }) std::fill(v->begin(), v->end(), 0);     // a stage that does not run leaves zeros
 
-        // 1. candidates, their offsets and stored rows; the host learns the counts
-        if (blk.ok()) blk.note(detect_enqueue_find(st, dtype, da));
-        if (blk.ok()) blk.note(tagchain_enqueue_offsets(st, da.count, C, m, blk.at(s_candoff)));
-        if (blk.ok()) blk.note(detect_enqueue_emit(st, da));
-        blk.download(h_count.data(), da.count, m);
-        if (blk.ok()) blk.note(hipStreamSynchronize(st));
+        // 1. - 3. candidates, their offsets and stored rows; the host learns the counts; starts and refinement
+        const size_t n_cand = front.run(blk, st, b, k0, m, h_count);
         if (!blk.ok()) break;
-        const size_t n_cand = total_of(h_count, m, C);
+        qa.img = ta.img = front.da.img;
 
-        // 2. - 5. starts, refinement, rounding and merge, the points' compact layout; the host learns the kept counts
+        // 4. - 5. rounding and merge, the points' compact layout; the host learns the kept counts
         if (n_cand) {
-            ca.n = (int64_t)n_cand;
-            blk.note(tagchain_enqueue_starts(st, da.oxy, ca.xy, (int64_t)(2 * n_cand)));
-            if (blk.ok()) blk.note(corners_enqueue(st, dtype, ca));
-            if (blk.ok()) blk.note(tagchain_enqueue_merge(st, ma));
+            blk.note(tagchain_enqueue_merge(st, ma));
             if (blk.ok()) blk.note(tagchain_enqueue_offsets(st, ma.kept, C, m, blk.at(s_ptoff)));
             if (blk.ok()) {
                 hipLaunchKernelGGL(k_chain_compact, dim3((unsigned)((C + 255) / 256), (unsigned)m), dim3(256), 0, st, ma.off, blk.at(s_ptoff),
@@ -340,7 +297,7 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
             if (blk.ok()) blk.note(hipStreamSynchronize(st));
             if (!blk.ok()) break;
         }
-        const size_t n_pts = total_of(h_kept, m, C);
+        const size_t n_pts = clamped_total(h_kept, m, C);
 
         // 6. edges and the count walk, the two scans; the host learns the quad counts and cut bits
         if (n_pts) {
@@ -357,7 +314,7 @@ int tagchain_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, int d, c
             if (blk.ok()) blk.note(hipStreamSynchronize(st));
             if (!blk.ok()) break;
         }
-        const size_t n_quads = total_of(h_qcount, m, Q);
+        const size_t n_quads = clamped_total(h_qcount, m, Q);
 
         // 6. - 8. the stored quads, the decoder, the selection; the tags come back
         if (n_quads) {

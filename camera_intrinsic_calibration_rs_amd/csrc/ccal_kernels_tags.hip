@@ -217,8 +217,7 @@ namespace {
 int tags_call(ccal_ctx* ctx, const char* where, const GreyBatch& b, const int64_t* offsets, const double* quads, int d, int border,
               const uint64_t* codes, int n_codes, int samples, double min_contrast, int max_border_errors, int max_hamming,
               int32_t* reason_out, int32_t* id_out, int32_t* rot_out, int32_t* hamming_out, double* corners_out, uint64_t* code_out, double* margin_out) {
-    char msg[160];
-    auto bad = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", where, what); return fail(ctx, CCAL_ERR_INVALID_ARG, msg); };
+    const BadArg bad{ ctx, where };
     if (const char* what = tags_bad_params(d, border, n_codes, samples, min_contrast, max_border_errors, max_hamming)) return bad(what);
     if (const char* what = b.bad()) return bad(what);
     if (const char* what = tags_bad_codes(d, codes, n_codes)) return bad(what);

@@ -1,12 +1,13 @@
-// How ccal_detect_tags_* sizes its device block and cuts a batch into chunks of whole images: plain arithmetic, no context and no HIP
-// include, so that a plain C++ program can hold it to the groupings the tests rely on (tests/cpp/test_tagchain_plan.cpp,
-// tests/test_detect_tags_cpu.py).  The counts of an image are not known before its stages have run, so the bound per image comes from
-// the caps alone, each cut to what the image's size allows; every image of a call has the same bound, and a chunk is a fixed number
-// of images.
+// How ccal_detect_tags_* and ccal_detect_checkerboards_* size their device blocks and cut a batch into chunks of whole images: plain
+// arithmetic, no context and no HIP include, so that a plain C++ program can hold it to the groupings the tests rely on
+// (tests/cpp/test_tagchain_plan.cpp, tests/test_detect_tags_cpu.py).  The counts of an image are not known before its stages have
+// run, so the bound per image comes from the caps alone, each cut to what the image's size allows; every image of a call has the same
+// bound, and a chunk is a fixed number of images.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include "../../include/ccal.h"
 #include "ccal_image_plan.hpp"
 
 namespace ccal {
@@ -19,8 +20,13 @@ namespace ccal {
 //   tag        id, rot, hamming 12 | corners 64 | margin 8
 //   image      the detector's Rmax 8 and count 4, three offsets 24, kept / quads / flags / tags / OK quads 20 - rounded up to 64
 constexpr size_t kChainPerSlotBytes = 24, kChainPerCandBytes = 136, kChainPerQuadBytes = 180, kChainPerTagBytes = 84, kChainPerImageBytes = 64;
-constexpr size_t kChainMaxImages = 65535;        // a grid's y and z extents
-constexpr size_t kChainQuadsPerPoint = 512;      // 8^3 chains start at a point
+// the board assembly's: per input row xy 16, Hessian 24 or 12, response 8, kept index 4, status 4 in the chain; per kept-row slot
+// position 16, M 24, response 8, directions 32, input row 4, links 16, seed 4, attempt bits 4.  In its chain a candidate is the
+// detector's stored row and an input row.
+constexpr size_t kBoardPerRowBytes = 56, kBoardPerKeptBytes = 108, kBoardPerImageBytes = 64, kBoardChainPerCandBytes = 28 + kBoardPerRowBytes;
+constexpr int kBoardMaxKept = CCAL_BOARD_MAX_KEPT;
+constexpr size_t kChainChunkBytes = (size_t)256 << 20;    // the block one chunk should need, in either chain and in the assembly's own call
+constexpr size_t kChainMaxImages = 65535, kChainQuadsPerPoint = 512;      // a grid's y and z extents; 8^3 chains start at a point
 
 struct ChainShape {
     size_t img_bytes = 0;          // one image
@@ -42,9 +48,20 @@ inline ChainShape chain_shape(size_t width, size_t height, size_t itemsize, size
     return s;
 }
 
+// what both chains begin with (ccal_chain_front.hpp): the image when staged, the detector's slots and row offsets, the candidate rows
+inline size_t front_per_image_bytes(bool images_on_device, const ChainShape& s, size_t per_cand) {
+    return (images_on_device ? 0 : s.img_bytes) + s.slots * kChainPerSlotBytes + (size_t)s.dom.dh * 4 + s.cand * per_cand;
+}
+
 inline size_t chain_per_image_bytes(bool images_on_device, const ChainShape& s) {
-    return (images_on_device ? 0 : s.img_bytes) + s.slots * kChainPerSlotBytes + (size_t)s.dom.dh * 4 + s.cand * kChainPerCandBytes +
-           s.quads * kChainPerQuadBytes + s.tags * kChainPerTagBytes + kChainPerImageBytes;
+    return front_per_image_bytes(images_on_device, s, kChainPerCandBytes) + s.quads * kChainPerQuadBytes + s.tags * kChainPerTagBytes +
+           kChainPerImageBytes;
+}
+
+// ccal_detect_checkerboards_*: s from chain_shape with quad_cap = tag_cap = n_codes = 1; corners = cols * rows of the board
+inline size_t board_chain_per_image_bytes(bool images_on_device, const ChainShape& s, size_t corners) {
+    return front_per_image_bytes(images_on_device, s, kBoardChainPerCandBytes) + std::min(s.cand, (size_t)kBoardMaxKept) * kBoardPerKeptBytes +
+           corners * 16 + kBoardPerImageBytes;
 }
 
 // images per chunk: as many as keep the chunk within `limit` bytes, at least one

@@ -327,8 +327,7 @@ class Context:
 
     # -- from pixels to detections: checkerboard-corner candidates of whole images (ccal_detect_corners_batch, ccal_kernels_detect.hip) --
     def _detect(self, fn, where, ptr, dtype, width, height, n_img, step, nms_radius, min_response, rel_threshold, max_per_image):
-        if not np.isfinite(rel_threshold):
-            raise ValueError(f"{where}: rel_threshold is not finite")
+        rel_q10 = _rel_q10(where, rel_threshold)
         cap, m = int(max_per_image), max(int(n_img), 1)
         # an image holds at most one candidate per (r + 1) x (r + 1) block of its domain: no room beyond that is needed
         r1, d = max(int(nms_radius), 0) + 1, 2 * (int(step) + 2)
@@ -340,7 +339,7 @@ class Context:
         xy = np.empty((m, rows, 2), dtype=np.int32); hess = np.empty((m, rows, 3), dtype=np.int32)
         resp = np.empty((m, rows), dtype=np.int64)
         rc = fn(self.handle, int(dtype), int(width), int(height), int(n_img), C.c_void_p(ptr), int(step), int(nms_radius),
-                int(min_response), int(round(1024.0 * float(rel_threshold))), cap, _ip(count), _ip(xy), _ip(hess), _lp(resp))
+                int(min_response), rel_q10, cap, _ip(count), _ip(xy), _ip(hess), _lp(resp))
         if rc != _ffi.OK:
             raise CcalError(rc, where, self.last_error())
         # one compact copy of the stored rows of all images; the per-image results are views of it
@@ -465,8 +464,7 @@ class Context:
                      max_candidates, half_win, max_iterations, eps, merge_radius, min_side, max_side, max_side_ratio, offset,
                      edge_samples, edge_min_contrast, max_quads, border, cell_samples, tag_min_contrast, max_border_errors, max_hamming,
                      max_tags):
-        if not np.isfinite(rel_threshold):
-            raise ValueError(f"{where}: rel_threshold is not finite")
+        front = _front_opts(where, step, nms_radius, min_response, rel_threshold, max_candidates, half_win, max_iterations, eps)
         d, codes = _family(where, family_bits, codes)
         if max_side is None:
             max_side = max(int(width), int(height)) / 2.0
@@ -475,9 +473,7 @@ class Context:
         if max_tags is None:
             max_tags = max(len(codes), 1)              # an image's tags have distinct ids
         o = _ffi.DetectTagsOpts(
-            step=int(step), nms_radius=int(nms_radius), min_response=int(min_response), rel_q10=int(round(1024.0 * float(rel_threshold))),
-            cand_cap=int(max_candidates), half_win=int(half_win), max_iterations=int(max_iterations), eps=float(eps),
-            merge_radius=float(merge_radius), min_side=float(min_side), max_side=float(max_side), max_side_ratio=float(max_side_ratio),
+            **front, merge_radius=float(merge_radius), min_side=float(min_side), max_side=float(max_side), max_side_ratio=float(max_side_ratio),
             offset=float(offset), edge_min_contrast=float(edge_min_contrast), edge_samples=int(edge_samples), quad_cap=int(max_quads),
             border=int(border), cell_samples=int(cell_samples), tag_min_contrast=float(tag_min_contrast),
             max_border_errors=int(max_border_errors), max_hamming=int(max_hamming), tag_cap=int(max_tags))
@@ -561,11 +557,8 @@ class Context:
 
     def _detect_boards(self, fn, where, ptr, dtype, width, height, n_img, cols, rows, step, nms_radius, min_response, rel_threshold,
                        max_candidates, half_win, max_iterations, eps):
-        if not np.isfinite(rel_threshold):
-            raise ValueError(f"{where}: rel_threshold is not finite")
         o = _ffi.DetectCheckerboardsOpts(
-            step=int(step), nms_radius=int(nms_radius), min_response=int(min_response), rel_q10=int(round(1024.0 * float(rel_threshold))),
-            cand_cap=int(max_candidates), half_win=int(half_win), max_iterations=int(max_iterations), eps=float(eps),
+            **_front_opts(where, step, nms_radius, min_response, rel_threshold, max_candidates, half_win, max_iterations, eps),
             cols=int(cols), rows=int(rows))
         m, nw = max(int(n_img), 1), max(int(cols) * int(rows), 1)
         found = np.zeros(m, dtype=np.int32); flags = np.zeros(m, dtype=np.int32); stats = np.zeros((m, 4), dtype=np.int32)
@@ -620,6 +613,19 @@ def _grey_batch(images, who: str):
         raise ValueError(f"{who}: single-channel images [n][H][W]")
     n_img, H, W = images.shape[:3]
     return images, (images.ctypes.data, dtype, W, H, n_img)
+
+
+def _rel_q10(where: str, rel_threshold) -> int:
+    """rel_threshold as the detector takes it: round(1024 rel_threshold); ValueError when it is not finite."""
+    if not np.isfinite(rel_threshold):
+        raise ValueError(f"{where}: rel_threshold is not finite")
+    return int(round(1024.0 * float(rel_threshold)))
+
+
+def _front_opts(where: str, step, nms_radius, min_response, rel_threshold, max_candidates, half_win, max_iterations, eps) -> dict:
+    """The detector's and the refinement's fields, with which the options of both image chains begin."""
+    return dict(step=int(step), nms_radius=int(nms_radius), min_response=int(min_response), rel_q10=_rel_q10(where, rel_threshold),
+                cand_cap=int(max_candidates), half_win=int(half_win), max_iterations=int(max_iterations), eps=float(eps))
 
 
 def _family(where: str, family_bits, codes):

@@ -125,6 +125,24 @@ def plan_model(on_device, width, height, itemsize, step, r, cand_cap, quad_cap, 
     return per, min(n_img, MAX_IMAGES, max(limit // per, 1))
 
 
+BOARD_PER_CAND, BOARD_PER_KEPT, BOARD_PER_CORNER, BOARD_MAX_KEPT = 28 + 56, 108, 16, 512
+
+
+def board_plan_model(on_device, width, height, itemsize, step, r, cand_cap, corners, limit, n_img):
+    """plan_model for ccal_detect_checkerboards_*: per candidate the detector's stored row and the assembly's input row, per kept slot
+    (at most 512 of the candidates) the assembly's work, 16 bytes per corner of the cols x rows = `corners` board."""
+    d0 = step + 2
+    if width <= 2 * d0 or height <= 2 * d0:
+        slots = dh = cand = 0
+    else:
+        dw, dh = width - 2 * d0, height - 2 * d0
+        slots = -(-dw // (r + 1)) * -(-dh // (r + 1))
+        cand = min(cand_cap, slots)
+    per = (0 if on_device else itemsize * width * height) + PER_SLOT * slots + 4 * dh + BOARD_PER_CAND * cand + \
+        BOARD_PER_KEPT * min(cand, BOARD_MAX_KEPT) + BOARD_PER_CORNER * corners + PER_IMAGE
+    return per, min(n_img, MAX_IMAGES, max(limit // per, 1))
+
+
 def chunk_limit(on_device, shape, itemsize, o, n_codes, images_per_chunk):
     """A byte limit at which the planner puts exactly `images_per_chunk` images of `shape` = (H, W) into a chunk."""
     per, _ = plan_model(on_device, shape[1], shape[0], itemsize, o["step"], o["nms_radius"], o["cand_cap"], o["quad_cap"], o["tag_cap"],

@@ -1,7 +1,7 @@
 """CPU: ccal_detect_tags_* without a device - the exported symbols, the binding's struct against the header, the links of the rule as
 tests/tagchain_ref.py restates them (merge, select, and chain() over the four stage yardsticks on the montage fixture), and the chunk
-planner (csrc/ccal_tagchain_plan.hpp) through a plain C++ program under the host's address and undefined-behaviour sanitizers.  No
-GPU, nothing outside the repository."""
+planner of both image chains (csrc/ccal_tagchain_plan.hpp) through a plain C++ program under the host's address and
+undefined-behaviour sanitizers.  No GPU, nothing outside the repository."""
 import ctypes
 import os
 import re
@@ -100,7 +100,7 @@ def test_the_chain_on_a_montage_keeps_one_quad_of_each_pair(nms_radius):
 
 # ---- the planner ----------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def planner(tmp_path_factory):
+def planner_lines(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("tagchain_plan") / "test_tagchain_plan")
     subprocess.check_call([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-Wall", "-Xarch_host", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "cpp", "test_tagchain_plan.cpp"), "-o", exe])
@@ -109,9 +109,26 @@ def planner(tmp_path_factory):
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
         out = subprocess.run([exe] + [str(int(a)) for a in args], env=env, capture_output=True, text=True, timeout=60)
         assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-        lines = out.stdout.split("\n")
+        return out.stdout.split("\n")
+    return run
+
+
+@pytest.fixture(scope="module")
+def planner(planner_lines):
+    def run(*args):
+        lines = planner_lines(*args)
         assert lines[0].startswith("ROWS ") and lines[1].startswith("PER-IMAGE ") and lines[2].startswith("CHUNK ")
         return int(lines[1].split()[1]), int(lines[2].split()[1])
+    return run
+
+
+@pytest.fixture(scope="module")
+def board_planner(planner_lines):
+    """(bytes per image, images per chunk) of ccal_detect_checkerboards_*; the tag chain's caps do not enter (the library passes 1)."""
+    def run(on_device, width, height, itemsize, step, r, cand_cap, corners, limit, n_img):
+        lines = planner_lines(on_device, width, height, itemsize, step, r, cand_cap, 1, 1, 1, limit, n_img, corners)
+        assert lines[3].startswith("BOARD-PER-IMAGE ") and lines[4].startswith("BOARD-CHUNK ")
+        return int(lines[3].split()[1]), int(lines[4].split()[1])
     return run
 
 
@@ -139,3 +156,30 @@ def test_the_limits_of_the_gpu_chunk_test_cut_its_batch_as_it_says(planner):
             args = (on_device, tag_ref.GRID_W, tag_ref.GRID_H, 1, o["step"], o["nms_radius"], o["cand_cap"], o["quad_cap"], o["tag_cap"], 40)
             assert planner(*args, limit, 4)[1] == per_chunk
         assert planner(*args, 256 << 20, 4)[1] == 4
+
+
+def test_the_board_chains_planner_follows_its_rule(board_planner):
+    rng = np.random.default_rng(20)
+    shapes = [(320, 240, 1, 1, 5, 4096, 35), (752, 480, 2, 2, 3, 7, 4), (6, 240, 1, 1, 5, 4096, 35)]           # the last: no domain
+    for _ in range(8):
+        shapes.append((int(rng.integers(7, 1500)), int(rng.integers(7, 1100)), int(rng.integers(1, 3)), int(rng.integers(1, 5)),
+                       int(rng.integers(1, 16)), int(rng.integers(1, 4097)), int(rng.integers(2, 21)) * int(rng.integers(2, 21))))
+    for width, height, itemsize, step, r, cand_cap, corners in shapes:
+        for on_device in (False, True):
+            for limit, n_img in ((0, 5), (1, 1), (10 ** 6, 1024), (256 << 20, 1024), (2 ** 40, 10 ** 5)):
+                args = (on_device, width, height, itemsize, step, r, cand_cap, corners, limit, n_img)
+                assert board_planner(*args) == ref.board_plan_model(*args), args
+
+
+def test_the_limits_of_the_board_chunk_test_cut_its_batch_as_it_says(board_planner):
+    """tests/test_gpu_board.py::test_a_batch_cut_into_chunks runs 320 x 240 u8 images at step 1, radius 5, cand_cap 4096 for a 7 x 5
+    board through ccal_detect_checkerboards_* with limits of 1 and 800 000 bytes.  The domain is 314 x 234: 53 x 39 = 2067 slots, as
+    many candidate rows, 512 kept slots.  Per image 2067 * 24 + 234 * 4 + 2067 * 84 + 512 * 108 + 35 * 16 + 64 = 280 092 bytes, and
+    76 800 more when the call stages the image: two images per chunk at 800 000 either way, one at a limit of 1."""
+    shape = (320, 240, 1, 1, 5, 4096, 35)
+    assert 2067 * 24 + 234 * 4 + 2067 * (28 + 56) + 512 * 108 + 35 * 16 + 64 == 280092
+    assert board_planner(True, *shape, 800000, 6) == (280092, 2)
+    assert board_planner(False, *shape, 800000, 6) == (356892, 2)
+    assert board_planner(True, *shape, 1, 6)[1] == 1 and board_planner(False, *shape, 1, 6)[1] == 1
+    assert board_planner(True, *shape, 3 * 280092, 6)[1] == 3 and board_planner(True, *shape, 3 * 280092 - 1, 6)[1] == 2       # inclusive
+    assert board_planner(False, *shape, 256 << 20, 6)[1] == 6                                  # the product's limit: one chunk
