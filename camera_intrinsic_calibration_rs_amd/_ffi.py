@@ -96,6 +96,23 @@ class DetectCheckerboardsOpts(C.Structure):          # ccal_detect_checkerboards
 BOARD_MIN_SIDE, BOARD_MAX_SIDE, BOARD_MAX_ROWS, BOARD_MAX_KEPT = 2, 20, 4096, 512
 BOARD_FLAG_CAND_CAP, BOARD_FLAG_KEPT_LIMIT = 1, 2
 
+TARGET_CHECKERBOARD, TARGET_APRILGRID = 0, 1    # ccal_target_kind
+
+
+class RenderTarget(C.Structure):          # ccal_render_target: one struct for both kinds of target
+    _fields_ = [
+        ("kind", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32), ("reserved_", C.c_int32), ("square", C.c_double),
+        ("tag_size", C.c_double), ("tag_spacing", C.c_double),
+        ("tag_rows", C.c_int32), ("tag_cols", C.c_int32), ("first_id", C.c_int32), ("family_bits", C.c_int32),
+        ("n_codes", C.c_int32), ("border", C.c_int32), ("codes", _up),
+    ]
+
+
+class RenderOpts(C.Structure):            # ccal_render_opts
+    _fields_ = [("supersample", C.c_int32), ("reserved_", C.c_int32), ("black", C.c_double), ("white", C.c_double),
+                ("background", C.c_double), ("margin", C.c_double)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 LIB_PATH = os.environ.get("CCAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libccal_hip.so")
@@ -232,6 +249,12 @@ SYMBOLS = [
                                                   _ip, _dp, _ip, _ip]),
     ("ccal_detect_checkerboards_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(DetectCheckerboardsOpts),
                                                 _ip, _dp, _ip, _ip]),
+    # rendering calibration targets through the camera models
+    ("ccal_render_set_defaults", C.c_int, [C.POINTER(RenderTarget), C.POINTER(RenderOpts)]),
+    ("ccal_render_targets_batch", C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(RenderTarget),
+                                            C.POINTER(RenderOpts), _vp]),
+    ("ccal_render_targets_dev", C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(RenderTarget),
+                                          C.POINTER(RenderOpts), _vp]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

@@ -53,8 +53,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from .engine import (CcalError, Context, MultiContext, MultiProblem, Problem, UndistortMap, check_images, check_maps, default_opts,
-                     make_desc)
+from .engine import (CcalError, Context, MultiContext, MultiProblem, Problem, UndistortMap, aprilgrid_target, check_images, check_maps,
+                     checkerboard_target, default_opts, make_desc)
 from .synth import MODEL_NAMES, MODEL_NPARAMS, PMAX, rodrigues, rotmat_to_rvec, splitmix64
 
 _MODEL_KEYS = {
@@ -1260,6 +1260,51 @@ def detect_aprilgrid(images, family: TagFamily, board: AprilGridBoard, step: int
     proposed = c.propose_quads_batch(stack, points, min_side, max_side, 2.0, offset, 8, min_contrast)
     decoded = decode_tags(list(stack), [p[1] for p in proposed], family, border, 3, min_contrast, 0, max_hamming, ctx=c)
     return frames_from_tags(decoded, board, (W, H), times, min_corners)
+
+
+def _render_args(where: str, model: GenericModel, poses, dtype) -> Tuple[np.ndarray, np.dtype]:
+    """The checks of the two renderers that need no device: (poses [n, 6], the images' dtype)."""
+    model._usable(where)
+    if np.dtype(dtype) not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+        raise ValueError(f"{where}: dtype is uint8 or uint16")
+    if len(poses) and all(isinstance(p, RvecTvec) for p in poses):
+        poses = [p.as6() for p in poses]
+    poses = np.asarray(poses, dtype=np.float64)
+    if poses.ndim != 2 or poses.shape[1] != 6:
+        raise ValueError(f"{where}: poses is a sequence of RvecTvec or an [n, 6] array of rvec, tvec")
+    w, h = int(model.width()), int(model.height())
+    if w != model.width() or h != model.height() or w <= 0 or h <= 0:
+        raise ValueError(f"{where}: the model's width and height are positive whole numbers of pixels")
+    return np.ascontiguousarray(poses), np.dtype(dtype)
+
+
+def render_checkerboard(model: GenericModel, poses, pattern: Tuple[int, int], square_size: float, dtype=np.uint8, supersample: int = 4,
+                        black: float = 40, white: float = 215, background: float = 0, margin: Optional[float] = None,
+                        ctx: Optional[Context] = None) -> np.ndarray:
+    """Images [n, H, W] of a checkerboard of pattern = (cols, rows) inner corners and squares of square_size metres as `model` sees
+    it at `poses` (board -> camera; a sequence of RvecTvec or an [n, 6] array), rendered on the GPU by the rule stated at
+    ccal_render_targets_batch in include/ccal.h: every pixel the mean of supersample x supersample rays through the model, black
+    and white squares at the given 8-bit grey levels (times 257 for uint16), `background` beyond the white sheet, which extends
+    `margin` metres (default: one square; inf: a white plane) beyond the squares.  Inner corner (c, r) is the board point
+    (c square_size, r square_size, 0), the labelling of detect_checkerboard.  H, W are the model's.  No blur, noise or vignetting."""
+    poses, dt = _render_args("render_checkerboard", model, poses, dtype)
+    target = checkerboard_target(int(pattern[0]), int(pattern[1]), square_size)
+    return _ctx(ctx).render_targets_batch(model.model_id, model.params(), int(model.width()), int(model.height()), poses, target, dt,
+                                          supersample, black, white, background, margin)
+
+
+def render_aprilgrid(model: GenericModel, poses, board: AprilGridBoard, family: TagFamily, border: int = 1, dtype=np.uint8,
+                     supersample: int = 4, black: float = 40, white: float = 215, background: float = 0,
+                     margin: Optional[float] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """Images [n, H, W] of the AprilGrid `board` printed from `family` (tag (r, c) shows the code of id first_id + r tag_cols + c,
+    `border` black cells around its data cells, black squares in the gaps at the tag corners) as `model` sees it at `poses`,
+    rendered on the GPU like render_checkerboard.  The geometry is board.id_to_3d's and the decoder's corner order; margin
+    defaults to one tag pitch."""
+    poses, dt = _render_args("render_aprilgrid", model, poses, dtype)
+    target = aprilgrid_target(board.tag_size_meter, board.tag_spacing, board.tag_rows, board.tag_cols, board.first_id, family.bits,
+                              family.codes, border)
+    return _ctx(ctx).render_targets_batch(model.model_id, model.params(), int(model.width()), int(model.height()), poses, target, dt,
+                                          supersample, black, white, background, margin)
 
 
 class ReprojectionFactor:

@@ -591,6 +591,43 @@ class Context:
                                    height, n_img, cols, rows, step, nms_radius, min_response, rel_threshold, max_candidates, half_win,
                                    max_iterations, eps)
 
+    # -- rendering calibration targets through the camera models (ccal_render_targets_batch, ccal_kernels_render.hip) ----------------
+    def _render(self, fn, where, out_ptr, model, params, dtype, width, height, poses, target, supersample, black, white, background,
+                margin):
+        poses = _f64(poses)
+        if poses.ndim != 2 or poses.shape[1] != 6:
+            raise ValueError(f"{where}: poses is an [n, 6] array of rvec, tvec")
+        o = render_opts(target, supersample, black, white, background, margin, lib=self.lib)
+        rc = fn(self.handle, int(model), _dp(_f64(params)), int(dtype), int(width), int(height), poses.shape[0], _dp(poses),
+                C.byref(target), C.byref(o), C.c_void_p(out_ptr))
+        if rc != _ffi.OK:
+            raise CcalError(rc, where, self.last_error())
+
+    def render_targets_batch(self, model: int, params, width: int, height: int, poses, target: "_ffi.RenderTarget", dtype=np.uint8,
+                             supersample: Optional[int] = None, black: Optional[float] = None, white: Optional[float] = None,
+                             background: Optional[float] = None, margin: Optional[float] = None) -> np.ndarray:
+        """Grey images [n][height][width] (uint8 or uint16) of `target` (checkerboard_target / aprilgrid_target) as the camera
+        (model, params) sees it at poses [n, 6] (rvec, tvec: board -> camera), by the rule stated at ccal_render_targets_batch in
+        include/ccal.h: every pixel the mean of supersample x supersample rays.  An option left at None takes
+        ccal_render_set_defaults' value (4; 40, 215, 0 grey levels; a margin of one square or one tag pitch)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise ValueError("render_targets_batch: uint8 or uint16 images")
+        n = _f64(poses).shape[0] if np.ndim(poses) == 2 else 0
+        out = np.empty((n, max(int(height), 0), max(int(width), 0)), dtype=dt)
+        self._render(self.lib.ccal_render_targets_batch, "ccal_render_targets_batch", out.ctypes.data if out.size else 0, model, params,
+                     _ffi.PIX_U8 if dt == np.uint8 else _ffi.PIX_U16, width, height, poses, target, supersample, black, white,
+                     background, margin)
+        return out
+
+    def render_targets_dev(self, out_ptr: int, model: int, params, dtype: int, width: int, height: int, poses, target: "_ffi.RenderTarget",
+                           supersample: Optional[int] = None, black: Optional[float] = None, white: Optional[float] = None,
+                           background: Optional[float] = None, margin: Optional[float] = None) -> None:
+        """render_targets_batch into a device block (a device pointer to [n][height][width] of dtype _ffi.PIX_U8 / PIX_U16) on the
+        context's stream: the block goes straight into detect_checkerboards_dev, detect_tags_dev or UndistortMap.remap_dev."""
+        self._render(self.lib.ccal_render_targets_dev, "ccal_render_targets_dev", out_ptr, model, params, dtype, width, height, poses,
+                     target, supersample, black, white, background, margin)
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first
@@ -634,6 +671,37 @@ def _family(where: str, family_bits, codes):
     if d * d != int(family_bits):
         raise ValueError(f"{where}: family_bits is not a square")
     return d, np.ascontiguousarray(np.asarray([int(c) for c in codes], dtype=np.uint64))
+
+
+def checkerboard_target(cols: int, rows: int, square: float) -> "_ffi.RenderTarget":
+    """The ccal_render_target of a checkerboard of cols x rows inner corners and squares of `square` metres."""
+    return _ffi.RenderTarget(kind=_ffi.TARGET_CHECKERBOARD, cols=int(cols), rows=int(rows), square=float(square))
+
+
+def aprilgrid_target(tag_size: float, tag_spacing: float, tag_rows: int, tag_cols: int, first_id: int, family_bits: int, codes,
+                     border: int = 1) -> "_ffi.RenderTarget":
+    """The ccal_render_target of an AprilGrid; it keeps the code table it points to alive."""
+    table = np.ascontiguousarray(np.asarray([int(c) for c in codes], dtype=np.uint64))
+    t = _ffi.RenderTarget(kind=_ffi.TARGET_APRILGRID, tag_size=float(tag_size), tag_spacing=float(tag_spacing), tag_rows=int(tag_rows),
+                          tag_cols=int(tag_cols), first_id=int(first_id), family_bits=int(family_bits), n_codes=len(table),
+                          border=int(border), codes=table.ctypes.data_as(C.POINTER(C.c_uint64)) if len(table) else None)
+    t._table = table
+    return t
+
+
+def render_opts(target: "_ffi.RenderTarget", supersample=None, black=None, white=None, background=None, margin=None,
+                lib=None) -> "_ffi.RenderOpts":
+    """ccal_render_set_defaults for `target`, then every option that is not None."""
+    o = _ffi.RenderOpts()
+    rc = (lib or _ffi.load()).ccal_render_set_defaults(C.byref(target), C.byref(o))
+    if rc != _ffi.OK:
+        raise CcalError(rc, "ccal_render_set_defaults")
+    if supersample is not None:
+        o.supersample = int(supersample)
+    for name, v in (("black", black), ("white", white), ("background", background), ("margin", margin)):
+        if v is not None:
+            setattr(o, name, float(v))
+    return o
 
 
 def _per_image(offs, n_img: int, arrays):

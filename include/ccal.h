@@ -1016,6 +1016,80 @@ int ccal_detect_checkerboards_dev(ccal_ctx* ctx, int dtype, int width, int heigh
                                   double* xy_out /* [n_img][cols*rows][2] */, int32_t* flags_out /* [n_img] */,
                                   int32_t* stats_out /* [n_img][4] or NULL */);
 
+/* ---- rendering calibration targets through the camera models ----------------------------------------------------------------------
+ * Grey images of a checkerboard or an AprilGrid as a camera of one of the four models sees it at given poses: what a synthetic
+ * session, a check of a planned board, lens and distance, or a timing tool needs in front of the image stages above.
+ * tests/render_ref.py is the numpy f64 yardstick of the rule below; the render unit is compiled without fused multiply-adds, so
+ * that steps 3 to 5 round as numpy rounds them.  Every operation is an IEEE f64 + - * / floor or rint, rounded on its own, in the
+ * order written.
+ *
+ * Inputs.  model, params: UCM, EUCM, KB4 or OPENCV5 with its parameters in the context's conventions (OPENCV5's coefficients are
+ * permuted to the canonical order at the boundary, as by ccal_project_points; the two small-radius thresholds are the context's).
+ * dtype, width, height, n_img: the images [n_img][height][width] of CCAL_PIX_U8 / CCAL_PIX_U16.  poses [n_img][6]: rvec then tvec,
+ * board -> camera.  The host turns each into R = I + sin(a) K + (1 - cos(a)) K K (a = |rvec|, K = [rvec / a]x; R = I when
+ * a < 1e-12) and tb = R^T t, tb_j = R[0][j] t[0] + R[1][j] t[1] + R[2][j] t[2], in f64.  target: ccal_render_target, one struct for
+ * both kinds.  opts: ccal_render_opts - supersample s in 1 .. 8; black, white, background in 8-bit grey levels (finite); margin >= 0
+ * in metres, +inf allowed: the white sheet extends that far beyond the pattern.  ccal_render_set_defaults: s = 4, black 40, white
+ * 215, background 0, margin = one square (checkerboard) or one tag pitch tag_size (1 + tag_spacing) (AprilGrid).
+ *
+ * Per sub-pixel ray (a, b), a, b = 0 .. s - 1, of pixel (px, py); its class is B (black), W (white) or G (background):
+ *   1 pixel     u = px + ((a + 0.5) / s - 0.5), v = py + ((b + 0.5) / s - 0.5).
+ *   2 ray       GenericModel::unproject of (u, v) as ccal_unproject_points states it; no ray: G.
+ *   3 plane     d_j = R[0][j] ray.x + R[1][j] ray.y + R[2][j] ray.z (d = R^T ray); k = tb.z / d.z; k not finite or not > 0: G.
+ *   4 point     X = k d.x - tb.x, Y = k d.y - tb.y: the point of the plane z = 0 of the board.
+ *   5 pattern   below; a point outside the sheet: G.
+ * Checkerboard (cols, rows inner corners, square): sheet -square - margin <= X <= cols square + margin, the same for Y with rows.
+ *   i = floor(X / square) + 1, j = floor(Y / square) + 1; the point is on the pattern when 0 <= i <= cols and 0 <= j <= rows, and
+ *   then B when i + j is even; everything else on the sheet is W.  Inner corner (c, r) lies at (c square, r square, 0) - the
+ *   labelling of ccal_detect_checkerboards_*.
+ * AprilGrid (tag_size, tag_spacing, tag_rows, tag_cols, first_id, family_bits = d d, codes, border): x to the right, rows towards
+ *   negative y.  pitch = tag_size (1 + tag_spacing), Yd = -Y, sheet -tag_spacing tag_size - margin <= X <= tag_cols pitch + margin,
+ *   the same for Yd with tag_rows.  c = floor(X / pitch), r = floor(Yd / pitch), u = (X - c pitch) / tag_size,
+ *   v = (Yd - r pitch) / tag_size.  Inside a tag - 0 <= c < tag_cols, 0 <= r < tag_rows, u < 1, v < 1 - with n = d + 2 border:
+ *   cell (cv, cu) = (floor(v n), floor(u n)) clamped to 0 .. n - 1; a cell of the border ring is B; data cell (cv - border,
+ *   cu - border) = (y, x) is W when bit d d - 1 - (y d + x) of code first_id + r tag_cols + c is set, else B - the bit order of
+ *   ccal_decode_tags_*.  A gap square - u >= 1, v >= 1, -1 <= c < tag_cols, -1 <= r < tag_rows - is B.  Everything else on the
+ *   sheet is W.  Tag (r, c)'s outer corners are (x, y), (x + s, y), (x + s, y - s), (x, y - s) with x = c pitch, y = -r pitch,
+ *   s = tag_size: the order of the decoder's corners_out.
+ * Pixel: lum = ((n_B black + n_W white) + n_G background) / (s s); the pixel is rint(lum) for u8 and rint(lum 257) for u16 (round
+ * half to even), clamped to the type.  The plane is two-sided: a pose that shows the back shows the mirror image.  No blur, noise
+ * or vignetting.
+ * An image is a pure function of the model, the target, the options and its pose: image k of a call equals the same pose rendered
+ * alone, whatever the batch and however the library cuts it into chunks, and runs repeat to the bit.  No atomics.
+ *
+ * ccal_render_targets_batch: images_out is a host array.  ccal_render_targets_dev: images_out_dev is a device pointer; the render
+ * runs on the context's stream and the block is never touched by the host, so it goes straight into ccal_detect_checkerboards_dev,
+ * ccal_detect_tags_dev or ccal_remap_dev.  Both return when the images are written.
+ * CCAL_ERR_UNSUPPORTED: the EUCMT container.  CCAL_ERR_INVALID_ARG with a message that names the argument, nothing launched or
+ * written: an unknown model, dtype or target kind; width, height <= 0 or n_img < 0; more than 2^31 - 1 pixels in an image;
+ * supersample outside 1 .. 8; black, white or background not finite; margin negative or NaN; square, tag_size or tag_spacing not
+ * finite and positive; cols, rows, tag_rows or tag_cols < 1; more than 4096 tags; family_bits not a square in 1 .. 64; border < 1;
+ * first_id < 0; n_codes < first_id + tag_rows tag_cols; params, target or opts NULL; with n_img > 0: poses, the output pointer or
+ * (AprilGrid) codes NULL.  n_img == 0 is valid. */
+typedef enum { CCAL_TARGET_CHECKERBOARD = 0, CCAL_TARGET_APRILGRID = 1 } ccal_target_kind;
+typedef struct {
+    int32_t kind;                          /* ccal_target_kind */
+    /* checkerboard */
+    int32_t cols, rows, reserved_;         /* inner corners */
+    double square;                         /* metres */
+    /* AprilGrid */
+    double tag_size, tag_spacing;          /* metres; the gap between tags as a fraction of tag_size */
+    int32_t tag_rows, tag_cols, first_id, family_bits, n_codes, border;
+    const uint64_t* codes;                 /* [n_codes]: the family's table, as for ccal_decode_tags_* */
+} ccal_render_target;
+typedef struct {
+    int32_t supersample, reserved_;
+    double black, white, background;       /* 8-bit grey levels */
+    double margin;                         /* metres */
+} ccal_render_opts;
+int ccal_render_set_defaults(const ccal_render_target* target, ccal_render_opts* opts);
+int ccal_render_targets_batch(ccal_ctx* ctx, int model, const double* params, int dtype, int width, int height, int n_img,
+                              const double* poses /* [n_img][6] */, const ccal_render_target* target, const ccal_render_opts* opts,
+                              void* images_out /* [n_img][height][width] */);
+int ccal_render_targets_dev(ccal_ctx* ctx, int model, const double* params, int dtype, int width, int height, int n_img,
+                            const double* poses /* [n_img][6] */, const ccal_render_target* target, const ccal_render_opts* opts,
+                            void* images_out_dev /* [n_img][height][width] */);
+
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
                              double* err_out /* [n_corners] Euclidean px error */);
