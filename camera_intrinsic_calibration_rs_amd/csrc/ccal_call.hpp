@@ -1,8 +1,11 @@
 // One-shot batch calls (host arrays in, host arrays out): ONE device block of the context's allocator, cut into slices that each
 // start on a 256-byte boundary; uploads, the launch, downloads and one synchronise, all on the context's stream.
-//   CallPlan   the slices in order and the total - plain arithmetic, no context and no HIP call (ccal_plan.hpp)
+//   CallPlan   the slices in order and the total - plain arithmetic, no context and no HIP call (ccal_plan.hpp; GuardedPlan: with
+//              the tests' guards)
 //   CallBlock  the plan, the block and a sticky hipError_t: after the first failure every step is a no-op and finish() reports it;
-//              the destructor drains the stream before the block goes back to the context's cache, on every way out
+//              the destructor drains the stream before the block goes back to the context's cache, on every way out.  In the tests'
+//              guard mode (CCAL_TEST_GUARD_SLICES in the second library) guards of a known byte lie round every slice and
+//              finish() reports a damaged one
 //   BadArg     the way out of an entry point on a bad argument, with the call's name in the message
 //   check_offsets  the argument check of a batched call's CSR offsets, with the call's name in the message
 //   GreyBatch  the image arguments of the image stages' calls: their check, an image's bytes, the device pointer to a chunk's images
@@ -38,13 +41,13 @@ inline int check_offsets(ccal_ctx* ctx, const char* where, const char* name, con
     return bad ? BadArg{ ctx, where }((std::string(name) + bad).c_str()) : CCAL_OK;
 }
 
-class CallBlock : public CallPlan {
+class CallBlock : public GuardedPlan {
     ccal_ctx* ctx;
     char* base = nullptr;
     hipError_t e = hipSuccess;
 
 public:
-    explicit CallBlock(ccal_ctx* c) : ctx(c) {}
+    explicit CallBlock(ccal_ctx* c) : ctx(c) { guard_front(test_guard_slices() ? kGuardGap : 0); }
     CallBlock(const CallBlock&) = delete;
     CallBlock& operator=(const CallBlock&) = delete;
     ~CallBlock() {
@@ -57,12 +60,23 @@ public:
     bool alloc() {                                   // after the last add(); false: there is no block, leave through finish()
         note(hipSetDevice(ctx->device));
         if (ok()) note(ctx_dev_alloc(ctx, (void**)&base, total));
+        fill_guards();
         return ok();
     }
     template <class T> T* at(Slice<T> s) const { return s.bytes ? reinterpret_cast<T*>(base + s.off) : nullptr; }
     // the test hook's NaN fill over the slices first .. last (slices of doubles, never offsets, indices, seeds or counts)
+    // In the guard mode the fill spans the guards between its slices without touching them: it goes from guard to guard, so that they
+    // hold their pattern after it - and still hold what a kernel of an earlier chunk did to them, which a refill would wipe out.
     template <class A, class B> void poison(Slice<A> first, Slice<B> last) {
-        if (ok()) note(test_poison_f64(ctx, base + first.off, last.off + last.bytes - first.off, false, ctx->stream));
+        size_t from = first.off;
+        const size_t end = last.off + last.bytes;
+        for (int i = 0; i < n_guards && ok(); ++i) {
+            const Guard& g = guards[i];
+            if (g.off + g.bytes <= from || g.off >= end) continue;
+            if (g.off > from) note(test_poison_f64(ctx, base + from, g.off - from, false, ctx->stream));
+            from = g.off + g.bytes;
+        }
+        if (ok() && from < end) note(test_poison_f64(ctx, base + from, end - from, false, ctx->stream));
     }
     template <class T> void memset(Slice<T> s, int value, size_t count) {
         if (ok() && count) note(hipMemsetAsync(at(s), value, count * sizeof(T), ctx->stream));
@@ -76,7 +90,41 @@ public:
     void launched() { note(hipGetLastError()); }
     int finish(const char* where) {
         if (ok()) note(hipStreamSynchronize(ctx->stream));
+        if (ok() && n_guards) return check_guards(where);
         return ok() ? CCAL_OK : hip_fail(ctx, where, e);
+    }
+
+private:
+    // The guard mode (the second library with CCAL_TEST_GUARD_SLICES=1, tests/test_gpu_guard.py; n_guards == 0 everywhere else): the
+    // plan's guards hold kGuardByte from alloc() on, and finish() - a call that got that far without an error - reads them back.
+    static constexpr size_t kGuardGap = 256;
+    static constexpr int kGuardByte = 0xA5;          // neither a cleared byte nor the poison's 0xFF
+    void fill_guards() {
+        for (int i = 0; i < n_guards && ok(); ++i) note(hipMemsetAsync(base + guards[i].off, kGuardByte, guards[i].bytes, ctx->stream));
+    }
+    // the first damaged byte: CCAL_ERR_HIP, "<where>: guard after slice <ordinal> damaged, <d> bytes past the slice's end" or "<where>:
+    // guard in front of the block damaged, <d> bytes in front of the first slice"
+    int check_guards(const char* where) {
+        size_t all = 0;
+        for (int i = 0; i < n_guards; ++i) all += guards[i].bytes;
+        std::vector<unsigned char> h(all);
+        unsigned char* to = h.data();
+        for (int i = 0; i < n_guards && ok(); to += guards[i++].bytes)
+            note(hipMemcpyAsync(to, base + guards[i].off, guards[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (ok()) note(hipStreamSynchronize(ctx->stream));
+        if (!ok()) return hip_fail(ctx, where, e);
+        const unsigned char* at = h.data();
+        for (int i = 0; i < n_guards; at += guards[i++].bytes) {
+            const Guard& g = guards[i];
+            for (size_t j = 0; j < g.bytes; ++j) {
+                if (at[j] == kGuardByte) continue;
+                char msg[200];
+                if (g.after < 0) snprintf(msg, sizeof msg, "%s: guard in front of the block damaged, %zu bytes in front of the first slice", where, g.bytes - j);
+                else snprintf(msg, sizeof msg, "%s: guard after slice %d damaged, %zu bytes past the slice's end", where, g.after, j);
+                return fail(ctx, CCAL_ERR_HIP, msg);
+            }
+        }
+        return CCAL_OK;
     }
 };
 

@@ -142,6 +142,10 @@ inline void ctx_stream_put(ccal_ctx* ctx, hipStream_t s) {
 // wrote turns into NaN (tests/test_gpu_poison.py).  Never called on indices, offsets, counters, flags or DevState.  Defined out of
 // line in ccal_solver_ws.hip, which each library compiles itself; hidden, so that each library calls its own.  The product's is empty.
 __attribute__((visibility("hidden"))) hipError_t test_poison_f64(ccal_ctx* ctx, void* p, size_t bytes, bool host, hipStream_t s);
+// Test hook of the second library, the same way: true with CCAL_TEST_GUARD_SLICES=1 - a one-shot call's block (ccal_call.hpp:
+// CallBlock) then keeps a guard of a known byte in front of its first slice and behind every slice, and finish() reports a damaged one
+// (tests/test_gpu_guard.py).  Read on every call.  The product's returns false.
+__attribute__((visibility("hidden"))) bool test_guard_slices();
 // A persistent block as its plan describes it: from the context's allocator, the test hook's NaN over its slices of doubles, then ONE
 // clear of the slices that must start as zeros - on the context's stream (it does not synchronise with the null stream), in front of every use
 inline hipError_t ctx_block_alloc(ccal_ctx* ctx, const CallPlan& pl, char** out, bool host) {

@@ -34,6 +34,35 @@ struct CallPlan {
     }
 };
 
+// The one-shot calls' plan (ccal_call.hpp: CallBlock), which the tests can lay out with guards (CCAL_TEST_GUARD_SLICES in the second
+// library); the persistent blocks' plans are plain CallPlans and know nothing of it.  guard_front(gap) in front of the first add() puts
+// `gap` bytes at the head of the block, and every present slice is followed by a guard that starts at the slice's EXACT end - the slack
+// up to the next 256-byte boundary is part of it - and goes on for `gap` bytes past that boundary.  Slices still start on 256-byte
+// boundaries; an absent slice adds nothing.  after: the ordinal of the slice (absent ones count) the guard follows, -1 for the one in
+// front.  With gap 0 offsets and total are CallPlan's.
+struct GuardedPlan : CallPlan {
+    struct Guard { size_t off = 0, bytes = 0; int after = -1; };
+    static constexpr int kMaxGuards = 96;  // the largest call has a few dozen slices
+    size_t gap = 0;
+    Guard guards[kMaxGuards];
+    int n_guards = 0, n_slices = 0;
+    void guard_front(size_t g) {
+        assert(total == 0 && n_slices == 0 && g % 256 == 0 && "in front of the first slice");
+        gap = g;
+        if (gap) { guards[n_guards++] = { 0, gap, -1 }; total = gap; }
+    }
+    template <class T> Slice<T> add(size_t count) {      // (a one-shot call's slices carry no flags: poison() and memset() are explicit there)
+        const Slice<T> s = CallPlan::add<T>(count);
+        const int ordinal = n_slices++;
+        if (gap && s.bytes) {
+            assert(n_guards < kMaxGuards);
+            guards[n_guards++] = { s.off + count * sizeof(T), s.bytes - count * sizeof(T) + gap, ordinal };
+            total += gap;
+        }
+        return s;
+    }
+};
+
 // a planned block where it lies: the slices' addresses (absent = NULL)
 struct Bound { char* base = nullptr; template <class T> T* at(Slice<T> s) const { return s.bytes ? reinterpret_cast<T*>(base + s.off) : nullptr; } };
 

@@ -1,7 +1,8 @@
 // Mode N host side, the workspaces: what a problem's solves and builds keep on the device and in pinned memory (NormalWs: every loop's
 // part and the general loop's; FusedWs: the single-camera loop's), each ONE planned block from its layout (ccal_normal.hpp), made on
-// first use and given back to the context's cache with the problem; the column table; and the tests' poison hook, which every
-// allocation of doubles passes through (ccal_internal.hpp).  The loops that use them: ccal_solver.hip.
+// first use and given back to the context's cache with the problem; the column table; and the tests' two hooks: the poison, which
+// every allocation of doubles passes through, and the switch of the one-shot calls' slice guards (ccal_internal.hpp).  The loops that
+// use them: ccal_solver.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +23,15 @@ hipError_t test_poison_f64(ccal_ctx* ctx, void* p, size_t bytes, bool host, hipS
 #else
     (void)ctx; (void)p; (void)bytes; (void)host; (void)s;
     return hipSuccess;
+#endif
+}
+
+bool test_guard_slices() {
+#ifdef CCAL_TEST_HOOKS
+    const char* e = std::getenv("CCAL_TEST_GUARD_SLICES");       // read on every call, as above
+    return e && e[0] == '1';
+#else
+    return false;
 #endif
 }
 

@@ -176,4 +176,28 @@ extern "C" int ccal_test_select_tags(ccal_ctx* ctx, int n_img, const int64_t* of
     return blk.finish(where);
     CCAL_API_CATCH(ctx)
 }
+
+// The proof that CallBlock's guard mode (CCAL_TEST_GUARD_SLICES, ccal_call.hpp) sees a stray write (tests/test_gpu_guard.py): a block
+// of three slices - double x 5, an absent one, int32_t x 65 - of which the host damages ONE byte, `delta` bytes from the exact end
+// (from_end != 0) or from the start of slice 0 or 2, with a memset on the context's stream; the status is finish()'s.  A position
+// outside the block's own allocation (the byte in front of slice 0 without the guard mode) is not written.
+extern "C" int ccal_test_guard_damage(ccal_ctx* ctx, int slice, int from_end, int64_t delta) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    const char* where = "ccal_test_guard_damage";
+    if (slice != 0 && slice != 2) return ccal::fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_test_guard_damage: slice 0 or 2");
+    ccal::CallBlock blk(ctx);
+    const auto s_a = blk.add<double>(5);
+    const auto s_none = blk.add<double>(0);
+    const auto s_c = blk.add<int32_t>(65);
+    (void)s_none;
+    if (!blk.alloc()) return blk.finish(where);
+    blk.memset(s_a, 0, 5);
+    blk.memset(s_c, 0, 65);
+    const int64_t pos = (int64_t)(slice == 0 ? s_a.off : s_c.off) + (from_end ? (slice == 0 ? 5 * (int64_t)sizeof(double) : 65 * (int64_t)sizeof(int32_t)) : 0) + delta;
+    if (pos >= 0 && pos < (int64_t)blk.total && blk.ok())
+        blk.note(hipMemsetAsync(reinterpret_cast<char*>(blk.at(s_a)) - s_a.off + pos, 0x3C, 1, ctx->stream));
+    return blk.finish(where);
+    CCAL_API_CATCH(ctx)
+}
 #endif

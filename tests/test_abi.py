@@ -50,6 +50,7 @@ def test_no_test_hooks_in_the_product_library():
     legacy = open(_ffi.LEGACY_LIB_PATH, "rb").read()
     assert b"CCAL_TEST_FAIL_SHARD" in legacy
     assert b"CCAL_TEST_POISON_ALLOC" in legacy
+    assert b"CCAL_TEST_GUARD_SLICES" in legacy                         # the one-shot calls' slice guards (tests/test_gpu_guard.py)
 
 
 def test_host_only_entry_points():

@@ -1,7 +1,10 @@
 """CPU: the slice plan of the one-shot calls' device block (csrc/ccal_call.hpp: CallPlan) through a plain C++ program
 (tests/cpp/test_call_plan.cpp) under the host's address and undefined-behaviour sanitizers: every slice on a 256-byte boundary, in
 declaration order, none overlapping, an absent optional slice of zero bytes, the total the sum of the rounded sizes - and the layout of
-ccal_refine_poses_batch for 5 problems with 195 points as large as the byte formulas of that entry point say, worked out here."""
+ccal_refine_poses_batch for 5 problems with 195 points as large as the byte formulas of that entry point say, worked out here.  The
+same program holds the guarded layout of the tests' CCAL_TEST_GUARD_SLICES mode (tests/test_gpu_guard.py): a guard in front, slices
+on 256-byte boundaries and in order, a guard of at least 256 bytes from every present slice's exact end, none for an absent slice, the
+total the sum - and with gap 0 the numbers above."""
 import os
 import subprocess
 

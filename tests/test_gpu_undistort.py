@@ -293,6 +293,31 @@ def test_remap_dev_equals_the_host_pointer_call(gpu_ctx, dtype, ch):
         m.close()
 
 
+@pytest.mark.parametrize("n_img", [1, 5])
+@pytest.mark.parametrize("dtype,ch", _PIX)
+def test_remap_dev_writes_every_byte_and_nothing_else(gpu_ctx, dtype, ch, n_img):
+    """ccal_remap_dev writes into the caller's device memory: the destination lies in a torch block with 64 guard bytes on each side,
+    every byte set to a fill beforehand.  With two fills, the guards keep theirs and every destination byte is the host-pointer
+    call's - a byte the kernel skipped would keep one of the fills.  A 37 x 23 map: 851 pixels, no multiple of 4."""
+    import torch
+    xm, ym = _random_maps(37, 23)
+    imgs = _images(dtype, ch, n_img)
+    m = gpu_ctx.undistort_map_from_arrays(xm, ym)
+    try:
+        host = m.remap(imgs)
+        raw = torch.from_numpy(imgs.view(np.uint8).reshape(-1).copy()).cuda()
+        for fill in (0x5A, 0xA5):
+            block = torch.full((host.nbytes + 128,), fill, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            m.remap_dev(raw.data_ptr(), block.data_ptr() + 64, _ffi.PIX_U8 if dtype == np.uint8 else _ffi.PIX_U16, ch, SW, SH, n_img)
+            gpu_ctx.sync()
+            got = block.cpu().numpy()
+            assert (got[:64] == fill).all() and (got[-64:] == fill).all(), "bytes outside the destination were written"
+            assert got[64:-64].tobytes() == host.tobytes(), fill
+    finally:
+        m.close()
+
+
 def test_remap_refuses_bad_arguments(gpu_ctx):
     xm, ym = _identity_maps()
     m = gpu_ctx.undistort_map_from_arrays(xm, ym)
