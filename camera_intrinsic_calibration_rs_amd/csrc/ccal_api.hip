@@ -238,18 +238,39 @@ int ccal_problem_create(ccal_ctx* ctx, const ccal_problem_desc* d, ccal_problem*
     HIP_TRY(ctx, ctx_dev_alloc(ctx, (void**)&p->d_block, total));
     // Session-sized problems (up to 8 MB of inputs) are packed into ONE pinned staging block laid out like the device block and
     // uploaded with ONE copy: ten hipMemcpyAsync calls from pageable memory - each staged by the runtime on its own - were
-    // ~0.1 ms of ccal_problem_create's 0.2 ms at 600 frames.  Larger problems keep the per-array copies (packing 29 MB on the
-    // host would cost more than it saves).
+    // ~0.1 ms of ccal_problem_create's 0.2 ms at 600 frames.  Larger problems are cleared on the device and go array by array
+    // (no image of 29 MB and more on the host), see below.
     char* h_pack = nullptr;
     struct PackGuard { ccal_ctx* c; char*& p; ~PackGuard() { if (p) { (void)hipStreamSynchronize(c->stream); ccal::ctx_release(c, p, true); } } } pack_guard{ ctx, h_pack };      // (a copy may still read it on an error exit)
     if (total <= ((size_t)8 << 20)) HIP_TRY(ctx, ctx_host_alloc(ctx, (void**)&h_pack, total));
-    if (!h_pack) HIP_TRY(ctx, hipMemsetAsync(p->d_block, 0, total, ctx->stream));
+    // Larger problems: array by array, but through a pinned staging buffer of the library's own, never with a copy from the caller's
+    // pageable memory.  For a pageable source of this size the runtime pins the caller's pages in place and remembers the pinning by
+    // address and size; a process that had freed an array of the same size at the same address before (the arrays of an earlier problem
+    // of as many frames) ended in `an illegal memory access was encountered` inside this function - every recorded case is this path, a
+    // problem of 3 000 or 10 000 frames created after another one of that size in the same process.  (The stale pinning is a reading of
+    // those records, not a measurement.)
+    constexpr size_t kStageBytes = (size_t)4 << 20;
+    char* h_stage = nullptr;
+    PackGuard stage_guard{ ctx, h_stage };
+    if (!h_pack) {
+        HIP_TRY(ctx, ctx_host_alloc(ctx, (void**)&h_stage, kStageBytes));
+        HIP_TRY(ctx, hipMemsetAsync(p->d_block, 0, total, ctx->stream));
+    }
     {
         const Bound dev{ p->d_block }, img{ h_pack };
         auto put = [&](auto** dst, auto slice, const auto* src, size_t n) -> hipError_t {
             *dst = dev.at(slice);
             const size_t nb = src ? n * sizeof(*src) : 0;
-            if (!h_pack) return nb ? hipMemcpyAsync(*dst, src, nb, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+            if (!h_pack) {
+                for (size_t off = 0; off < nb; off += kStageBytes) {      // (the buffer is free again once the stream has drained)
+                    const size_t m = std::min(kStageBytes, nb - off);
+                    std::memcpy(h_stage, reinterpret_cast<const char*>(src) + off, m);
+                    hipError_t e = hipMemcpyAsync(reinterpret_cast<char*>(*dst) + off, h_stage, m, hipMemcpyHostToDevice, ctx->stream);
+                    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+                    if (e != hipSuccess) return e;
+                }
+                return hipSuccess;
+            }
             if (nb) std::memcpy(img.at(slice), src, nb);       // (the slack behind the data must be zeros: the kernels load - and mask - one element past an empty last frame)
             if (slice.bytes) std::memset((char*)img.at(slice) + nb, 0, slice.bytes - nb);
             return hipSuccess;

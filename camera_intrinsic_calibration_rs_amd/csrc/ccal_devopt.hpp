@@ -3,7 +3,7 @@
 // switch below is compiled out (dev_env is a constant NULL, the branches behind it disappear).  The SECOND build of the library
 // (libccal_hip_legacy.so: -DCCAL_DEV_SWITCHES -DCCAL_LEGACY_KERNELS -DCCAL_TEST_HOOKS; tests and A/B tools load it by name)
 // reads them from the environment: they select among implementations that the parity tests hold to the same results.
-// All call sites live in translation units that are compiled twice (ccal_kernels_fused, ccal_kernels_normal and the solver's
+// All call sites live in translation units that are compiled twice (ccal_kernels_fused, ccal_kernels_normal, ccal_kernels_eval and the solver's
 // host side: ccal_solver, ccal_solver_ws, ccal_solver_many); choices that concern other translation units travel as arguments (FusedArgs::lpf_force, NormalWs::schurq_slots).
 #pragma once
 #include <cstdlib>
