@@ -113,6 +113,13 @@ class RenderOpts(C.Structure):            # ccal_render_opts
                 ("background", C.c_double), ("margin", C.c_double)]
 
 
+class PhotoOpts(C.Structure):             # ccal_photo_opts: the photometric stage; ccal_photo_set_defaults switches everything off
+    _fields_ = [("blur_sigma", C.c_double), ("vignette", C.c_double), ("gain", C.c_double), ("noise_read", C.c_double),
+                ("noise_shot", C.c_double), ("seed", C.c_uint64), ("first_index", C.c_int64)]
+
+
+PHOTO_MAX_RADIUS = 16                     # CCAL_PHOTO_MAX_RADIUS
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 LIB_PATH = os.environ.get("CCAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libccal_hip.so")
@@ -255,6 +262,14 @@ SYMBOLS = [
                                             C.POINTER(RenderOpts), _vp]),
     ("ccal_render_targets_dev", C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(RenderTarget),
                                           C.POINTER(RenderOpts), _vp]),
+    # the photometric stage: lens blur, vignetting, exposure and sensor noise
+    ("ccal_photo_set_defaults", C.c_int, [C.POINTER(PhotoOpts)]),
+    ("ccal_photo_tables", C.c_int, [C.POINTER(PhotoOpts), _ip, _dp, _dp]),
+    ("ccal_photo_apply_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(PhotoOpts)]),
+    ("ccal_render_photo_targets", C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(RenderTarget),
+                                            C.POINTER(RenderOpts), C.POINTER(PhotoOpts), _vp]),
+    ("ccal_render_photo_targets_dev", C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(RenderTarget),
+                                                C.POINTER(RenderOpts), C.POINTER(PhotoOpts), _vp]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

@@ -1278,33 +1278,49 @@ def _render_args(where: str, model: GenericModel, poses, dtype) -> Tuple[np.ndar
     return np.ascontiguousarray(poses), np.dtype(dtype)
 
 
+@dataclasses.dataclass
+class PhotoOpts:
+    """The photometric stage between ideal irradiance and pixels (ccal_photo_opts in include/ccal.h states the rule): a Gaussian lens
+    blur of blur_sigma px (0 .. 16/3), vignetting with the gain 1 / (1 + vignette)^2 at the corners, the exposure `gain`, read noise
+    of noise_read grey levels (8-bit scale) and shot noise of variance noise_shot per grey level; image k of a call draws from the
+    stream seed + first_index + k.  The defaults switch everything off."""
+    blur_sigma: float = 0.0
+    vignette: float = 0.0
+    gain: float = 1.0
+    noise_read: float = 0.0
+    noise_shot: float = 0.0
+    seed: int = 0
+    first_index: int = 0
+
+
 def render_checkerboard(model: GenericModel, poses, pattern: Tuple[int, int], square_size: float, dtype=np.uint8, supersample: int = 4,
                         black: float = 40, white: float = 215, background: float = 0, margin: Optional[float] = None,
-                        ctx: Optional[Context] = None) -> np.ndarray:
+                        ctx: Optional[Context] = None, photo: Optional[PhotoOpts] = None) -> np.ndarray:
     """Images [n, H, W] of a checkerboard of pattern = (cols, rows) inner corners and squares of square_size metres as `model` sees
     it at `poses` (board -> camera; a sequence of RvecTvec or an [n, 6] array), rendered on the GPU by the rule stated at
     ccal_render_targets_batch in include/ccal.h: every pixel the mean of supersample x supersample rays through the model, black
     and white squares at the given 8-bit grey levels (times 257 for uint16), `background` beyond the white sheet, which extends
     `margin` metres (default: one square; inf: a white plane) beyond the squares.  Inner corner (c, r) is the board point
-    (c square_size, r square_size, 0), the labelling of detect_checkerboard.  H, W are the model's.  No blur, noise or vignetting."""
+    (c square_size, r square_size, 0), the labelling of detect_checkerboard.  H, W are the model's.  photo None: ideal images;
+    a PhotoOpts: lens blur, vignetting, exposure and sensor noise on the device, in the same call."""
     poses, dt = _render_args("render_checkerboard", model, poses, dtype)
     target = checkerboard_target(int(pattern[0]), int(pattern[1]), square_size)
     return _ctx(ctx).render_targets_batch(model.model_id, model.params(), int(model.width()), int(model.height()), poses, target, dt,
-                                          supersample, black, white, background, margin)
+                                          supersample, black, white, background, margin, photo=photo)
 
 
 def render_aprilgrid(model: GenericModel, poses, board: AprilGridBoard, family: TagFamily, border: int = 1, dtype=np.uint8,
                      supersample: int = 4, black: float = 40, white: float = 215, background: float = 0,
-                     margin: Optional[float] = None, ctx: Optional[Context] = None) -> np.ndarray:
+                     margin: Optional[float] = None, ctx: Optional[Context] = None, photo: Optional[PhotoOpts] = None) -> np.ndarray:
     """Images [n, H, W] of the AprilGrid `board` printed from `family` (tag (r, c) shows the code of id first_id + r tag_cols + c,
     `border` black cells around its data cells, black squares in the gaps at the tag corners) as `model` sees it at `poses`,
     rendered on the GPU like render_checkerboard.  The geometry is board.id_to_3d's and the decoder's corner order; margin
-    defaults to one tag pitch."""
+    defaults to one tag pitch; photo as there."""
     poses, dt = _render_args("render_aprilgrid", model, poses, dtype)
     target = aprilgrid_target(board.tag_size_meter, board.tag_spacing, board.tag_rows, board.tag_cols, board.first_id, family.bits,
                               family.codes, border)
     return _ctx(ctx).render_targets_batch(model.model_id, model.params(), int(model.width()), int(model.height()), poses, target, dt,
-                                          supersample, black, white, background, margin)
+                                          supersample, black, white, background, margin, photo=photo)
 
 
 class ReprojectionFactor:

@@ -1,0 +1,263 @@
+// The photometric stage (ccal_photo_apply_dev; ccal_render_photo_targets / _dev through the renderer's host code): from ideal
+// irradiance to pixels - Gaussian lens blur, vignetting, exposure, read and shot noise, quantisation - by the rule stated at the
+// entry points in include/ccal.h.  All images of a call in ONE launch:
+//   k_photo<S, D>  a workgroup owns an output tile of 64 x 16 pixels of one image; blockIdx.x walks the tiles of an image,
+//            blockIdx.y the images.  The radius, the taps and the noise table arrive by value in the kernel's arguments and go into
+//            LDS once per workgroup: no device allocation, nothing staged.
+//   tile     the source tile with a halo of r pixels on every side, clamped to the image, goes into LDS as u16 (a u8 source times 257).
+//   rows     the horizontal pass: lane = x, a wavefront per tile row (halo rows included), f64 rows in LDS.
+//   columns  the vertical pass: lane = x again, so that the 64 lanes of a wavefront read 64 consecutive doubles of one f64 row - no
+//            bank conflict; a lane owns four rows of its column and reads every f64 row it needs once.  r = 0 skips both passes and
+//            reads the pixel from the source.
+//   pixel    steps c to g in the lane that holds B(x, y).  The noise is counter-based: three splitmix64 finalisers per pixel, keyed by
+//            the image's stream and the pixel's index - no state, no atomics, no order.
+//   stores   the lanes of a group of 4 (u8) or 2 (u16) adjacent pixels hand their pixels to the group's first lane, which stores them
+//            as one dword; a group that ends at the image's right edge, or whose first pixel is not on a dword boundary (rows of a
+//            width that is no multiple of 4 bytes), stores pixel by pixel: no lane ever writes a byte outside the image.
+// This unit is compiled with -ffp-contract=off (csrc/Makefile): every product and sum rounds on its own, as tests/photo_ref.py, the
+// numpy yardstick, does; the device is held to it bit for bit.
+#include <algorithm>
+#include <cmath>
+#include "ccal_call.hpp"
+#include "ccal_photo.hpp"
+
+namespace ccal {
+
+constexpr int kPhotoTileW = 64, kPhotoTileH = 16, kPhotoRows = 4;   // a workgroup: 4 wavefronts, each 64 columns x 4 rows
+constexpr int kPhotoMaxR = CCAL_PHOTO_MAX_RADIUS;
+static_assert(kPhotoTileH == 4 * kPhotoRows, "four wavefronts cover the tile's rows");
+
+struct PhotoArgs {
+    PhotoTables t;                     // 273 doubles: under the 4 KB of a kernel's arguments
+    const void* src;                   // [n_img][H][W]
+    void* dst;                         // [n_img][H][W]
+    int32_t W, H, n_img, tiles_x;
+    double vignette, gain, cx, cy, den;   // den = cx cx + cy cy, 0 for a 1 x 1 image
+    unsigned long long stream0;        // seed + first_index + the index in the call of the launch's first image
+    int32_t noisy, reserved_;          // 0: the noise table is all zeros, Y = V
+};
+static_assert(sizeof(PhotoArgs) <= 4096, "the kernel's arguments");
+
+__host__ __device__ __forceinline__ unsigned long long photo_mix(unsigned long long a) {
+    a ^= a >> 30; a *= 0xBF58476D1CE4E5B9ull;
+    a ^= a >> 27; a *= 0x94D049BB133111EBull;
+    a ^= a >> 31;
+    return a;
+}
+__device__ __forceinline__ unsigned photo_fields(unsigned long long w) {
+    return (unsigned)(w & 0xFFFFull) + (unsigned)((w >> 16) & 0xFFFFull) + (unsigned)((w >> 32) & 0xFFFFull) + (unsigned)(w >> 48);
+}
+
+template <class T> struct PhotoPix;
+template <> struct PhotoPix<uint8_t> { static constexpr double hi = 255.0, scale = 1.0; static constexpr unsigned up = 257u; };
+template <> struct PhotoPix<uint16_t> { static constexpr double hi = 65535.0, scale = 257.0; static constexpr unsigned up = 1u; };
+
+// LDS: the noise table [256], the taps [24 with padding], the f64 rows [TH + 2 r][TW], the u16 tile [TH + 2 r][TW + 2 r]
+__host__ __device__ inline size_t photo_lds_bytes(int r) {
+    const size_t ih = (size_t)(kPhotoTileH + 2 * r), iw = (size_t)(kPhotoTileW + 2 * r);
+    return r == 0 ? sizeof(double) * (256 + 24) : sizeof(double) * (256 + 24 + ih * kPhotoTileW) + ((sizeof(uint16_t) * ih * iw + 15) & ~(size_t)15);
+}
+
+template <class S, class D>
+__global__ __launch_bounds__(256) void k_photo(const PhotoArgs a) {
+    constexpr int PX = 4 / (int)sizeof(D), BITS = 8 * (int)sizeof(D);
+    extern __shared__ __attribute__((aligned(16))) double lds_photo[];
+    double* sig_s = lds_photo;                                       // [256]
+    double* tap_s = lds_photo + 256;                                 // [17], 24 reserved
+    double* rows_s = lds_photo + 256 + 24;                           // [ih][TW]
+    const int r = a.t.radius;
+    const int ih = kPhotoTileH + 2 * r, iw = kPhotoTileW + 2 * r;
+    uint16_t* tile_s = reinterpret_cast<uint16_t*>(rows_s + (size_t)ih * kPhotoTileW);   // [ih][iw]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    sig_s[tid] = a.t.sigma[tid];
+    if (tid <= kPhotoMaxR) tap_s[tid] = a.t.taps[tid];
+
+    const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
+    const int x_t = tile_x * kPhotoTileW, y_t = tile_y * kPhotoTileH;      // the tile's first pixel
+    const int x = x_t + lane, y0 = y_t + wave * kPhotoRows;                // this lane's column and its first row
+    const int xc = min(x, a.W - 1);                                        // a lane beyond the right edge works on the edge and stores nothing
+    const S* src = static_cast<const S*>(a.src);
+    D* dst = static_cast<D*>(a.dst);
+    const int64_t n_pix = (int64_t)a.W * a.H;
+
+    for (int img = blockIdx.y; img < a.n_img; img += gridDim.y) {
+        const S* I = src + (int64_t)img * n_pix;
+        double B[kPhotoRows];
+        if (r == 0) {
+            __syncthreads();                                               // the tables, on the first image
+#pragma unroll
+            for (int i = 0; i < kPhotoRows; ++i) B[i] = (double)((unsigned)I[(int64_t)min(y0 + i, a.H - 1) * a.W + xc] * PhotoPix<S>::up);
+        } else {
+            // the tile with its halo, clamped to the image
+            for (int e = tid; e < ih * iw; e += 256) {
+                const int ty = e / iw, tx = e - ty * iw;
+                const int gx = min(max(x_t - r + tx, 0), a.W - 1), gy = min(max(y_t - r + ty, 0), a.H - 1);
+                tile_s[e] = (uint16_t)((unsigned)I[(int64_t)gy * a.W + gx] * PhotoPix<S>::up);
+            }
+            __syncthreads();
+            // a: rows.  tile column lane + r + j is pixel x + j
+            for (int ty = wave; ty < ih; ty += 4) {
+                const uint16_t* row = tile_s + ty * iw + lane;
+                double acc = 0.0;
+                for (int j = -r; j <= r; ++j) acc = acc + tap_s[abs(j)] * (double)row[r + j];
+                rows_s[ty * kPhotoTileW + lane] = acc;
+            }
+            __syncthreads();
+            // b: columns.  f64 row ty is image row y_t - r + ty: output row y0 + i takes the rows wave * 4 + i + (0 .. 2 r), tap |m - r|
+#pragma unroll
+            for (int i = 0; i < kPhotoRows; ++i) B[i] = 0.0;
+            const double* col = rows_s + (wave * kPhotoRows) * kPhotoTileW + lane;
+            for (int m = 0; m < kPhotoRows + 2 * r; ++m) {
+                const double h = col[m * kPhotoTileW];
+#pragma unroll
+                for (int i = 0; i < kPhotoRows; ++i) {
+                    const int j = m - i - r;                               // ascending in m for every i
+                    if (j >= -r && j <= r) B[i] = B[i] + tap_s[abs(j)] * h;
+                }
+            }
+        }
+        const unsigned long long key = photo_mix(a.stream0 + (unsigned long long)img);
+#pragma unroll
+        for (int i = 0; i < kPhotoRows; ++i) {
+            const int y = y0 + i;                                          // wave-uniform
+            if (y >= a.H) break;
+            // c
+            const double dx = (double)x - a.cx, dy = (double)y - a.cy;
+            const double rho2 = a.den > 0.0 ? (dx * dx + dy * dy) / a.den : 0.0;
+            const double f = 1.0 + a.vignette * rho2;
+            const double g = 1.0 / (f * f);
+            const double V = ((B[i] / 257.0) * a.gain) * g;
+            double Y = V;
+            if (a.noisy) {
+                // d
+                const double Vc = fmin(fmax(V, 0.0), 255.0);
+                const double fi = fmin(floor(Vc), 254.0);
+                const int k = (int)fi;
+                const double sig = sig_s[k] + (sig_s[k + 1] - sig_s[k]) * (Vc - fi);
+                // e
+                const unsigned long long at = key + 4ull * (unsigned long long)((int64_t)y * a.W + x);
+                const unsigned S12 = photo_fields(photo_mix(at)) + photo_fields(photo_mix(at + 1ull)) + photo_fields(photo_mix(at + 2ull));
+                const double z = (double)((int)S12 - 393210) / 65536.0;
+                // f
+                Y = V + sig * z;
+            }
+            // g
+            const unsigned q = (unsigned)rint(fmin(fmax(Y * PhotoPix<D>::scale, 0.0), PhotoPix<D>::hi));
+            // the group's pixels to its first lane; every lane of the wavefront is here
+            unsigned word = q;
+#pragma unroll
+            for (int k = 1; k < PX; ++k) word |= (unsigned)__shfl_down((int)q, k, 64) << (BITS * k);
+            const int x_g = x - (lane & (PX - 1));                         // the group's first pixel
+            D* row = dst + ((int64_t)img * a.H + y) * a.W;
+            const bool whole = x_g + PX <= a.W && (reinterpret_cast<uintptr_t>(row + x_g) & 3u) == 0;
+            if (whole) {
+                if ((lane & (PX - 1)) == 0) *reinterpret_cast<uint32_t*>(row + x) = word;
+            } else if (x < a.W) row[x] = (D)q;
+        }
+    }
+}
+
+namespace {
+
+template <class S>
+void photo_launch_d(int dst_dtype, dim3 grid, size_t lds, hipStream_t st, const PhotoArgs& a) {
+    if (dst_dtype == CCAL_PIX_U16) hipLaunchKernelGGL((k_photo<S, uint16_t>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((k_photo<S, uint8_t>), grid, dim3(256), lds, st, a);
+}
+
+bool finite_nonneg(double v) { return v >= 0.0 && std::isfinite(v); }
+
+}  // namespace
+
+const char* photo_check(const ccal_photo_opts* o, PhotoTables* t) {
+    if (!(o->blur_sigma >= 0.0 && o->blur_sigma <= 16.0 / 3.0)) return "blur_sigma is outside 0 .. 16/3";
+    if (!finite_nonneg(o->vignette)) return "vignette is negative or not finite";
+    if (!finite_nonneg(o->gain)) return "gain is negative or not finite";
+    if (!finite_nonneg(o->noise_read)) return "noise_read is negative or not finite";
+    if (!finite_nonneg(o->noise_shot)) return "noise_shot is negative or not finite";
+    if (o->first_index < 0) return "first_index < 0";
+    const double s = o->blur_sigma;
+    const int r = (int)std::min(16.0, std::ceil(3.0 * s));
+    t->radius = r; t->reserved_ = 0;
+    for (int k = 0; k <= kPhotoMaxR; ++k) t->taps[k] = 0.0;
+    if (r == 0) t->taps[0] = 1.0;
+    else {
+        double w[kPhotoMaxR + 1] = { 1.0 }, tail = 0.0;    // w_0 = 1 as written: -0 / (2 s s) is not a number once 2 s s underflows
+        for (int k = 1; k <= r; ++k) w[k] = std::exp(-(double)(k * k) / (2.0 * s * s));
+        for (int k = 1; k <= r; ++k) tail = tail + w[k];
+        const double norm = w[0] + 2.0 * tail;
+        for (int k = 0; k <= r; ++k) t->taps[k] = w[k] / norm;
+    }
+    for (int g = 0; g < 256; ++g) t->sigma[g] = std::sqrt(o->noise_read * o->noise_read + o->noise_shot * (double)g);
+    return nullptr;
+}
+
+hipError_t photo_enqueue(hipStream_t st, const PhotoTables& tables, const ccal_photo_opts& o, int src_dtype, int dst_dtype, int width, int height,
+                         int n_img, uint64_t stream0, const void* src, void* dst) {
+    if (n_img <= 0) return hipSuccess;
+    PhotoArgs a = {};
+    a.t = tables; a.src = src; a.dst = dst;
+    a.W = width; a.H = height; a.n_img = n_img;
+    a.tiles_x = (width + kPhotoTileW - 1) / kPhotoTileW;
+    a.vignette = o.vignette; a.gain = o.gain;
+    a.cx = (double)(width - 1) / 2.0; a.cy = (double)(height - 1) / 2.0;
+    a.den = a.cx * a.cx + a.cy * a.cy;
+    a.stream0 = stream0;
+    a.noisy = (o.noise_read > 0.0 || o.noise_shot > 0.0) ? 1 : 0;
+    const int tiles_y = (height + kPhotoTileH - 1) / kPhotoTileH;
+    const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)std::min(n_img, 65535));
+    const size_t lds = photo_lds_bytes(tables.radius);
+    if (src_dtype == CCAL_PIX_U16) photo_launch_d<uint16_t>(dst_dtype, grid, lds, st, a);
+    else photo_launch_d<uint8_t>(dst_dtype, grid, lds, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace ccal
+
+using namespace ccal;
+
+extern "C" {
+
+int ccal_photo_set_defaults(ccal_photo_opts* photo) {
+    if (!photo) return CCAL_ERR_INVALID_ARG;
+    photo->blur_sigma = 0.0; photo->vignette = 0.0; photo->gain = 1.0;
+    photo->noise_read = 0.0; photo->noise_shot = 0.0;
+    photo->seed = 0; photo->first_index = 0;
+    return CCAL_OK;
+}
+
+int ccal_photo_tables(const ccal_photo_opts* photo, int32_t* radius_out, double* taps_out, double* sigma_out) {
+    if (!photo || !radius_out || !taps_out || !sigma_out) return CCAL_ERR_INVALID_ARG;
+    PhotoTables t;
+    if (photo_check(photo, &t)) return CCAL_ERR_INVALID_ARG;
+    *radius_out = t.radius;
+    for (int k = 0; k <= kPhotoMaxR; ++k) taps_out[k] = t.taps[k];
+    for (int g = 0; g < 256; ++g) sigma_out[g] = t.sigma[g];
+    return CCAL_OK;
+}
+
+int ccal_photo_apply_dev(ccal_ctx* ctx, int src_dtype, int dst_dtype, int width, int height, int n_img, const void* src_dev, void* dst_dev,
+                         const ccal_photo_opts* photo) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    const BadArg bad{ ctx, "ccal_photo_apply_dev" };
+    if (!photo) return bad("photo is NULL");
+    PhotoTables t;
+    if (const char* what = photo_check(photo, &t)) return bad(what);
+    const GreyBatch in{ src_dtype, width, height, n_img, src_dev, true }, out{ dst_dtype, width, height, n_img, dst_dev, true };
+    if (const char* what = in.bad()) return bad(src_dtype != CCAL_PIX_U8 && src_dtype != CCAL_PIX_U16 ? "src_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16" : what);
+    if (const char* what = out.bad()) return bad(dst_dtype != CCAL_PIX_U8 && dst_dtype != CCAL_PIX_U16 ? "dst_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16" : what);
+    if (n_img == 0) return CCAL_OK;
+    if (!src_dev) return bad("src_dev is NULL");
+    if (!dst_dev) return bad("dst_dev is NULL");
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_dev), s1 = s0 + in.img_bytes() * (size_t)n_img;
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_dev), d1 = d0 + out.img_bytes() * (size_t)n_img;
+    if (s0 < d1 && d0 < s1) return bad("src_dev and dst_dev overlap");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, photo_enqueue(ctx->stream, t, *photo, src_dtype, dst_dtype, width, height, n_img, photo->seed + (uint64_t)photo->first_index,
+                               src_dev, dst_dev));
+    return CCAL_OK;
+    CCAL_API_CATCH(ctx)
+}
+
+}  // extern "C"

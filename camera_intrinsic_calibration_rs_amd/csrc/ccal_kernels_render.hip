@@ -18,6 +18,7 @@
 #include "ccal_call.hpp"
 #include "ccal_device.hpp"
 #include "ccal_model_inverse.hpp"
+#include "ccal_photo.hpp"
 
 namespace ccal {
 
@@ -180,8 +181,11 @@ void pose_to_rt(const double* p, double* out) {
     for (int j = 0; j < 3; ++j) out[9 + j] = R[j] * p[3] + R[3 + j] * p[4] + R[6 + j] * p[5];
 }
 
+// with_photo: the ideal images are rendered at CCAL_PIX_U16 chunk by chunk into a slice of the block and go through the photometric
+// stage (ccal_kernels_photo.hip) into the destination; without it the render writes the destination itself, as it always did
 int render_call(ccal_ctx* ctx, const char* where, bool on_device, int model, const double* params, int dtype, int width, int height, int n_img,
-                const double* poses, const ccal_render_target* tg, const ccal_render_opts* o, void* out) {
+                const double* poses, const ccal_render_target* tg, const ccal_render_opts* o, void* out, bool with_photo = false,
+                const ccal_photo_opts* photo = nullptr) {
     const BadArg bad{ ctx, where };
     if (!params) return bad("params is NULL");
     if (!tg) return bad("target is NULL");
@@ -219,6 +223,11 @@ int render_call(ccal_ctx* ctx, const char* where, bool on_device, int model, con
     if (o->supersample < 1 || o->supersample > kRenderMaxSS) return bad("supersample outside 1 .. 8");
     if (!std::isfinite(o->black) || !std::isfinite(o->white) || !std::isfinite(o->background)) return bad("black, white or background is not finite");
     if (!(o->margin >= 0.0)) return bad("margin is negative or not a number");
+    PhotoTables tables;
+    if (with_photo) {
+        if (!photo) return bad("photo is NULL");
+        if (const char* what = photo_check(photo, &tables)) return bad(what);
+    }
     if (n_img == 0) return CCAL_OK;
     if (!poses) return bad("poses is NULL");
     if (!out) return bad("the output pointer is NULL");
@@ -230,14 +239,18 @@ int render_call(ccal_ctx* ctx, const char* where, bool on_device, int model, con
     std::vector<double> rt(12 * (size_t)n_img);
     for (int k = 0; k < n_img; ++k) pose_to_rt(poses + 6 * (size_t)k, rt.data() + 12 * (size_t)k);
 
-    // the host form goes chunk by chunk through one staged block of images; the device form writes where the caller says
+    // the host form goes chunk by chunk through one staged block of images; the device form writes where the caller says.  With the
+    // photometric stage both forms go chunk by chunk through one block of u16 ideal images, whose bytes the limit then counts
     const size_t img_bytes = (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height;
+    const size_t ideal_bytes = 2 * (size_t)width * (size_t)height;
     const size_t limit = test_chunk_bytes("CCAL_TEST_RENDER_CHUNK_BYTES", kRenderChunkBytes);
-    const size_t per = on_device ? (size_t)n_img : std::min<size_t>((size_t)n_img, std::max<size_t>(limit / img_bytes, 1));
+    const size_t per = on_device && !with_photo ? (size_t)n_img
+                                                : std::min<size_t>((size_t)n_img, std::max<size_t>(limit / (with_photo ? ideal_bytes : img_bytes), 1));
     CallBlock blk(ctx);
     const auto s_pose = blk.add<double>(12 * (size_t)n_img);
     const auto s_codes = blk.add<unsigned long long>((size_t)n_tags);
     const auto s_img = blk.add<char>(on_device ? 0 : img_bytes * per);
+    const auto s_ideal = blk.add<char>(with_photo ? ideal_bytes * per : 0);
     if (!blk.alloc()) return blk.finish(where);
     blk.upload(s_pose, rt.data(), rt.size());
     if (n_tags) blk.upload(s_codes, tg->codes + tg->first_id, (size_t)n_tags);
@@ -245,8 +258,12 @@ int render_call(ccal_ctx* ctx, const char* where, bool on_device, int model, con
     for (size_t k0 = 0; k0 < (size_t)n_img && blk.ok(); k0 += per) {
         const size_t m = std::min(per, (size_t)n_img - k0);
         a.pose = blk.at(s_pose) + 12 * k0; a.n_img = (int32_t)m;
-        a.out = on_device ? static_cast<void*>(static_cast<char*>(out) + k0 * img_bytes) : static_cast<void*>(blk.at(s_img));
-        blk.note(render_enqueue(model, tg->kind, dtype, ctx->stream, a));
+        void* const dst = on_device ? static_cast<void*>(static_cast<char*>(out) + k0 * img_bytes) : static_cast<void*>(blk.at(s_img));
+        a.out = with_photo ? static_cast<void*>(blk.at(s_ideal)) : dst;
+        blk.note(render_enqueue(model, tg->kind, with_photo ? (int)CCAL_PIX_U16 : dtype, ctx->stream, a));
+        if (with_photo && blk.ok())                      // an image's noise index is its index in the call
+            blk.note(photo_enqueue(ctx->stream, tables, *photo, CCAL_PIX_U16, dtype, width, height, (int)m,
+                                   photo->seed + (uint64_t)photo->first_index + (uint64_t)k0, a.out, dst));
         if (!on_device) blk.download(static_cast<char*>(out) + k0 * img_bytes, blk.at(s_img), img_bytes * m);
     }                                                    // the next chunk's launch follows this copy on the same stream
     return blk.finish(where);
@@ -280,6 +297,24 @@ int ccal_render_targets_dev(ccal_ctx* ctx, int model, const double* params, int 
     if (!ctx) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
     return render_call(ctx, "ccal_render_targets_dev", true, model, params, dtype, width, height, n_img, poses, target, opts, images_out_dev);
+    CCAL_API_CATCH(ctx)
+}
+
+int ccal_render_photo_targets(ccal_ctx* ctx, int model, const double* params, int dtype, int width, int height, int n_img, const double* poses,
+                              const ccal_render_target* target, const ccal_render_opts* opts, const ccal_photo_opts* photo, void* images_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    return render_call(ctx, "ccal_render_photo_targets", false, model, params, dtype, width, height, n_img, poses, target, opts, images_out, true, photo);
+    CCAL_API_CATCH(ctx)
+}
+
+int ccal_render_photo_targets_dev(ccal_ctx* ctx, int model, const double* params, int dtype, int width, int height, int n_img, const double* poses,
+                                  const ccal_render_target* target, const ccal_render_opts* opts, const ccal_photo_opts* photo,
+                                  void* images_out_dev) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    return render_call(ctx, "ccal_render_photo_targets_dev", true, model, params, dtype, width, height, n_img, poses, target, opts, images_out_dev, true,
+                       photo);
     CCAL_API_CATCH(ctx)
 }
 

@@ -592,41 +592,58 @@ class Context:
                                    max_iterations, eps)
 
     # -- rendering calibration targets through the camera models (ccal_render_targets_batch, ccal_kernels_render.hip) ----------------
-    def _render(self, fn, where, out_ptr, model, params, dtype, width, height, poses, target, supersample, black, white, background,
-                margin):
+    def _render(self, where, out_ptr, model, params, dtype, width, height, poses, target, supersample, black, white, background,
+                margin, photo=None):
+        """where: ccal_render_targets_batch / _dev; with photo the call is its ccal_render_photo_targets form."""
+        if photo is not None:
+            where = "ccal_render_photo_targets" + ("_dev" if where.endswith("_dev") else "")
         poses = _f64(poses)
         if poses.ndim != 2 or poses.shape[1] != 6:
             raise ValueError(f"{where}: poses is an [n, 6] array of rvec, tvec")
         o = render_opts(target, supersample, black, white, background, margin, lib=self.lib)
-        rc = fn(self.handle, int(model), _dp(_f64(params)), int(dtype), int(width), int(height), poses.shape[0], _dp(poses),
-                C.byref(target), C.byref(o), C.c_void_p(out_ptr))
+        head = (self.handle, int(model), _dp(_f64(params)), int(dtype), int(width), int(height), poses.shape[0], _dp(poses),
+                C.byref(target), C.byref(o))
+        tail = (C.c_void_p(out_ptr),) if photo is None else (C.byref(photo_opts(photo)), C.c_void_p(out_ptr))
+        rc = getattr(self.lib, where)(*head, *tail)
         if rc != _ffi.OK:
             raise CcalError(rc, where, self.last_error())
 
     def render_targets_batch(self, model: int, params, width: int, height: int, poses, target: "_ffi.RenderTarget", dtype=np.uint8,
                              supersample: Optional[int] = None, black: Optional[float] = None, white: Optional[float] = None,
-                             background: Optional[float] = None, margin: Optional[float] = None) -> np.ndarray:
+                             background: Optional[float] = None, margin: Optional[float] = None, photo=None) -> np.ndarray:
         """Grey images [n][height][width] (uint8 or uint16) of `target` (checkerboard_target / aprilgrid_target) as the camera
         (model, params) sees it at poses [n, 6] (rvec, tvec: board -> camera), by the rule stated at ccal_render_targets_batch in
         include/ccal.h: every pixel the mean of supersample x supersample rays.  An option left at None takes
-        ccal_render_set_defaults' value (4; 40, 215, 0 grey levels; a margin of one square or one tag pitch)."""
+        ccal_render_set_defaults' value (4; 40, 215, 0 grey levels; a margin of one square or one tag pitch).  photo (an
+        api.PhotoOpts or a _ffi.PhotoOpts; None: ideal images, the call above): the ideal images at uint16 go through the
+        photometric stage - lens blur, vignetting, exposure, sensor noise - on the device (ccal_render_photo_targets)."""
         dt = np.dtype(dtype)
         if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
             raise ValueError("render_targets_batch: uint8 or uint16 images")
         n = _f64(poses).shape[0] if np.ndim(poses) == 2 else 0
         out = np.empty((n, max(int(height), 0), max(int(width), 0)), dtype=dt)
-        self._render(self.lib.ccal_render_targets_batch, "ccal_render_targets_batch", out.ctypes.data if out.size else 0, model, params,
-                     _ffi.PIX_U8 if dt == np.uint8 else _ffi.PIX_U16, width, height, poses, target, supersample, black, white,
-                     background, margin)
+        self._render("ccal_render_targets_batch", out.ctypes.data if out.size else 0, model, params, _ffi.PIX_U8 if dt == np.uint8 else _ffi.PIX_U16, width,
+                     height, poses, target, supersample, black, white, background, margin, photo)
         return out
 
     def render_targets_dev(self, out_ptr: int, model: int, params, dtype: int, width: int, height: int, poses, target: "_ffi.RenderTarget",
                            supersample: Optional[int] = None, black: Optional[float] = None, white: Optional[float] = None,
-                           background: Optional[float] = None, margin: Optional[float] = None) -> None:
+                           background: Optional[float] = None, margin: Optional[float] = None, photo=None) -> None:
         """render_targets_batch into a device block (a device pointer to [n][height][width] of dtype _ffi.PIX_U8 / PIX_U16) on the
         context's stream: the block goes straight into detect_checkerboards_dev, detect_tags_dev or UndistortMap.remap_dev."""
-        self._render(self.lib.ccal_render_targets_dev, "ccal_render_targets_dev", out_ptr, model, params, dtype, width, height, poses,
-                     target, supersample, black, white, background, margin)
+        self._render("ccal_render_targets_dev", out_ptr, model, params, dtype, width, height, poses, target, supersample, black, white, background, margin,
+                     photo)
+
+    # -- the photometric stage (ccal_photo_apply_dev, ccal_kernels_photo.hip) -------------------------------------------------------
+    def photo_apply_dev(self, src_ptr: int, dst_ptr: int, src_dtype: int, dst_dtype: int, width: int, height: int, n_img: int,
+                        photo) -> None:
+        """Lens blur, vignetting, exposure and sensor noise (photo: an api.PhotoOpts or a _ffi.PhotoOpts) from the device block
+        src_ptr to the device block dst_ptr, [n_img][height][width] of _ffi.PIX_U8 / PIX_U16 each, by the rule stated at
+        ccal_photo_apply_dev in include/ccal.h.  Only enqueued on the context's stream; the blocks must not overlap."""
+        rc = self.lib.ccal_photo_apply_dev(self.handle, int(src_dtype), int(dst_dtype), int(width), int(height), int(n_img),
+                                           C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.byref(photo_opts(photo)))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_photo_apply_dev", self.last_error())
 
     def close(self):
         if getattr(self, "handle", None):
@@ -702,6 +719,25 @@ def render_opts(target: "_ffi.RenderTarget", supersample=None, black=None, white
         if v is not None:
             setattr(o, name, float(v))
     return o
+
+
+def photo_opts(photo) -> "_ffi.PhotoOpts":
+    """The ccal_photo_opts of `photo`: a _ffi.PhotoOpts as it is, else anything with the seven fields (api.PhotoOpts)."""
+    if isinstance(photo, _ffi.PhotoOpts):
+        return photo
+    return _ffi.PhotoOpts(blur_sigma=float(photo.blur_sigma), vignette=float(photo.vignette), gain=float(photo.gain),
+                          noise_read=float(photo.noise_read), noise_shot=float(photo.noise_shot),
+                          seed=int(photo.seed) & 0xFFFFFFFFFFFFFFFF, first_index=int(photo.first_index))
+
+
+def photo_tables(photo, lib=None):
+    """(radius, taps f64 [17], sigma f64 [256]) of ccal_photo_tables: exactly what the photometric kernel uses for `photo`.  Host
+    only.  ValueError when an option is out of range."""
+    radius, taps, sigma = C.c_int32(0), np.zeros(_ffi.PHOTO_MAX_RADIUS + 1), np.zeros(256)
+    rc = (lib or _ffi.load()).ccal_photo_tables(C.byref(photo_opts(photo)), C.byref(radius), _dp(taps), _dp(sigma))
+    if rc != _ffi.OK:
+        raise ValueError("photo_tables: an option is out of range (include/ccal.h, the photometric stage)")
+    return int(radius.value), taps, sigma
 
 
 def _per_image(offs, n_img: int, arrays):

@@ -1052,8 +1052,9 @@ int ccal_detect_checkerboards_dev(ccal_ctx* ctx, int dtype, int width, int heigh
  *   sheet is W.  Tag (r, c)'s outer corners are (x, y), (x + s, y), (x + s, y - s), (x, y - s) with x = c pitch, y = -r pitch,
  *   s = tag_size: the order of the decoder's corners_out.
  * Pixel: lum = ((n_B black + n_W white) + n_G background) / (s s); the pixel is rint(lum) for u8 and rint(lum 257) for u16 (round
- * half to even), clamped to the type.  The plane is two-sided: a pose that shows the back shows the mirror image.  No blur, noise
- * or vignetting.
+ * half to even), clamped to the type.  The plane is two-sided: a pose that shows the back shows the mirror image.  These are ideal
+ * images; lens blur, vignetting, exposure and sensor noise are the photometric stage's, stated in the next section
+ * (ccal_render_photo_targets_* renders and degrades in one call).
  * An image is a pure function of the model, the target, the options and its pose: image k of a call equals the same pose rendered
  * alone, whatever the batch and however the library cuts it into chunks, and runs repeat to the bit.  No atomics.
  *
@@ -1089,6 +1090,72 @@ int ccal_render_targets_batch(ccal_ctx* ctx, int model, const double* params, in
 int ccal_render_targets_dev(ccal_ctx* ctx, int model, const double* params, int dtype, int width, int height, int n_img,
                             const double* poses /* [n_img][6] */, const ccal_render_target* target, const ccal_render_opts* opts,
                             void* images_out_dev /* [n_img][height][width] */);
+
+/* ---- the photometric stage: lens blur, vignetting, exposure and sensor noise ------------------------------------------------------
+ * From ideal irradiance to pixels: what stands between the renderer above and the frames a camera delivers, so that a robustness
+ * question of the image stages (what half_win, nms_radius, rel_threshold, min_contrast or offset tolerate at a given defocus and
+ * noise level) is answered without the images leaving the device.  tests/photo_ref.py is the numpy yardstick of the rule below and
+ * the device is held to it to the bit: the unit is compiled without fused multiply-adds; all arithmetic is IEEE f64 + - * /, floor,
+ * rint, min, max, every operation rounded on its own, in the order written; the integer parts are u64 modulo 2^64.
+ *
+ * Options: ccal_photo_opts.  blur_sigma in 0 .. 16/3 px (a Gaussian PSF; 0: none); vignette v >= 0 (the gain at the corners is
+ * 1 / (1 + v)^2; 0: none); gain finite, >= 0 (exposure; 1: none); noise_read >= 0 in 8-bit grey levels; noise_shot >= 0, variance
+ * per grey level; seed; first_index >= 0: the noise stream of image k of a call is seed + first_index + k.
+ * ccal_photo_set_defaults switches everything off: 0, 0, 1, 0, 0, 0, 0.
+ *
+ * Tables, made on the host (ccal_photo_tables returns exactly what the kernel uses; host only, no context):
+ *   radius  r = min(16, ceil(3 blur_sigma)).
+ *   taps    w_0 = 1, w_k = exp(-k k / (2 sigma sigma)) (0 where 2 sigma sigma underflows), norm = w_0 + 2 (w_1 + ... + w_r) with the
+ *           inner sum in ascending k, t_k = w_k / norm, k = 0 .. r; for r = 0, t_0 = 1.  taps_out[17]: the entries above r are 0.
+ *   sigma   T[g] = sqrt(noise_read noise_read + noise_shot g), g = 0 .. 255.
+ *
+ * Per output pixel (x, y) of image k of W x H pixels.  I is the ideal image on the 16-bit scale: a u16 source as it is, 257 p for a
+ * u8 source.
+ *   a  H(x, y) = the sum over j = -r .. r, ascending, of t_|j| I(clamp(x + j, 0, W - 1), y): acc = 0.0, then acc = acc + t I.
+ *   b  B(x, y) = the same sum over H(x, clamp(y + j, 0, H - 1)).  For r = 0, B = I.
+ *   c  V = ((B / 257) gain) g with g = 1 / ((1 + v rho2) (1 + v rho2)), rho2 = (dx dx + dy dy) / (cx cx + cy cy), cx = (W - 1) / 2,
+ *      cy = (H - 1) / 2, dx = x - cx, dy = y - cy; for a 1 x 1 image rho2 = 0.
+ *   d  Vc = min(max(V, 0), 255), i = min(floor(Vc), 254), sig = T[i] + (T[i + 1] - T[i]) (Vc - i).
+ *   e  z = (S - 393210) / 65536, S = the integer sum of the twelve 16-bit fields of w_0, w_1, w_2; w_j = mix(key + 4 (y W + x) + j),
+ *      key = mix(seed + first_index + k); mix(a) is splitmix64's finaliser: a ^= a >> 30, a *= 0xBF58476D1CE4E5B9, a ^= a >> 27,
+ *      a *= 0x94D049BB133111EB, a ^= a >> 31.  z is an Irwin-Hall draw of unit variance with its tails cut at +-6.
+ *   f  Y = V + sig z.
+ *   g  u8: rint(min(max(Y, 0), 255)); u16: rint(min(max(Y 257, 0), 65535)).
+ * Consequences: with every effect off and u16 output the result is the source (of ccal_render_photo_targets_*: the images of
+ * ccal_render_targets_* at CCAL_PIX_U16) bit for bit; image k of a call equals image 0 of a call with first_index + k, in any batch,
+ * under any chunking, from run to run.  No atomics.
+ *
+ * ccal_photo_apply_dev: src_dev [n_img][height][width] of src_dtype to dst_dev of dst_dtype, both device pointers, CCAL_PIX_U8 /
+ * CCAL_PIX_U16 each.  It only enqueues on the context's stream, like ccal_remap_dev, and stages nothing: the tables travel in the
+ * kernel's arguments.  The two blocks must not overlap.
+ * ccal_render_photo_targets / _dev: the arguments of ccal_render_targets_batch / _dev and the photo options.  The ideal images are
+ * rendered at CCAL_PIX_U16 chunk by chunk into the call's own block and go through the stage into images_out (a host array) /
+ * images_out_dev; an image's noise index is its index in the call.  Both return when the images are written.
+ * CCAL_ERR_INVALID_ARG with a message that names the argument, nothing launched or written: photo NULL; blur_sigma outside
+ * 0 .. 16/3 or NaN; vignette, noise_read, noise_shot or gain negative or not finite; first_index < 0; a dtype other than the two,
+ * width, height <= 0, n_img < 0, more than 2^31 - 1 pixels in an image; with n_img > 0 a NULL block or blocks that overlap; and
+ * what ccal_render_targets_* refuses.  n_img == 0 is valid. */
+#define CCAL_PHOTO_MAX_RADIUS 16
+typedef struct {
+    double blur_sigma;                     /* px, 0 .. 16/3: Gaussian PSF; 0 = none */
+    double vignette;                       /* v >= 0: corner gain 1 / (1 + v)^2; 0 = none */
+    double gain;                           /* exposure, finite, >= 0; 1 = none */
+    double noise_read;                     /* grey levels (8-bit scale), >= 0 */
+    double noise_shot;                     /* variance per grey level, >= 0 */
+    uint64_t seed;
+    int64_t first_index;                   /* the noise stream of image k is seed + first_index + k */
+} ccal_photo_opts;
+int ccal_photo_set_defaults(ccal_photo_opts* photo);
+int ccal_photo_tables(const ccal_photo_opts* photo, int32_t* radius_out, double* taps_out /* [17] */, double* sigma_out /* [256] */);
+int ccal_photo_apply_dev(ccal_ctx* ctx, int src_dtype, int dst_dtype, int width, int height, int n_img, const void* src_dev,
+                         void* dst_dev, const ccal_photo_opts* photo);
+int ccal_render_photo_targets(ccal_ctx* ctx, int model, const double* params, int dtype, int width, int height, int n_img,
+                              const double* poses /* [n_img][6] */, const ccal_render_target* target, const ccal_render_opts* opts,
+                              const ccal_photo_opts* photo, void* images_out /* [n_img][height][width] */);
+int ccal_render_photo_targets_dev(ccal_ctx* ctx, int model, const double* params, int dtype, int width, int height, int n_img,
+                                  const double* poses /* [n_img][6] */, const ccal_render_target* target,
+                                  const ccal_render_opts* opts, const ccal_photo_opts* photo,
+                                  void* images_out_dev /* [n_img][height][width] */);
 
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
