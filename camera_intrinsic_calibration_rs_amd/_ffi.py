@@ -120,6 +120,13 @@ class PhotoOpts(C.Structure):             # ccal_photo_opts: the photometric sta
 
 PHOTO_MAX_RADIUS = 16                     # CCAL_PHOTO_MAX_RADIUS
 
+
+class NormalizeOpts(C.Structure):         # ccal_normalize_opts: local contrast normalisation; ccal_normalize_set_defaults: 16, 0, 4.0, 64.0
+    _fields_ = [("radius", C.c_int32), ("reserved_", C.c_int32), ("min_sigma", C.c_double), ("amp", C.c_double)]
+
+
+NORMALIZE_MAX_RADIUS = 32                 # CCAL_NORMALIZE_MAX_RADIUS
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 LIB_PATH = os.environ.get("CCAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libccal_hip.so")
@@ -270,6 +277,9 @@ SYMBOLS = [
                                             C.POINTER(RenderOpts), C.POINTER(PhotoOpts), _vp]),
     ("ccal_render_photo_targets_dev", C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(RenderTarget),
                                                 C.POINTER(RenderOpts), C.POINTER(PhotoOpts), _vp]),
+    # local contrast normalisation ahead of the detectors
+    ("ccal_normalize_set_defaults", C.c_int, [C.POINTER(NormalizeOpts)]),
+    ("ccal_normalize_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(NormalizeOpts)]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

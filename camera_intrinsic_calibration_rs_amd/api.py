@@ -1293,6 +1293,17 @@ class PhotoOpts:
     first_index: int = 0
 
 
+@dataclasses.dataclass
+class NormalizeOpts:
+    """Local contrast normalisation ahead of the detectors (ccal_normalize_opts in include/ccal.h states the rule;
+    Context.normalize_dev): every pixel minus the mean of the (2 radius + 1)^2 window around it (radius 1 .. 32) over the window's
+    standard deviation, which is held above min_sigma grey levels (8-bit scale, 0 .. 255), times `amp` grey levels, around 128.
+    For frames whose contrast falls towards the edge or that are under-exposed; on a clean frame it costs accuracy (README)."""
+    radius: int = 16
+    min_sigma: float = 4.0
+    amp: float = 64.0
+
+
 def render_checkerboard(model: GenericModel, poses, pattern: Tuple[int, int], square_size: float, dtype=np.uint8, supersample: int = 4,
                         black: float = 40, white: float = 215, background: float = 0, margin: Optional[float] = None,
                         ctx: Optional[Context] = None, photo: Optional[PhotoOpts] = None) -> np.ndarray:

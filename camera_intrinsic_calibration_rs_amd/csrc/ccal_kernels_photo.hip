@@ -11,15 +11,16 @@
 //            reads the pixel from the source.
 //   pixel    steps c to g in the lane that holds B(x, y).  The noise is counter-based: three splitmix64 finalisers per pixel, keyed by
 //            the image's stream and the pixel's index - no state, no atomics, no order.
-//   stores   the lanes of a group of 4 (u8) or 2 (u16) adjacent pixels hand their pixels to the group's first lane, which stores them
-//            as one dword; a group that ends at the image's right edge, or whose first pixel is not on a dword boundary (rows of a
-//            width that is no multiple of 4 bytes), stores pixel by pixel: no lane ever writes a byte outside the image.
+//   stores   store_pixel_group (ccal_pix_store.hpp): the lanes of a group of 4 (u8) or 2 (u16) adjacent pixels hand their pixels to
+//            the group's first lane, which stores them as one dword; a group that ends at the image's right edge, or whose first
+//            pixel is not on a dword boundary, stores pixel by pixel: no lane ever writes a byte outside the image.
 // This unit is compiled with -ffp-contract=off (csrc/Makefile): every product and sum rounds on its own, as tests/photo_ref.py, the
 // numpy yardstick, does; the device is held to it bit for bit.
 #include <algorithm>
 #include <cmath>
 #include "ccal_call.hpp"
 #include "ccal_photo.hpp"
+#include "ccal_pix_store.hpp"
 
 namespace ccal {
 
@@ -60,7 +61,6 @@ __host__ __device__ inline size_t photo_lds_bytes(int r) {
 
 template <class S, class D>
 __global__ __launch_bounds__(256) void k_photo(const PhotoArgs a) {
-    constexpr int PX = 4 / (int)sizeof(D), BITS = 8 * (int)sizeof(D);
     extern __shared__ __attribute__((aligned(16))) double lds_photo[];
     double* sig_s = lds_photo;                                       // [256]
     double* tap_s = lds_photo + 256;                                 // [17], 24 reserved
@@ -144,15 +144,7 @@ __global__ __launch_bounds__(256) void k_photo(const PhotoArgs a) {
             // g
             const unsigned q = (unsigned)rint(fmin(fmax(Y * PhotoPix<D>::scale, 0.0), PhotoPix<D>::hi));
             // the group's pixels to its first lane; every lane of the wavefront is here
-            unsigned word = q;
-#pragma unroll
-            for (int k = 1; k < PX; ++k) word |= (unsigned)__shfl_down((int)q, k, 64) << (BITS * k);
-            const int x_g = x - (lane & (PX - 1));                         // the group's first pixel
-            D* row = dst + ((int64_t)img * a.H + y) * a.W;
-            const bool whole = x_g + PX <= a.W && (reinterpret_cast<uintptr_t>(row + x_g) & 3u) == 0;
-            if (whole) {
-                if ((lane & (PX - 1)) == 0) *reinterpret_cast<uint32_t*>(row + x) = word;
-            } else if (x < a.W) row[x] = (D)q;
+            store_pixel_group<D>(dst + ((int64_t)img * a.H + y) * a.W, x, lane, a.W, q);
         }
     }
 }

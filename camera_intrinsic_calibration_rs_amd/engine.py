@@ -645,6 +645,19 @@ class Context:
         if rc != _ffi.OK:
             raise CcalError(rc, "ccal_photo_apply_dev", self.last_error())
 
+    # -- local contrast normalisation (ccal_normalize_dev, ccal_kernels_normalize.hip) ------------------------------------------------
+    def normalize_dev(self, src_ptr: int, dst_ptr: int, src_dtype: int, dst_dtype: int, width: int, height: int, n_img: int,
+                      norm=None) -> None:
+        """Every pixel's distance from the mean of the (2 r + 1)^2 window around it in units of the window's standard deviation
+        (norm: an api.NormalizeOpts or a _ffi.NormalizeOpts; None: ccal_normalize_set_defaults) from the device block src_ptr to
+        the device block dst_ptr, [n_img][height][width] of _ffi.PIX_U8 / PIX_U16 each, by the rule stated at ccal_normalize_dev in
+        include/ccal.h; dst_ptr then goes into detect_checkerboards_dev / detect_tags_dev.  Only enqueued on the context's stream;
+        the blocks must not overlap."""
+        rc = self.lib.ccal_normalize_dev(self.handle, int(src_dtype), int(dst_dtype), int(width), int(height), int(n_img),
+                                         C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.byref(normalize_opts(norm, lib=self.lib)))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_normalize_dev", self.last_error())
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first
@@ -738,6 +751,20 @@ def photo_tables(photo, lib=None):
     if rc != _ffi.OK:
         raise ValueError("photo_tables: an option is out of range (include/ccal.h, the photometric stage)")
     return int(radius.value), taps, sigma
+
+
+def normalize_opts(norm=None, lib=None) -> "_ffi.NormalizeOpts":
+    """The ccal_normalize_opts of `norm`: a _ffi.NormalizeOpts as it is; None: ccal_normalize_set_defaults; else anything with the
+    fields radius, min_sigma and amp (api.NormalizeOpts)."""
+    if isinstance(norm, _ffi.NormalizeOpts):
+        return norm
+    o = _ffi.NormalizeOpts()
+    rc = (lib or _ffi.load()).ccal_normalize_set_defaults(C.byref(o))
+    if rc != _ffi.OK:
+        raise CcalError(rc, "ccal_normalize_set_defaults")
+    if norm is not None:
+        o.radius, o.min_sigma, o.amp = int(norm.radius), float(norm.min_sigma), float(norm.amp)
+    return o
 
 
 def _per_image(offs, n_img: int, arrays):

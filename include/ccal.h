@@ -1157,6 +1157,50 @@ int ccal_render_photo_targets_dev(ccal_ctx* ctx, int model, const double* params
                                   const ccal_render_opts* opts, const ccal_photo_opts* photo,
                                   void* images_out_dev /* [n_img][height][width] */);
 
+/* ---- local contrast normalisation: frames ahead of the detectors ----------------------------------------------------------------
+ * The saddle detector keeps candidates above rel_threshold times the strongest response of the whole image, and the proposer's and
+ * the decoder's min_contrast are absolute grey levels: a frame whose contrast falls towards the edge (vignetting) or that is
+ * under-exposed loses corners and tags where a fisheye lens has its information.  This stage maps every pixel to its distance from
+ * the mean of the (2 r + 1)^2 window around it in units of the window's standard deviation, device block to device block; the result
+ * feeds the _dev calls above as any frame does.  It is for frames that need it, not a default: on a clean frame it costs accuracy
+ * (README, EXPERIMENTS.md).  tests/normalize_ref.py is the numpy yardstick of the rule below and the device is held to it to the
+ * bit: the sums, the variance term and its square root are exact integers (u64 / i64 suffice: the largest intermediate is
+ * 4225^2 65535^2 < 2^63), the last two steps are IEEE f64, every operation rounded on its own (the unit is compiled without fused
+ * multiply-adds).
+ *
+ * Options: ccal_normalize_opts.  radius r in 1 .. 32: the window is (2 r + 1)^2 pixels, N its pixel count; min_sigma in 0 .. 255, in
+ * 8-bit grey levels: the noise floor, so that flat regions are not blown up; amp finite, >= 0: output grey levels (8-bit scale) per
+ * local standard deviation.  ccal_normalize_set_defaults: 16, 0, 4.0, 64.0 - a window half black, half white maps to 64 and 192.
+ *
+ * Per output pixel (x, y) of image k of W x H pixels.  I is the source on the 16-bit scale: a u16 source as it is, 257 p for a u8
+ * source.
+ *   a  S1 = the sum of I(clamp(x + i, 0, W - 1), clamp(y + j, 0, H - 1)) over i, j = -r .. r; S2 = the same sum of I I.
+ *   b  v = N S2 - S1 S1; s0 = the largest integer with s0 s0 <= v; F = max(1, rint(257 min_sigma)); s = max(s0, N F).
+ *   c  d = N I(x, y) - S1.
+ *   d  q = (double)d / (double)s; Y = 128.0 + amp q.
+ *   e  u8: rint(min(max(Y, 0), 255)); u16: rint(min(max(Y 257, 0), 65535)).
+ * Consequences: a constant image gives 128 (u8) or 32896 (u16) everywhere; a u16 source equal to 257 times a u8 source gives the
+ * same output; image k does not depend on its batch; results are equal from run to run.  No atomics.  Because the sums are
+ * integers, the order of summation is free - the kernel keeps running sums down a column - and that latitude is deliberate.
+ *
+ * ccal_normalize_dev: src_dev [n_img][height][width] of src_dtype to dst_dev of dst_dtype, both device pointers, CCAL_PIX_U8 /
+ * CCAL_PIX_U16 each.  It only enqueues on the context's stream, like ccal_photo_apply_dev, allocates and stages nothing.  The two
+ * blocks must not overlap.  There is no host-pointer form.
+ * CCAL_ERR_INVALID_ARG with a message that names the argument, nothing launched or written: norm NULL; radius outside 1 .. 32;
+ * min_sigma outside 0 .. 255 or NaN; amp negative or not finite; a dtype other than the two, width, height <= 0, n_img < 0, more
+ * than 2^31 - 1 pixels in an image; with n_img > 0 a NULL block or blocks that overlap.  n_img == 0 is valid.
+ * ccal_normalize_set_defaults is host only and needs no context. */
+#define CCAL_NORMALIZE_MAX_RADIUS 32
+typedef struct {
+    int32_t radius;                        /* r in 1 .. 32: a window of (2 r + 1)^2 pixels */
+    int32_t reserved_;
+    double min_sigma;                      /* grey levels (8-bit scale), 0 .. 255: the floor of the local standard deviation */
+    double amp;                            /* output grey levels (8-bit scale) per local standard deviation; finite, >= 0 */
+} ccal_normalize_opts;
+int ccal_normalize_set_defaults(ccal_normalize_opts* norm);
+int ccal_normalize_dev(ccal_ctx* ctx, int src_dtype, int dst_dtype, int width, int height, int n_img, const void* src_dev,
+                       void* dst_dev, const ccal_normalize_opts* norm);
+
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
                              double* err_out /* [n_corners] Euclidean px error */);
