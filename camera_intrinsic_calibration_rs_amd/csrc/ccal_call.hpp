@@ -8,12 +8,14 @@
 //              finish() reports a damaged one
 //   BadArg     the way out of an entry point on a bad argument, with the call's name in the message
 //   check_offsets  the argument check of a batched call's CSR offsets, with the call's name in the message
-//   GreyBatch  the image arguments of the image stages' calls: their check, an image's bytes, the device pointer to a chunk's images
+//   GreyBatch  the image arguments of the image stages' calls: their check (its messages, and a source / destination pair's check:
+//              ccal_image_plan.hpp), an image's bytes, the device pointer to a chunk's images
 //   test_chunk_bytes  the tests' way to make those calls cut a small batch into chunks
 // Host only; for the translation units of the one-shot entry points ("One-shot calls").
 #pragma once
 #include <cstdio>
 #include <cstdlib>
+#include "ccal_image_plan.hpp"
 #include "ccal_internal.hpp"
 #include "ccal_plan.hpp"
 
@@ -135,13 +137,8 @@ struct GreyBatch {
     const void* images;
     bool on_device;
     // the message of the first argument out of range, or nullptr (images == NULL is the caller's check: it comes after n_img == 0)
-    const char* bad() const {
-        if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return "dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16";
-        if (width <= 0 || height <= 0 || n_img < 0) return "a size is not positive";
-        if ((int64_t)width * height > (int64_t)INT32_MAX) return "more than 2^31 - 1 pixels in an image";
-        return nullptr;
-    }
-    size_t img_bytes() const { return (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height; }
+    const char* bad() const { return grey_batch_bad(dtype, width, height, n_img); }
+    size_t img_bytes() const { return grey_image_bytes(dtype, width, height); }
     size_t staged_bytes(size_t m) const { return on_device ? 0 : img_bytes() * m; }       // room in the call's block for m images
     // the device pointer to the images k0 .. k0 + m - 1: where they are, or slice s of the block, to which they are uploaded
     const void* chunk(CallBlock& blk, Slice<char> s, size_t k0, size_t m) const {

@@ -1,11 +1,12 @@
 // What the kernels of the image stages share (ccal_kernels_detect / corners / quads / tags / tagchain / board.hip): the f64 bilinear sample,
 // the row-to-image search over CSR offsets and an image's clamped span of them, the hand-off between lanes of one wavefront and the wavefront's int32 scan.  Header only,
 // every function forced inline: the code follows the flags of the unit that includes it (-ffp-contract=off for quads, tags and board, fast
-// for the others - csrc/Makefile), so there is no translation unit of its own.
+// for the others - csrc/Makefile), so there is no translation unit of its own.  The choice of a launch's pixel type: ccal_pix.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include "ccal_pix.hpp"
 
 namespace ccal {
 

@@ -1,14 +1,40 @@
-// The host arithmetic the image stages share: the detector's domain, and how ccal_propose_quads_* and ccal_decode_tags_* cut a CSR
-// batch into chunks of whole images.  Plain arithmetic, no context and no HIP include, so that a plain C++ program can hold it to the
-// groupings the tests rely on (tests/cpp/test_quads_plan.cpp, tests/test_quads_plan_cpu.py; through ccal_tagchain_plan.hpp also
-// tests/cpp/test_tagchain_plan.cpp).
+// The host arithmetic the image stages share: the check of a batch of images and of a source / destination pair, the detector's
+// domain, and how ccal_propose_quads_* and ccal_decode_tags_* cut a CSR batch into chunks of whole images.  Plain arithmetic, no context
+// and no HIP include, so that plain C++ programs can hold it to the messages and groupings the tests rely on (tests/cpp/test_image_pair.cpp,
+// test_quads_plan.cpp, through ccal_tagchain_plan.hpp also test_tagchain_plan.cpp; tests/test_image_pair_cpu.py, test_quads_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+#include "../../include/ccal.h"
 
 namespace ccal {
+
+// [n_img][height][width] of CCAL_PIX_U8 / CCAL_PIX_U16: the message of the first argument out of range, `bad_dtype` for the first of
+// them, or nullptr (the pointer is the caller's check: it comes after n_img == 0)
+inline const char* grey_batch_bad(int dtype, int width, int height, int n_img, const char* bad_dtype = "dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16") {
+    if (dtype != CCAL_PIX_U8 && dtype != CCAL_PIX_U16) return bad_dtype;
+    if (width <= 0 || height <= 0 || n_img < 0) return "a size is not positive";
+    if ((int64_t)width * height > (int64_t)INT32_MAX) return "more than 2^31 - 1 pixels in an image";
+    return nullptr;
+}
+inline size_t grey_image_bytes(int dtype, int width, int height) { return (dtype == CCAL_PIX_U16 ? 2 : 1) * (size_t)width * (size_t)height; }
+
+// The source and destination blocks of an image-to-image stage (ccal_photo_apply_dev, ccal_normalize_dev).  go: launch; else what is the
+// first bad argument's message, or nullptr: nothing to do - n_img == 0 is a success that looks at no pointer.  Blocks that touch are fine.
+struct PairCheck { const char* what; bool go; };
+inline PairCheck image_pair_check(int src_dtype, int dst_dtype, int width, int height, int n_img, const void* src, const void* dst) {
+    if (const char* what = grey_batch_bad(src_dtype, width, height, n_img, "src_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16")) return { what, false };
+    if (const char* what = grey_batch_bad(dst_dtype, width, height, n_img, "dst_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16")) return { what, false };
+    if (n_img == 0) return { nullptr, false };
+    if (!src) return { "src_dev is NULL", false };
+    if (!dst) return { "dst_dev is NULL", false };
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), s1 = s0 + grey_image_bytes(src_dtype, width, height) * (size_t)n_img;
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + grey_image_bytes(dst_dtype, width, height) * (size_t)n_img;
+    if (s0 < d1 && d0 < s1) return { "src_dev and dst_dev overlap", false };
+    return { nullptr, true };
+}
 
 // the pixels the detector tests: x in [d0, d0 + dw), y in [d0, d0 + dh), and their (r+1) x (r+1) blocks, each of which holds at
 // most one candidate.  dw == 0: the image is too small to have a domain, there is nothing to launch.

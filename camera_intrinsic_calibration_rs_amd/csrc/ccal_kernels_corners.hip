@@ -102,8 +102,7 @@ hipError_t corners_enqueue(hipStream_t s, int dtype, const CornerArgs& a) {
     const int ps = 2 * a.h + 3;
     const size_t lds = sizeof(double) * (size_t)kCornerWaves * (size_t)(ps * ps + kCornerWTab);
     const dim3 grid((unsigned)(((size_t)a.n + kCornerWaves - 1) / kCornerWaves));
-    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_corner_refine<uint16_t>, grid, dim3(64 * kCornerWaves), lds, s, a);
-    else hipLaunchKernelGGL(k_corner_refine<uint8_t>, grid, dim3(64 * kCornerWaves), lds, s, a);
+    for_pix_type(dtype, [&](auto t) { hipLaunchKernelGGL(k_corner_refine<decltype(t)>, grid, dim3(64 * kCornerWaves), lds, s, a); });
     return hipGetLastError();
 }
 

@@ -206,8 +206,7 @@ hipError_t detect_enqueue_find(hipStream_t s, int dtype, const DetectArgs& a) {
     if (e != hipSuccess) return e;
     const size_t lds = det_lds_bytes(a.s, a.r);
     const dim3 grid((unsigned)((a.dw + kDetTile - 1) / kDetTile), (unsigned)((a.dh + kDetTile - 1) / kDetTile), (unsigned)m);
-    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_detect_tiles<uint16_t>, grid, dim3(kDetThreads), lds, s, a);
-    else hipLaunchKernelGGL(k_detect_tiles<uint8_t>, grid, dim3(kDetThreads), lds, s, a);
+    for_pix_type(dtype, [&](auto t) { hipLaunchKernelGGL(k_detect_tiles<decltype(t)>, grid, dim3(kDetThreads), lds, s, a); });
     hipLaunchKernelGGL(k_detect_rows, dim3((unsigned)m), dim3(kDetThreads), 0, s, a);
     return hipGetLastError();
 }

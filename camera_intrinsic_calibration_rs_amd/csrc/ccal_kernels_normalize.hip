@@ -14,14 +14,14 @@
 //            conflict).  A wavefront reads the rows it wrote.
 //   pixel    v = N S2 - S1 S1, its integer square root seeded from the f64 square root and corrected in integers both ways, the
 //            floor N F, d = N I - S1, q = d / s, Y = 128 + amp q, the quantisation.
-//   stores   store_pixel_group (ccal_pix_store.hpp), k_photo's: dwords of 4 u8 or 2 u16, pixel by pixel at the right edge and on
-//            unaligned rows; no lane writes outside the image.
+//   stores   store_pixel_group: dwords of 4 u8 or 2 u16, pixel by pixel at the right edge and on unaligned rows; no lane writes outside
+//            the image.  It, the pixel table, the tile's load, the quantisation and the tile arithmetic are ccal_pix.hpp's, k_photo's too.
 // This unit is compiled with -ffp-contract=off (csrc/Makefile): Y = 128 + amp q rounds the product and the sum on their own, as
 // tests/normalize_ref.py, the numpy yardstick, does; the device is held to it bit for bit.
 #include <algorithm>
 #include <cmath>
 #include "ccal_call.hpp"
-#include "ccal_pix_store.hpp"
+#include "ccal_pix.hpp"
 
 namespace ccal {
 
@@ -55,10 +55,6 @@ struct NormArgs {
     double amp;
 };
 
-template <class T> struct NormPix;
-template <> struct NormPix<uint8_t> { static constexpr double hi = 255.0, scale = 1.0; static constexpr unsigned up = 257u; };
-template <> struct NormPix<uint16_t> { static constexpr double hi = 65535.0, scale = 257.0; static constexpr unsigned up = 1u; };
-
 // the largest s with s s <= v, v < 2^63: the seed's rounding does not reach the result
 __device__ __forceinline__ unsigned long long norm_isqrt(unsigned long long v) {
     unsigned long long s = (unsigned long long)sqrt((double)v);
@@ -78,9 +74,8 @@ __global__ __launch_bounds__(256) void k_normalize(const NormArgs a) {
     uint16_t* tile_s = reinterpret_cast<uint16_t*>(cols_s + (size_t)th * iw);   // [ih][iw]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
-    const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
-    const int x_t = tile_x * kNormTileW, y_t = tile_y * th;                 // the tile's first pixel
-    const int x = x_t + lane;                                               // a lane beyond the right edge works on clamped pixels and stores nothing
+    const TileAt t = tile_at(a.tiles_x, kNormTileW, th);                    // the tile's first pixel: (t.x_t, t.y_t)
+    const int x = t.x_t + lane;                                             // a lane beyond the right edge works on clamped pixels and stores nothing
     const int k0 = wave * rpw;                                              // this wavefront's first output row of the tile
     const S* src = static_cast<const S*>(a.src);
     D* dst = static_cast<D*>(a.dst);
@@ -88,12 +83,7 @@ __global__ __launch_bounds__(256) void k_normalize(const NormArgs a) {
 
     for (int img = blockIdx.y; img < a.n_img; img += gridDim.y) {
         const S* I = src + (int64_t)img * n_pix;
-        // the tile with its halo, clamped to the image
-        for (int e = tid; e < ih * iw; e += 256) {
-            const int ty = e / iw, tx = e - ty * iw;
-            const int gx = min(max(x_t - r + tx, 0), a.W - 1), gy = min(max(y_t - r + ty, 0), a.H - 1);
-            tile_s[e] = (uint16_t)((unsigned)I[(int64_t)gy * a.W + gx] * NormPix<S>::up);
-        }
+        load_halo_tile<S>(tile_s, I, a.W, a.H, t.x_t, t.y_t, r, iw, ih, tid);
         __syncthreads();
         // columns.  tile row ty is image row y_t - r + ty: output row y_t + k takes the tile rows k .. k + 2 r
         for (int cx = lane; cx < iw; cx += 64) {
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(256) void k_normalize(const NormArgs a) {
         __syncthreads();
         // rows.  column-sum column lane + j, j = 0 .. 2 r, is pixel x - r + j
         for (int i = 0; i < rpw; ++i) {
-            const int y = y_t + k0 + i;                                     // wave-uniform
+            const int y = t.y_t + k0 + i;                                   // wave-uniform
             if (y >= a.H) break;
             const unsigned long long* row = cols_s + (k0 + i) * iw + lane;
             unsigned S1 = 0u;
@@ -140,7 +130,7 @@ __global__ __launch_bounds__(256) void k_normalize(const NormArgs a) {
             const long long d = (long long)(a.n_win * c) - (long long)S1;
             const double q = (double)d / (double)s;
             const double Y = 128.0 + a.amp * q;
-            const unsigned px = (unsigned)rint(fmin(fmax(Y * NormPix<D>::scale, 0.0), NormPix<D>::hi));
+            const unsigned px = pix_quantise<D>(Y);
             store_pixel_group<D>(dst + ((int64_t)img * a.H + y) * a.W, x, lane, a.W, px);
         }
         __syncthreads();                                                    // the next image's tile overwrites what the rows read
@@ -148,23 +138,6 @@ __global__ __launch_bounds__(256) void k_normalize(const NormArgs a) {
 }
 
 namespace {
-
-template <class S, class D>
-void normalize_launch_h(int th, dim3 grid, size_t lds, hipStream_t st, const NormArgs& a) {
-    switch (th) {
-    case 32: hipLaunchKernelGGL((k_normalize<S, D, 32>), grid, dim3(256), lds, st, a); break;
-    case 16: hipLaunchKernelGGL((k_normalize<S, D, 16>), grid, dim3(256), lds, st, a); break;
-#ifdef CCAL_NORM_TILE_H
-    default: hipLaunchKernelGGL((k_normalize<S, D, CCAL_NORM_TILE_H>), grid, dim3(256), lds, st, a); break;
-#endif
-    }
-}
-
-template <class S>
-void normalize_launch_d(int dst_dtype, int th, dim3 grid, size_t lds, hipStream_t st, const NormArgs& a) {
-    if (dst_dtype == CCAL_PIX_U16) normalize_launch_h<S, uint16_t>(th, grid, lds, st, a);
-    else normalize_launch_h<S, uint8_t>(th, grid, lds, st, a);
-}
 
 // nullptr, or the message of the first option out of range
 const char* normalize_check(const ccal_normalize_opts* o) {
@@ -180,16 +153,24 @@ hipError_t normalize_enqueue(hipStream_t st, const ccal_normalize_opts& o, int s
     a.src = src; a.dst = dst;
     a.W = width; a.H = height; a.n_img = n_img;
     a.r = o.radius;
-    a.tiles_x = (width + kNormTileW - 1) / kNormTileW;
     const unsigned long long side = 2ull * (unsigned long long)o.radius + 1ull;
     a.n_win = side * side;
     a.floor_s = a.n_win * (unsigned long long)std::max(1.0, std::rint(257.0 * o.min_sigma));
     a.amp = o.amp;
-    const int th = normalize_tile_h(o.radius), tiles_y = (height + th - 1) / th;
-    const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)std::min(n_img, 65535));
+    const int th = normalize_tile_h(o.radius);
+    const TileGrid tg = tile_grid(width, height, kNormTileW, th, n_img);
+    a.tiles_x = tg.tiles_x;
     const size_t lds = normalize_lds_bytes(o.radius);
-    if (src_dtype == CCAL_PIX_U16) normalize_launch_d<uint16_t>(dst_dtype, th, grid, lds, st, a);
-    else normalize_launch_d<uint8_t>(dst_dtype, th, grid, lds, st, a);
+    for_pix_type(src_dtype, [&](auto s) { for_pix_type(dst_dtype, [&](auto d) {
+        using S = decltype(s); using D = decltype(d);
+        switch (th) {
+        case 32: hipLaunchKernelGGL((k_normalize<S, D, 32>), tg.grid, dim3(256), lds, st, a); break;
+        case 16: hipLaunchKernelGGL((k_normalize<S, D, 16>), tg.grid, dim3(256), lds, st, a); break;
+#ifdef CCAL_NORM_TILE_H
+        default: hipLaunchKernelGGL((k_normalize<S, D, CCAL_NORM_TILE_H>), tg.grid, dim3(256), lds, st, a); break;
+#endif
+        }
+    }); });
     return hipGetLastError();
 }
 
@@ -215,15 +196,8 @@ int ccal_normalize_dev(ccal_ctx* ctx, int src_dtype, int dst_dtype, int width, i
     const BadArg bad{ ctx, "ccal_normalize_dev" };
     if (!norm) return bad("norm is NULL");
     if (const char* what = normalize_check(norm)) return bad(what);
-    const GreyBatch in{ src_dtype, width, height, n_img, src_dev, true }, out{ dst_dtype, width, height, n_img, dst_dev, true };
-    if (const char* what = in.bad()) return bad(src_dtype != CCAL_PIX_U8 && src_dtype != CCAL_PIX_U16 ? "src_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16" : what);
-    if (const char* what = out.bad()) return bad(dst_dtype != CCAL_PIX_U8 && dst_dtype != CCAL_PIX_U16 ? "dst_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16" : what);
-    if (n_img == 0) return CCAL_OK;
-    if (!src_dev) return bad("src_dev is NULL");
-    if (!dst_dev) return bad("dst_dev is NULL");
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_dev), s1 = s0 + in.img_bytes() * (size_t)n_img;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_dev), d1 = d0 + out.img_bytes() * (size_t)n_img;
-    if (s0 < d1 && d0 < s1) return bad("src_dev and dst_dev overlap");
+    const PairCheck pair = image_pair_check(src_dtype, dst_dtype, width, height, n_img, src_dev, dst_dev);
+    if (!pair.go) return pair.what ? bad(pair.what) : CCAL_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, normalize_enqueue(ctx->stream, *norm, src_dtype, dst_dtype, width, height, n_img, src_dev, dst_dev));
     return CCAL_OK;

@@ -11,16 +11,16 @@
 //            reads the pixel from the source.
 //   pixel    steps c to g in the lane that holds B(x, y).  The noise is counter-based: three splitmix64 finalisers per pixel, keyed by
 //            the image's stream and the pixel's index - no state, no atomics, no order.
-//   stores   store_pixel_group (ccal_pix_store.hpp): the lanes of a group of 4 (u8) or 2 (u16) adjacent pixels hand their pixels to
-//            the group's first lane, which stores them as one dword; a group that ends at the image's right edge, or whose first
-//            pixel is not on a dword boundary, stores pixel by pixel: no lane ever writes a byte outside the image.
+//   stores   store_pixel_group: dwords of 4 u8 or 2 u16, pixel by pixel at the right edge and on unaligned rows; no lane writes
+//            outside the image.  It, the pixel table, the tile's load, the quantisation and the tile arithmetic are ccal_pix.hpp's,
+//            shared with k_normalize.
 // This unit is compiled with -ffp-contract=off (csrc/Makefile): every product and sum rounds on its own, as tests/photo_ref.py, the
 // numpy yardstick, does; the device is held to it bit for bit.
 #include <algorithm>
 #include <cmath>
 #include "ccal_call.hpp"
 #include "ccal_photo.hpp"
-#include "ccal_pix_store.hpp"
+#include "ccal_pix.hpp"
 
 namespace ccal {
 
@@ -49,10 +49,6 @@ __device__ __forceinline__ unsigned photo_fields(unsigned long long w) {
     return (unsigned)(w & 0xFFFFull) + (unsigned)((w >> 16) & 0xFFFFull) + (unsigned)((w >> 32) & 0xFFFFull) + (unsigned)(w >> 48);
 }
 
-template <class T> struct PhotoPix;
-template <> struct PhotoPix<uint8_t> { static constexpr double hi = 255.0, scale = 1.0; static constexpr unsigned up = 257u; };
-template <> struct PhotoPix<uint16_t> { static constexpr double hi = 65535.0, scale = 257.0; static constexpr unsigned up = 1u; };
-
 // LDS: the noise table [256], the taps [24 with padding], the f64 rows [TH + 2 r][TW], the u16 tile [TH + 2 r][TW + 2 r]
 __host__ __device__ inline size_t photo_lds_bytes(int r) {
     const size_t ih = (size_t)(kPhotoTileH + 2 * r), iw = (size_t)(kPhotoTileW + 2 * r);
@@ -72,9 +68,8 @@ __global__ __launch_bounds__(256) void k_photo(const PhotoArgs a) {
     sig_s[tid] = a.t.sigma[tid];
     if (tid <= kPhotoMaxR) tap_s[tid] = a.t.taps[tid];
 
-    const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
-    const int x_t = tile_x * kPhotoTileW, y_t = tile_y * kPhotoTileH;      // the tile's first pixel
-    const int x = x_t + lane, y0 = y_t + wave * kPhotoRows;                // this lane's column and its first row
+    const TileAt t = tile_at(a.tiles_x, kPhotoTileW, kPhotoTileH);         // the tile's first pixel: (t.x_t, t.y_t)
+    const int x = t.x_t + lane, y0 = t.y_t + wave * kPhotoRows;            // this lane's column and its first row
     const int xc = min(x, a.W - 1);                                        // a lane beyond the right edge works on the edge and stores nothing
     const S* src = static_cast<const S*>(a.src);
     D* dst = static_cast<D*>(a.dst);
@@ -86,14 +81,9 @@ __global__ __launch_bounds__(256) void k_photo(const PhotoArgs a) {
         if (r == 0) {
             __syncthreads();                                               // the tables, on the first image
 #pragma unroll
-            for (int i = 0; i < kPhotoRows; ++i) B[i] = (double)((unsigned)I[(int64_t)min(y0 + i, a.H - 1) * a.W + xc] * PhotoPix<S>::up);
+            for (int i = 0; i < kPhotoRows; ++i) B[i] = (double)((unsigned)I[(int64_t)min(y0 + i, a.H - 1) * a.W + xc] * Pix<S>::up);
         } else {
-            // the tile with its halo, clamped to the image
-            for (int e = tid; e < ih * iw; e += 256) {
-                const int ty = e / iw, tx = e - ty * iw;
-                const int gx = min(max(x_t - r + tx, 0), a.W - 1), gy = min(max(y_t - r + ty, 0), a.H - 1);
-                tile_s[e] = (uint16_t)((unsigned)I[(int64_t)gy * a.W + gx] * PhotoPix<S>::up);
-            }
+            load_halo_tile<S>(tile_s, I, a.W, a.H, t.x_t, t.y_t, r, iw, ih, tid);
             __syncthreads();
             // a: rows.  tile column lane + r + j is pixel x + j
             for (int ty = wave; ty < ih; ty += 4) {
@@ -142,7 +132,7 @@ __global__ __launch_bounds__(256) void k_photo(const PhotoArgs a) {
                 Y = V + sig * z;
             }
             // g
-            const unsigned q = (unsigned)rint(fmin(fmax(Y * PhotoPix<D>::scale, 0.0), PhotoPix<D>::hi));
+            const unsigned q = pix_quantise<D>(Y);
             // the group's pixels to its first lane; every lane of the wavefront is here
             store_pixel_group<D>(dst + ((int64_t)img * a.H + y) * a.W, x, lane, a.W, q);
         }
@@ -150,12 +140,6 @@ __global__ __launch_bounds__(256) void k_photo(const PhotoArgs a) {
 }
 
 namespace {
-
-template <class S>
-void photo_launch_d(int dst_dtype, dim3 grid, size_t lds, hipStream_t st, const PhotoArgs& a) {
-    if (dst_dtype == CCAL_PIX_U16) hipLaunchKernelGGL((k_photo<S, uint16_t>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((k_photo<S, uint8_t>), grid, dim3(256), lds, st, a);
-}
 
 bool finite_nonneg(double v) { return v >= 0.0 && std::isfinite(v); }
 
@@ -190,17 +174,17 @@ hipError_t photo_enqueue(hipStream_t st, const PhotoTables& tables, const ccal_p
     PhotoArgs a = {};
     a.t = tables; a.src = src; a.dst = dst;
     a.W = width; a.H = height; a.n_img = n_img;
-    a.tiles_x = (width + kPhotoTileW - 1) / kPhotoTileW;
+    const TileGrid tg = tile_grid(width, height, kPhotoTileW, kPhotoTileH, n_img);
+    a.tiles_x = tg.tiles_x;
     a.vignette = o.vignette; a.gain = o.gain;
     a.cx = (double)(width - 1) / 2.0; a.cy = (double)(height - 1) / 2.0;
     a.den = a.cx * a.cx + a.cy * a.cy;
     a.stream0 = stream0;
     a.noisy = (o.noise_read > 0.0 || o.noise_shot > 0.0) ? 1 : 0;
-    const int tiles_y = (height + kPhotoTileH - 1) / kPhotoTileH;
-    const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)std::min(n_img, 65535));
     const size_t lds = photo_lds_bytes(tables.radius);
-    if (src_dtype == CCAL_PIX_U16) photo_launch_d<uint16_t>(dst_dtype, grid, lds, st, a);
-    else photo_launch_d<uint8_t>(dst_dtype, grid, lds, st, a);
+    for_pix_type(src_dtype, [&](auto s) { for_pix_type(dst_dtype, [&](auto d) {
+        hipLaunchKernelGGL((k_photo<decltype(s), decltype(d)>), tg.grid, dim3(256), lds, st, a);
+    }); });
     return hipGetLastError();
 }
 
@@ -236,15 +220,8 @@ int ccal_photo_apply_dev(ccal_ctx* ctx, int src_dtype, int dst_dtype, int width,
     if (!photo) return bad("photo is NULL");
     PhotoTables t;
     if (const char* what = photo_check(photo, &t)) return bad(what);
-    const GreyBatch in{ src_dtype, width, height, n_img, src_dev, true }, out{ dst_dtype, width, height, n_img, dst_dev, true };
-    if (const char* what = in.bad()) return bad(src_dtype != CCAL_PIX_U8 && src_dtype != CCAL_PIX_U16 ? "src_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16" : what);
-    if (const char* what = out.bad()) return bad(dst_dtype != CCAL_PIX_U8 && dst_dtype != CCAL_PIX_U16 ? "dst_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16" : what);
-    if (n_img == 0) return CCAL_OK;
-    if (!src_dev) return bad("src_dev is NULL");
-    if (!dst_dev) return bad("dst_dev is NULL");
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_dev), s1 = s0 + in.img_bytes() * (size_t)n_img;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_dev), d1 = d0 + out.img_bytes() * (size_t)n_img;
-    if (s0 < d1 && d0 < s1) return bad("src_dev and dst_dev overlap");
+    const PairCheck pair = image_pair_check(src_dtype, dst_dtype, width, height, n_img, src_dev, dst_dev);
+    if (!pair.go) return pair.what ? bad(pair.what) : CCAL_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, photo_enqueue(ctx->stream, t, *photo, src_dtype, dst_dtype, width, height, n_img, photo->seed + (uint64_t)photo->first_index,
                                src_dev, dst_dev));

@@ -169,8 +169,7 @@ void quads_set_params(QuadArgs& a, double min_side, double max_side, double max_
 
 hipError_t quads_enqueue_count(hipStream_t s, int dtype, const QuadArgs& a) {
     const dim3 grid((unsigned)(((size_t)a.n + kQuadWaves - 1) / kQuadWaves)), block(64 * kQuadWaves);
-    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_quad_edges<uint16_t>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(k_quad_edges<uint8_t>, grid, block, 0, s, a);
+    for_pix_type(dtype, [&](auto t) { hipLaunchKernelGGL(k_quad_edges<decltype(t)>, grid, block, 0, s, a); });
     hipLaunchKernelGGL(k_quad_chains<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }

@@ -9,6 +9,7 @@
 //            once per workgroup; an image's R and R^T t are read wave-uniformly, once per image.
 //   stores   a lane whose pixels end at the image's right edge, or whose first pixel is not on a dword boundary (rows of a width that is
 //            no multiple of 4 bytes), stores its own pixels one by one: no lane ever writes a byte it does not own.
+//            This store is the renderer's own; the pixel table, the quantisation and the tile arithmetic are ccal_pix.hpp's.
 // No atomics, no cross-lane traffic: a pixel is a pure function of the model, the target, the options and its image's pose.
 // This unit is compiled with -ffp-contract=off (csrc/Makefile): the plane intersection and the lattice arithmetic round every
 // product and sum on their own, as tests/render_ref.py, the numpy f64 yardstick, does.
@@ -19,6 +20,7 @@
 #include "ccal_device.hpp"
 #include "ccal_model_inverse.hpp"
 #include "ccal_photo.hpp"
+#include "ccal_pix.hpp"
 
 namespace ccal {
 
@@ -74,10 +76,6 @@ __device__ __forceinline__ int target_class(const RenderArgs& a, const unsigned 
     }
 }
 
-template <class T> struct RenderPix;
-template <> struct RenderPix<uint8_t> { static constexpr double hi = 255.0, scale = 1.0; };
-template <> struct RenderPix<uint16_t> { static constexpr double hi = 65535.0, scale = 257.0; };
-
 template <int MODEL, int TARGET, class T>
 __global__ __launch_bounds__(256) void k_render(const RenderArgs a) {
     constexpr int PX = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
@@ -87,10 +85,10 @@ __global__ __launch_bounds__(256) void k_render(const RenderArgs a) {
     if ((int)threadIdx.x < a.s) sub[threadIdx.x] = ((double)threadIdx.x + 0.5) / (double)a.s - 0.5;
     __syncthreads();
 
-    const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
+    const TileAt t = tile_at(a.tiles_x, kRenderTileLanes * PX, kRenderTileRows);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int lx = (wave & 1) * 8 + (lane & 7), ly = (wave >> 1) * 8 + (lane >> 3);
-    const int x0 = (tile_x * kRenderTileLanes + lx) * PX, y = tile_y * kRenderTileRows + ly;
+    const int x0 = t.x_t + lx * PX, y = t.y_t + ly;
     if (x0 >= a.W || y >= a.H) return;                    // after the only barrier
 
     double th[th_len<MODEL>()];
@@ -126,8 +124,7 @@ __global__ __launch_bounds__(256) void k_render(const RenderArgs a) {
                 }
             }
             const double lum = (((double)n_b * a.black + (double)n_w * a.white) + (double)(n_ray - n_b - n_w) * a.background) / ss;
-            const double q = fmin(fmax(rint(lum * RenderPix<T>::scale), 0.0), RenderPix<T>::hi);
-            word |= (uint32_t)q << (BITS * k);
+            word |= pix_quantise<T>(lum) << (BITS * k);
         }
         T* dst = static_cast<T*>(a.out) + ((int64_t)img * a.H + y) * a.W + x0;
         if (x0 + PX <= a.W && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0) *reinterpret_cast<uint32_t*>(dst) = word;
@@ -138,27 +135,22 @@ __global__ __launch_bounds__(256) void k_render(const RenderArgs a) {
 
 namespace {
 
-template <int MODEL, int TARGET>
-void render_launch_t(int dtype, dim3 grid, size_t lds, hipStream_t st, const RenderArgs& a) {
-    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL((k_render<MODEL, TARGET, uint16_t>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((k_render<MODEL, TARGET, uint8_t>), grid, dim3(256), lds, st, a);
-}
 template <int MODEL>
 void render_launch_m(int kind, int dtype, dim3 grid, size_t lds, hipStream_t st, const RenderArgs& a) {
-    if (kind == CCAL_TARGET_APRILGRID) render_launch_t<MODEL, CCAL_TARGET_APRILGRID>(dtype, grid, lds, st, a);
-    else render_launch_t<MODEL, CCAL_TARGET_CHECKERBOARD>(dtype, grid, lds, st, a);
+    for_pix_type(dtype, [&](auto t) {
+        if (kind == CCAL_TARGET_APRILGRID) hipLaunchKernelGGL((k_render<MODEL, CCAL_TARGET_APRILGRID, decltype(t)>), grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((k_render<MODEL, CCAL_TARGET_CHECKERBOARD, decltype(t)>), grid, dim3(256), lds, st, a);
+    });
 }
 hipError_t render_enqueue(int model, int kind, int dtype, hipStream_t st, RenderArgs a) {
-    const int px = dtype == CCAL_PIX_U16 ? 2 : 4;
-    a.tiles_x = (a.W + kRenderTileLanes * px - 1) / (kRenderTileLanes * px);
-    const int tiles_y = (a.H + kRenderTileRows - 1) / kRenderTileRows;
-    const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)std::min(a.n_img, 65535));
+    const TileGrid tg = tile_grid(a.W, a.H, kRenderTileLanes * (dtype == CCAL_PIX_U16 ? 2 : 4), kRenderTileRows, a.n_img);
+    a.tiles_x = tg.tiles_x;
     const size_t lds = sizeof(unsigned long long) * (size_t)a.n_tags + sizeof(double) * kRenderMaxSS;
     switch (model) {
-        case kUCM: render_launch_m<kUCM>(kind, dtype, grid, lds, st, a); break;
-        case kEUCM: render_launch_m<kEUCM>(kind, dtype, grid, lds, st, a); break;
-        case kKB4: render_launch_m<kKB4>(kind, dtype, grid, lds, st, a); break;
-        default: render_launch_m<kOCV5>(kind, dtype, grid, lds, st, a); break;
+        case kUCM: render_launch_m<kUCM>(kind, dtype, tg.grid, lds, st, a); break;
+        case kEUCM: render_launch_m<kEUCM>(kind, dtype, tg.grid, lds, st, a); break;
+        case kKB4: render_launch_m<kKB4>(kind, dtype, tg.grid, lds, st, a); break;
+        default: render_launch_m<kOCV5>(kind, dtype, tg.grid, lds, st, a); break;
     }
     return hipGetLastError();
 }

@@ -207,8 +207,7 @@ const char* tags_bad_codes(int d, const uint64_t* codes, int n_codes) {       //
 hipError_t tags_enqueue(hipStream_t s, int dtype, const TagArgs& a) {
     static_assert(kTagMaxSide * kTagMaxSide <= 64 * kTagCellChunks, "three cells per lane hold the largest grid");
     const dim3 grid((unsigned)(((size_t)a.n + kTagWaves - 1) / kTagWaves));
-    if (dtype == CCAL_PIX_U16) hipLaunchKernelGGL(k_decode_tags<uint16_t>, grid, dim3(64 * kTagWaves), 0, s, a);
-    else hipLaunchKernelGGL(k_decode_tags<uint8_t>, grid, dim3(64 * kTagWaves), 0, s, a);
+    for_pix_type(dtype, [&](auto t) { hipLaunchKernelGGL(k_decode_tags<decltype(t)>, grid, dim3(64 * kTagWaves), 0, s, a); });
     return hipGetLastError();
 }
 

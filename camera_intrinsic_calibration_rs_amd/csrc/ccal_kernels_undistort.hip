@@ -8,7 +8,7 @@
 // Remap semantics (fixed by this project, the `image` crate is not part of the reference tree): a map entry (mx, my) is valid
 // iff 0 <= mx <= W-1 and 0 <= my <= H-1 (NaN and +-inf fail, -0.0 counts as 0); an invalid entry writes 0 in every channel;
 // a valid one, in f32: x0 = floor(mx), ax = mx - x0, x1 = min(x0 + 1, W-1), the same for y,
-// val = (1-ay) ((1-ax) p00 + ax p01) + ay ((1-ax) p10 + ax p11), output = (T)floorf(val + 0.5f) clamped to the range of T.
+// val = (1-ay) ((1-ax) p00 + ax p01) + ay ((1-ax) p10 + ax p11), output = (T)floorf(val + 0.5f) clamped to Pix<T>::hi (ccal_pix.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,6 +18,7 @@
 #include "ccal_call.hpp"
 #include "ccal_device.hpp"
 #include "ccal_model_inverse.hpp"
+#include "ccal_pix.hpp"
 
 struct ccal_undistort_map {
     ccal_ctx* ctx = nullptr;
@@ -118,10 +119,6 @@ struct RemapArgs {
     const void* src; void* dst;
 };
 
-template <class T> struct PixLimits;
-template <> struct PixLimits<uint8_t> { static constexpr float hi = 255.0f; };
-template <> struct PixLimits<uint16_t> { static constexpr float hi = 65535.0f; };
-
 // One tap set of an output pixel: element offsets of the four neighbours inside an image, the two weights, validity.
 struct Tap { int32_t o00, o01, o10, o11; float ax, ay; bool ok; };
 
@@ -143,7 +140,7 @@ __device__ __forceinline__ uint32_t blend(const Tap& t, T p00, T p01, T p10, T p
     const float top = (1.0f - t.ax) * (float)p00 + t.ax * (float)p01;
     const float bot = (1.0f - t.ax) * (float)p10 + t.ax * (float)p11;
     const float val = (1.0f - t.ay) * top + t.ay * bot;
-    const float r = fminf(fmaxf(floorf(val + 0.5f), 0.0f), PixLimits<T>::hi);
+    const float r = fminf(fmaxf(floorf(val + 0.5f), 0.0f), (float)Pix<T>::hi);
     return t.ok ? (uint32_t)r : 0u;
 }
 
