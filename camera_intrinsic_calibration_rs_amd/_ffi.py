@@ -127,6 +127,15 @@ class NormalizeOpts(C.Structure):         # ccal_normalize_opts: local contrast 
 
 NORMALIZE_MAX_RADIUS = 32                 # CCAL_NORMALIZE_MAX_RADIUS
 
+
+class GreyOpts(C.Structure):              # ccal_grey_opts: the grey stage; ccal_grey_set_defaults: 1; 19595, 38470, 7471
+    _fields_ = [("bin", C.c_int32), ("w_r", C.c_int32), ("w_g", C.c_int32), ("w_b", C.c_int32)]
+
+
+# ccal_pixel_layout: what a source pixel of ccal_grey_dev is
+(LAYOUT_GREY, LAYOUT_RGB, LAYOUT_BGR, LAYOUT_RGBA, LAYOUT_BGRA,
+ LAYOUT_BAYER_RGGB, LAYOUT_BAYER_BGGR, LAYOUT_BAYER_GRBG, LAYOUT_BAYER_GBRG) = range(9)
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 LIB_PATH = os.environ.get("CCAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libccal_hip.so")
@@ -280,6 +289,8 @@ SYMBOLS = [
     # local contrast normalisation ahead of the detectors
     ("ccal_normalize_set_defaults", C.c_int, [C.POINTER(NormalizeOpts)]),
     ("ccal_normalize_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(NormalizeOpts)]),
+    ("ccal_grey_set_defaults", C.c_int, [C.POINTER(GreyOpts)]),
+    ("ccal_grey_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(GreyOpts)]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 ]

@@ -1304,6 +1304,24 @@ class NormalizeOpts:
     amp: float = 64.0
 
 
+@dataclasses.dataclass
+class GreyOpts:
+    """The grey stage ahead of every image stage (ccal_grey_opts in include/ccal.h states the rule; Context.grey_dev): colour and raw
+    Bayer frames to grey ones, `bin` x `bin` source pixels (1, 2 or 4) to an output pixel, with the channel weights w_r, w_g, w_b in
+    units of 1 / 65536 (they sum to 65536; the defaults are 0.299 / 0.587 / 0.114).  Output pixel X has its centre at source
+    coordinate bin X + (bin - 1) / 2."""
+    bin: int = 1
+    w_r: int = 19595
+    w_g: int = 38470
+    w_b: int = 7471
+
+
+# ccal_pixel_layout by name: what a source pixel of Context.grey_dev is
+LAYOUTS = {"grey": _ffi.LAYOUT_GREY, "rgb": _ffi.LAYOUT_RGB, "bgr": _ffi.LAYOUT_BGR, "rgba": _ffi.LAYOUT_RGBA, "bgra": _ffi.LAYOUT_BGRA,
+           "bayer_rggb": _ffi.LAYOUT_BAYER_RGGB, "bayer_bggr": _ffi.LAYOUT_BAYER_BGGR, "bayer_grbg": _ffi.LAYOUT_BAYER_GRBG,
+           "bayer_gbrg": _ffi.LAYOUT_BAYER_GBRG}
+
+
 def render_checkerboard(model: GenericModel, poses, pattern: Tuple[int, int], square_size: float, dtype=np.uint8, supersample: int = 4,
                         black: float = 40, white: float = 215, background: float = 0, margin: Optional[float] = None,
                         ctx: Optional[Context] = None, photo: Optional[PhotoOpts] = None) -> np.ndarray:

@@ -1,7 +1,8 @@
 // The host arithmetic the image stages share: the check of a batch of images and of a source / destination pair, the detector's
 // domain, and how ccal_propose_quads_* and ccal_decode_tags_* cut a CSR batch into chunks of whole images.  Plain arithmetic, no context
 // and no HIP include, so that plain C++ programs can hold it to the messages and groupings the tests rely on (tests/cpp/test_image_pair.cpp,
-// test_quads_plan.cpp, through ccal_tagchain_plan.hpp also test_tagchain_plan.cpp; tests/test_image_pair_cpu.py, test_quads_plan_cpu.py).
+// test_grey_check.cpp, test_quads_plan.cpp, through ccal_tagchain_plan.hpp also test_tagchain_plan.cpp; tests/test_image_pair_cpu.py,
+// test_grey_cpu.py, test_quads_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -32,6 +33,37 @@ inline PairCheck image_pair_check(int src_dtype, int dst_dtype, int width, int h
     if (!dst) return { "dst_dev is NULL", false };
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), s1 = s0 + grey_image_bytes(src_dtype, width, height) * (size_t)n_img;
     const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + grey_image_bytes(dst_dtype, width, height) * (size_t)n_img;
+    if (s0 < d1 && d0 < s1) return { "src_dev and dst_dev overlap", false };
+    return { nullptr, true };
+}
+
+// The grey stage (ccal_grey_dev): a source block of a pixel layout and a destination of another shape, [n_img][height / bin][width / bin].
+inline bool layout_is_bayer(int layout) { return layout >= CCAL_LAYOUT_BAYER_RGGB && layout <= CCAL_LAYOUT_BAYER_GBRG; }
+inline int layout_channels(int layout) {
+    return layout == CCAL_LAYOUT_RGB || layout == CCAL_LAYOUT_BGR ? 3 : layout == CCAL_LAYOUT_RGBA || layout == CCAL_LAYOUT_BGRA ? 4 : 1;
+}
+// bytes of one source image and of one destination image
+inline size_t grey_src_image_bytes(int layout, int dtype, int width, int height) { return (size_t)layout_channels(layout) * grey_image_bytes(dtype, width, height); }
+inline size_t grey_dst_image_bytes(int dtype, int width, int height, int bin) { return grey_image_bytes(dtype, width / bin, height / bin); }
+
+// As image_pair_check, for that pair: the options, the layout, then the source's type and sizes, the destination's type, what the bin and
+// a mosaic ask of the sizes, and - past n_img == 0 - the pointers and the overlap of the two blocks' bytes.
+inline PairCheck grey_stage_check(int layout, int src_dtype, int dst_dtype, int width, int height, int n_img, const void* src, const void* dst,
+                                  const ccal_grey_opts* opts) {
+    if (!opts) return { "opts is NULL", false };
+    if (layout < CCAL_LAYOUT_GREY || layout > CCAL_LAYOUT_BAYER_GBRG) return { "layout is not a ccal_pixel_layout", false };
+    if (opts->bin != 1 && opts->bin != 2 && opts->bin != 4) return { "bin is not 1, 2 or 4", false };
+    if (opts->w_r < 0 || opts->w_g < 0 || opts->w_b < 0) return { "a weight (w_r, w_g, w_b) is negative", false };
+    if ((int64_t)opts->w_r + opts->w_g + opts->w_b != 65536) return { "the weights w_r + w_g + w_b do not sum to 65536", false };
+    if (const char* what = grey_batch_bad(src_dtype, width, height, n_img, "src_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16")) return { what, false };
+    if (dst_dtype != CCAL_PIX_U8 && dst_dtype != CCAL_PIX_U16) return { "dst_dtype is neither CCAL_PIX_U8 nor CCAL_PIX_U16", false };
+    if (width < opts->bin || height < opts->bin) return { "width or height is below bin", false };
+    if (layout_is_bayer(layout) && (width < 2 || height < 2)) return { "a Bayer layout needs a width and a height of at least 2", false };
+    if (n_img == 0) return { nullptr, false };
+    if (!src) return { "src_dev is NULL", false };
+    if (!dst) return { "dst_dev is NULL", false };
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), s1 = s0 + grey_src_image_bytes(layout, src_dtype, width, height) * (size_t)n_img;
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + grey_dst_image_bytes(dst_dtype, width, height, opts->bin) * (size_t)n_img;
     if (s0 < d1 && d0 < s1) return { "src_dev and dst_dev overlap", false };
     return { nullptr, true };
 }

@@ -1,5 +1,6 @@
 // What the image stages share about pixels: the table of the two pixel types, the quantisation, the load of a tile with its halo and
-// the store of a wavefront's row of pixels (k_photo, k_normalize), a workgroup's tile and the grid of tiles (those two and k_render),
+// the store of a wavefront's row of pixels (k_photo, k_normalize), the load of rows of bytes (k_grey, which stores as those two do), a
+// workgroup's tile and the grid of tiles (those three and k_render),
 // the run-time choice of the pixel type (every stage's launch).  Header only, every function forced inline: the code follows the
 // -ffp-contract flag of the unit that includes it (off for render, photo and normalize, fast for the others - csrc/Makefile).
 #pragma once
@@ -28,6 +29,44 @@ __device__ __forceinline__ void load_halo_tile(uint16_t* tile_s, const S* I, int
         tile_s[e] = (uint16_t)((unsigned)I[(int64_t)gy * W + gx] * Pix<S>::up);
     }
 }
+
+// Rows of BYTES into LDS, for a stage whose pixels are not one sample each (k_grey: 3- and 4-channel pixels, mosaics with a reflected
+// halo) and whose rows start on any byte: tile row t is the nb bytes from address row_addr(t) (0: the row is not wanted), and goes to
+// lds + t * stride as the 16-byte-aligned words of global memory that cover it, one 16-byte load per lane - so byte b of the row
+// stands at lds[t * stride + (row_addr(t) & 15) + b], and stride is a multiple of 16 of at least nb + 15 (byte_row_stride).  [lo, hi)
+// is the caller's whole block: a word that reaches past either end of it is not loaded whole but as those of its four aligned dwords
+// that hold at least one byte of the block (such a dword cannot cross a page), the others read as 0.  By the 256 threads.
+__host__ __device__ constexpr int byte_row_stride(int nb) { return (nb + 15 + 15) & ~15; }
+__device__ __forceinline__ uint4 load_word16_within(uintptr_t c, uintptr_t lo, uintptr_t hi) {
+    typedef unsigned int word16 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) word16* global_word16;   // the addresses are numbers: say that they are global ones,
+    typedef const __attribute__((address_space(1))) uint32_t* global_word4;  // or the loads are flat ones
+    if (c >= lo && c + 16 <= hi) {
+        const word16 v = *(global_word16)c;
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uintptr_t d = c + 4u * (unsigned)k;
+        w[k] = (d + 4 > lo && d < hi) ? *(global_word4)d : 0u;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+template <class RowAddr>
+__device__ __forceinline__ void load_byte_rows(unsigned char* lds, int stride, int n_rows, int nb, uintptr_t lo, uintptr_t hi, int tid, RowAddr row_addr) {
+    const int per_row = stride >> 4;
+    for (int e = tid; e < n_rows * per_row; e += 256) {
+        const int t = e / per_row, j = e - t * per_row;
+        const uintptr_t a = row_addr(t);
+        if (a == 0) continue;
+        const uintptr_t c = (a & ~(uintptr_t)15) + 16u * (unsigned)j;
+        if (c >= a + (unsigned)nb) continue;
+        *reinterpret_cast<uint4*>(lds + t * stride + 16 * j) = load_word16_within(c, lo, hi);
+    }
+}
+// a neighbour's coordinate reflected about the edge pixel of 0 .. n - 1 (n >= 2, i in -1 .. n): a mosaic keeps its parity
+__host__ __device__ __forceinline__ int reflect_at_edge(int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; }
 
 // The store of a wavefront's row of quantised pixels, lane `lane` holding the value q of pixel x of `row` (W pixels): the lanes of a
 // group of 4 (u8) or 2 (u16) adjacent pixels hand their pixels to the group's first lane, which stores them as one dword; a group that

@@ -658,6 +658,20 @@ class Context:
         if rc != _ffi.OK:
             raise CcalError(rc, "ccal_normalize_dev", self.last_error())
 
+    # -- grey frames from colour and raw Bayer frames (ccal_grey_dev, ccal_kernels_grey.hip) -------------------------------------------
+    def grey_dev(self, src_ptr: int, dst_ptr: int, layout: int, src_dtype: int, dst_dtype: int, width: int, height: int, n_img: int,
+                 opts=None) -> None:
+        """The grey frames of the device block src_ptr - [n_img][height][width][c] for the interleaved layouts (_ffi.LAYOUT_RGB, _BGR,
+        _RGBA, _BGRA), [n_img][height][width] for _ffi.LAYOUT_GREY and the four _ffi.LAYOUT_BAYER_* mosaics, of _ffi.PIX_U8 / PIX_U16 -
+        into the device block dst_ptr, [n_img][height // bin][width // bin] of dst_dtype (grey_out_size), by the rule stated at
+        ccal_grey_dev in include/ccal.h (opts: an api.GreyOpts or a _ffi.GreyOpts; None: ccal_grey_set_defaults); dst_ptr then goes
+        into normalize_dev, detect_checkerboards_dev or detect_tags_dev.  Only enqueued on the context's stream; the blocks must not
+        overlap."""
+        rc = self.lib.ccal_grey_dev(self.handle, int(layout), int(src_dtype), int(dst_dtype), int(width), int(height), int(n_img),
+                                    C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.byref(grey_opts(opts, lib=self.lib)))
+        if rc != _ffi.OK:
+            raise CcalError(rc, "ccal_grey_dev", self.last_error())
+
     def close(self):
         if getattr(self, "handle", None):
             for p in list(getattr(self, "_problems", ())):     # whatever order the garbage collector picks: problems first
@@ -765,6 +779,26 @@ def normalize_opts(norm=None, lib=None) -> "_ffi.NormalizeOpts":
     if norm is not None:
         o.radius, o.min_sigma, o.amp = int(norm.radius), float(norm.min_sigma), float(norm.amp)
     return o
+
+
+def grey_opts(opts=None, lib=None) -> "_ffi.GreyOpts":
+    """The ccal_grey_opts of `opts`: a _ffi.GreyOpts as it is; None: ccal_grey_set_defaults; else anything with the fields bin, w_r,
+    w_g and w_b (api.GreyOpts)."""
+    if isinstance(opts, _ffi.GreyOpts):
+        return opts
+    o = _ffi.GreyOpts()
+    rc = (lib or _ffi.load()).ccal_grey_set_defaults(C.byref(o))
+    if rc != _ffi.OK:
+        raise CcalError(rc, "ccal_grey_set_defaults")
+    if opts is not None:
+        o.bin, o.w_r, o.w_g, o.w_b = int(opts.bin), int(opts.w_r), int(opts.w_g), int(opts.w_b)
+    return o
+
+
+def grey_out_size(width: int, height: int, bin: int):
+    """(width, height) of the frames Context.grey_dev writes for sources of width x height at `bin`: the rows and columns of an
+    incomplete last block are dropped."""
+    return int(width) // int(bin), int(height) // int(bin)
 
 
 def _per_image(offs, n_img: int, arrays):

@@ -1201,6 +1201,70 @@ int ccal_normalize_set_defaults(ccal_normalize_opts* norm);
 int ccal_normalize_dev(ccal_ctx* ctx, int src_dtype, int dst_dtype, int width, int height, int n_img, const void* src_dev,
                        void* dst_dev, const ccal_normalize_opts* norm);
 
+/* ---- grey frames from colour and raw Bayer frames, with binning ------------------------------------------------------------------
+ * Every image stage above takes single-channel frames.  The reference hands its detector whatever the session's .png / .jpg
+ * decodes to (src/data_loader.rs:36-44), for most cameras colour; machine-vision cameras deliver the raw Bayer mosaic.  This stage
+ * turns any of the layouts below into a grey block, device block to device block, optionally binned 2 x or 4 x for sensors far
+ * larger than the detector's working scale (README).  The rule is exact integer arithmetic with ONE rounding; tests/grey_ref.py is
+ * its numpy yardstick and the device is held to it to the bit.
+ *
+ * Source block.  Interleaved layouts (RGB, BGR, RGBA, BGRA): [n_img][height][width][c] of src_dtype, c = 3 or 4; alpha is ignored.
+ * GREY and the Bayer layouts: [n_img][height][width].  A u16 block is 2-byte aligned, as its type requires; nothing more is asked
+ * of either block's address.  A Bayer layout names the 2 x 2 cell at the image's origin in row-major order, (x, y) = (column, row) -
+ * other libraries name the same mosaics differently:
+ *
+ *     layout                    (0,0)  (1,0)  (0,1)  (1,1)
+ *     CCAL_LAYOUT_BAYER_RGGB      R      G      G      B
+ *     CCAL_LAYOUT_BAYER_BGGR      B      G      G      R
+ *     CCAL_LAYOUT_BAYER_GRBG      G      R      B      G
+ *     CCAL_LAYOUT_BAYER_GBRG      G      B      R      G
+ *
+ * Destination block.  [n_img][height / bin][width / bin] of dst_dtype, integer division: the rows and columns of an incomplete
+ * last block are dropped.  Output pixel X has its centre at source coordinate bin X + (bin - 1) / 2 (likewise Y): a corner found at
+ * x in the grey frame lies at bin x + (bin - 1) / 2 on the sensor.
+ *
+ * Options: ccal_grey_opts.  bin 1, 2 or 4; the weights w_r, w_g, w_b >= 0 with w_r + w_g + w_b == 65536.
+ * ccal_grey_set_defaults: 1; 19595, 38470, 7471 (0.299 / 0.587 / 0.114).
+ *
+ * Per source pixel (x, y).  I is the sample on the 16-bit scale: a u16 sample as it is, 257 p for a u8 sample.
+ *   a  the triple (R4, G4, B4), four times the channel values, so that every term is an integer.
+ *        GREY         all three are 4 I.
+ *        interleaved  4 times the channel.
+ *        Bayer, at an R or B site of colour c: c4 = 4 I(x, y); G4 = the sum of the four edge neighbours; the opposite colour = the
+ *                     sum of the four diagonal neighbours.
+ *        Bayer, at a G site: G4 = 4 I; the colour of the horizontal neighbours is 2 (I(x - 1, y) + I(x + 1, y)), the colour of the
+ *                     vertical neighbours 2 (I(x, y - 1) + I(x, y + 1)).
+ *        Bayer border a neighbour coordinate i outside 0 .. n - 1 is reflected about the edge pixel: i < 0 gives -i, i >= n gives
+ *                     2 (n - 1) - i.  This keeps the mosaic's parity; hence width and height are at least 2 for a Bayer layout.
+ *   b  N = w_r R4 + w_g G4 + w_b B4 (< 2^34).
+ * Per output pixel: S = the sum of N over its bin x bin block (< 2^38); s = 18 + 2 log2(bin);
+ *   u16: (S + 2^(s-1)) >> s;   u8: floor((S + 257 2^(s-1)) / (257 2^s)).  One rounding, half up, for either type.
+ * Consequences: GREY at bin 1 with equal types is a copy; u8 -> u16 is 257 p; u16 -> u8 is (v + 128) / 257; a u16 source equal to
+ * 257 times a u8 source gives the same output for every layout, bin and destination type (so a u8 source is computed in 32 bits); a
+ * Bayer frame whose sites are all v gives v; full-scale input gives exactly 255 / 65535 at every bin; BGR(A) equals RGB(A) with the
+ * channels swapped; RGBA equals RGB for any alpha; image k does not depend on its batch; results are equal from run to run.  No
+ * atomics, no floating point.
+ *
+ * ccal_grey_dev: it only enqueues on the context's stream, like ccal_normalize_dev, allocates and stages nothing.  The two blocks
+ * must not overlap.  There is no host-pointer and no in-place form.
+ * CCAL_ERR_INVALID_ARG with a message that starts "ccal_grey_dev: " and names the argument, nothing launched or written: opts NULL; a
+ * layout outside the enum; bin not 1, 2 or 4; a negative weight or a sum other than 65536; a dtype other than the two; width,
+ * height <= 0 or n_img < 0; more than 2^31 - 1 pixels in a source image; width < bin or height < bin; a Bayer layout with a side
+ * below 2; with n_img > 0 a NULL block or blocks that share a byte (their byte counts follow from the layout, the types and the bin;
+ * blocks that touch are fine).  n_img == 0 is valid and looks at no pointer.
+ * ccal_grey_set_defaults is host only and needs no context. */
+typedef enum {
+    CCAL_LAYOUT_GREY = 0, CCAL_LAYOUT_RGB, CCAL_LAYOUT_BGR, CCAL_LAYOUT_RGBA, CCAL_LAYOUT_BGRA,
+    CCAL_LAYOUT_BAYER_RGGB, CCAL_LAYOUT_BAYER_BGGR, CCAL_LAYOUT_BAYER_GRBG, CCAL_LAYOUT_BAYER_GBRG
+} ccal_pixel_layout;
+typedef struct {
+    int32_t bin;                           /* 1, 2 or 4: the output is [height / bin][width / bin] */
+    int32_t w_r, w_g, w_b;                 /* >= 0, w_r + w_g + w_b == 65536 */
+} ccal_grey_opts;
+int ccal_grey_set_defaults(ccal_grey_opts* opts);
+int ccal_grey_dev(ccal_ctx* ctx, int layout, int src_dtype, int dst_dtype, int width, int height, int n_img, const void* src_dev,
+                  void* dst_dev, const ccal_grey_opts* opts);
+
 /* ---- reference validation() statistics (src/util.rs:721-795) ---------------------------- */
 int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* poses, const double* extr,
                              double* err_out /* [n_corners] Euclidean px error */);
