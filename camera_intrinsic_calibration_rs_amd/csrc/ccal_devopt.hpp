@@ -5,6 +5,7 @@
 // reads them from the environment: they select among implementations that the parity tests hold to the same results.
 // All call sites live in translation units that are compiled twice (ccal_kernels_fused, ccal_kernels_normal, ccal_kernels_eval and the solver's
 // host side: ccal_solver, ccal_solver_ws, ccal_solver_many); choices that concern other translation units travel as arguments (FusedArgs::lpf_force, NormalWs::schurq_slots).
+// The superseded kernels behind CCAL_GRAM=mfma, CCAL_FUSE_ELIM=0 and CCAL_GENERAL_GRAM=mfma: ccal_legacy_*.hip, second library only (Makefile).
 #pragma once
 #include <cstdlib>
 

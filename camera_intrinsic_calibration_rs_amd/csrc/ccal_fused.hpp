@@ -277,8 +277,8 @@ struct FusedArgs {
     int32_t cam; const double* extr[2];
     int32_t avg_corners;           // corners per observation frame on average (lanes-per-frame choice of the Gram launchers)
     int32_t slot_ident;            // obs_slot[f] == f for every frame (one camera that saw every slot): the prologue does not wait for the table
-    // single-camera loop: k_gram1w eliminates the pose blocks of its frames itself (gram_fused_tail): no k_schur1m launch,
-    // one row of partial sums per wavefront.  Set by launch_gram1v when the kernel it picks supports it (elim_fused = 1)
+    // single-camera loop: the Gram kernel eliminates the pose blocks of its frames itself (gram_fused_tail): no separate elimination
+    // launch, one row of partial sums per wavefront.  Set by launch_gram1v when the kernel it picks supports it (elim_fused = 1)
     int32_t fuse_elim, elim_fused;
     int32_t part_cap;              // rows the partial-sum buffer holds
     // GEN, all cameras of a rig in ONE launch (same model and focal mode): the camera of every observation frame; `list` then
@@ -381,7 +381,6 @@ struct UnpackArgs {               // the starting point of a single-camera solve
     DevState* st; ColInfo* cols;
 };
 hipError_t launch_unpack1(const UnpackArgs& a, hipStream_t s);
-hipError_t launch_gram1(int model, bool one_focal, const FusedArgs& a, hipStream_t s);     // MFMA Gram (any model)
 hipError_t launch_gram1v(int model, bool one_focal, FusedArgs& a, hipStream_t s);    // register (VALU) Gram, any model
 // rows of partial sums (= workgroups) a single-launch group of this problem would have; 0: that form does not apply
 int fused_iter_rows(int model, bool one_focal, int n_obs, int avg_corners, int K, int share, bool batch = false);     // batch: a member of a lockstep batch (OPENCV5 takes the form only there)
@@ -399,9 +398,12 @@ hipError_t launch_gram2(int model, bool one_focal, FusedArgs& a, hipStream_t s);
 int gram2_iter_rows(int model, bool one_focal, int n_obs, int avg_corners, int K);
 hipError_t launch_gram2_iter(int model, bool one_focal, FusedArgs& a, hipStream_t s);
 hipError_t launch_gram2_general(int model, bool one_focal, const FusedArgs& a, hipStream_t s);
-hipError_t launch_schur1m(FusedArgs& a, hipStream_t s);   // second library only (-DCCAL_LEGACY_KERNELS): the separate elimination launch; sets a.n_part
 hipError_t launch_reduce1(const FusedArgs& a, hipStream_t s);
 hipError_t launch_head(const HeadArgs& a, hipStream_t s);
 hipError_t launch_state_eval(DevState* st, double lambda, hipStream_t s);     // state := "first evaluation of set 0 with this lambda"
+#ifdef CCAL_LEGACY_KERNELS      // second library only (ccal_legacy_fused.hip)
+hipError_t launch_gram1(int model, bool one_focal, const FusedArgs& a, hipStream_t s);     // matrix-core Gram (any model)
+hipError_t launch_schur1m(FusedArgs& a, hipStream_t s);   // the separate elimination launch; sets a.n_part
+#endif
 
 }  // namespace ccal

@@ -1,4 +1,4 @@
-// Pieces shared by the register Gram kernels (ccal_kernels_fused.hip: k_gram1v / k_gram1w; ccal_kernels_gram2.hip: k_gram2):
+// Pieces shared by the Gram kernels (ccal_kernels_fused.hip: k_gram1v; ccal_kernels_gram2.hip: k_gram2; ccal_legacy_*.hip):
 // the wave-level LDS hand-off, the exact elimination of one frame's pose block, and the fused tail that runs it on the
 // records a Gram kernel has just left in LDS.
 #pragma once
@@ -178,7 +178,7 @@ __device__ __forceinline__ bool eliminate_frame(double* R, double* Ym, const int
     return ok;
 }
 
-// Fused elimination (single-camera loop, k_gram1w): the wavefront that built G frames' Grams eliminates their pose blocks
+// Fused elimination (single-camera loop, k_gram1v / k_gram2): the wavefront that built G frames' Grams eliminates their pose blocks
 // itself - records in LDS at red + g GS (what k_schur1m loads from HBM), LPF lanes per frame - and writes ONE row of
 // partial sums per wavefront, [A_dir | Y^T Y | model decrease | failed blocks], frames added in a fixed order, to `row`
 // (the wavefront's row of FusedArgs::partial; single-launch groups: a row in LDS that the workgroup adds up).

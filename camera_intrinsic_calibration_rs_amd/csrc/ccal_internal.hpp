@@ -552,7 +552,7 @@ const char* tags_bad_params(int d, int border, int n_codes, int samples, double 
 const char* tags_bad_codes(int d, const uint64_t* codes, int n_codes);       // the table, once the ranges hold
 hipError_t tags_enqueue(hipStream_t s, int dtype, const TagArgs& a);
 // ccal_kernels_tagchain.hip: the two decision kernels of ccal_detect_tags_* on device arrays (the second library's test entry points
-// run them alone, ccal_test_hooks.hip)
+// run them alone, ccal_legacy_test_hooks.hip)
 struct MergeArgs {
     const int64_t* off;                 // [n_img + 1]: image k owns the points [off[k], off[k + 1]) of xy, status and out
     const double* xy;                   // [.][2]

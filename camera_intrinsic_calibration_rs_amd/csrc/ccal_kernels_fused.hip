@@ -11,8 +11,8 @@
 //   k_reduce1       fixed-order sum over the rows -> red (the all-reduce buffer of sharded solves)
 //   k_head          one wavefront: accept / reject / convergence tests (tiny-solver's rules or the Ceres-style trust region),
 //                   K x K solve, candidate intrinsics, status to pinned host memory; in-process transport: adds the ranks' sums
-//   second library only (-DCCAL_LEGACY_KERNELS / -DCCAL_DEV_SWITCHES): k_gram1 (matrix core), k_gram1w (LDS accumulators),
-//                   k_schur1m (the separate elimination launch), the OPENCV5 instantiations of k_gram1v
+// Every kernel here is in the product library.  The superseded matrix-core Gram (k_gram1) and the separate elimination launch
+// (k_schur1m) are in ccal_legacy_fused.hip, which only the second library contains.
 // Same arithmetic and decision sequence as the general loop in ccal_solver.hip (multi-camera problems);
 // parity tests cover both.
 #include <algorithm>
@@ -54,166 +54,9 @@ hipError_t launch_unpack1(const UnpackArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-#ifdef CCAL_LEGACY_KERNELS      // the matrix-core Gram kernel of round 1: superseded by the register kernels for every model; kept in
-                                // libccal_hip_legacy.so as the independent second implementation the parity tests hold the product kernels against
 // ---------------------------------------------------------------------------------------------
-// k_gram1
-// ---------------------------------------------------------------------------------------------
-template <int MODEL, bool OF>
-__global__ __launch_bounds__(256, CCAL_GRAM_MINW) void k_gram1(const FusedArgs a) {
-    constexpr int D = block_dim(MODEL, OF, false);
-    constexpr int K = D - 6, K1 = K + 1;
-    constexpr int RS = 16, CS = 2 * RS + 2;
-    constexpr int WS = FC_N0P + GRAM_TILE_CORNERS * CS;
-    extern __shared__ double smem[];
-    const DevState* st = a.st;
-    if (st->done || st->redo) return;            // finished, or a re-elimination group (no evaluation)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f = blockIdx.x * WAVES_PER_BLOCK + wave;
-    if (f >= a.n_obs) return;
-    double* fc = smem + wave * WS;
-    double* tile = fc + FC_N0P;
-    const int cur = st->cur, first = st->first;
-    const int es = first ? cur : (cur ^ 1);
-    const double* th_g = a.intr[es];
-    double th[th_len<MODEL>()];
-    load_theta<MODEL, OF>(th_g, a.rt, th);
-    const int64_t start = a.obs_off[f];
-    const int n = (int)(a.obs_off[f + 1] - start);
-    // software prefetch: the first pass's corner rows are requested before the (long, latency-bound)
-    // back-substitution + exp-map below; every later pass is requested one pass ahead
-    float pX, pY, pZ, pU, pV;
-    {
-        const int64_t g0 = start + (lane < n ? lane : 0);
-        pX = a.x[g0]; pY = a.y[g0]; pZ = a.z[g0]; pU = a.u[g0]; pV = a.v[g0];
-    }
-    {
-        // candidate pose = accepted pose + back-substitution of the previous camera solve
-        // (dp = -L^-T (y_r + Y dc)), then the frame constants; wave-uniform, scalar loads
-        const int slot = __builtin_amdgcn_readfirstlane(a.obs_slot[f]);
-        double pose[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) pose[i] = a.poses[cur][(int64_t)slot * 6 + i];
-        double mc = 0.0;
-        if (!first) {
-            const double* pf = a.pf[cur] + (int64_t)slot * a.PF;
-            if (pf[0] != 0.0) {
-                double dp[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const double* yr = pf + 21 + i * K1;
-                    double t = yr[K];
-#pragma unroll
-                    for (int j = 0; j < K; ++j) t += yr[j] * a.dc[j];
-                    dp[i] = -t;
-                }
-#pragma unroll
-                for (int i = 5; i >= 0; --i) {
-                    double t = dp[i];
-#pragma unroll
-                    for (int k = i + 1; k < 6; ++k) t -= pf[k * (k + 1) / 2 + i] * dp[k];
-                    dp[i] = t * pf[i * (i + 1) / 2 + i];
-                }
-                const double lam = st->lambda_solve;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const double gp = pf[21 + 6 * K1 + i], dCi = pf[21 + 6 * K1 + 6 + i];
-                    const double Dii = lam > 0.0 ? lam * clampd1(dCi, a.min_diag, a.max_diag) : 0.0;
-                    mc += dp[i] * (Dii * dp[i] - gp);
-                    pose[i] += dp[i];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 6; ++i) if (lane == i) a.poses[es][(int64_t)slot * 6 + i] = pose[i];
-        }
-        if (lane == 0) a.mc_f[f] = mc;
-        double fcr[FC_N0];
-        frame_setup<false>(pose, nullptr, fcr);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < FC_N0; ++i) fc[i] = fcr[i];
-        }
-    }
-    wsync();
-
-    d4 acc0 = { 0, 0, 0, 0 }, acc1 = { 0, 0, 0, 0 };
-    const int rd_off = (lane >> 5) * CS + ((lane >> 4) & 1) * RS + (lane & 15);
-    for (int base = 0; base < n; base += 64) {
-        const int c = base + lane;
-        const bool valid = c < n;
-        const double X = pX, Y = pY, Z = pZ, uo = pU, vo = pV;
-        if (base + 64 < n) {                                              // wave-uniform: next pass in flight
-            const int cn = base + 64 + lane;
-            const int64_t gn = start + (cn < n ? cn : 0);
-            pX = a.x[gn]; pY = a.y[gn]; pZ = a.z[gn]; pU = a.u[gn]; pV = a.v[gn];
-        }
-        double ru, rv, J[2 * D];
-        corner_block<MODEL, OF, false, true>(th, fc, X, Y, Z, uo, vo, ru, rv, J, J + D);      // rotation columns in the phi basis
-        const double sw = valid ? huber_sqrt_weight(ru * ru + rv * rv, a.huber_delta) : 0.0;
-        const int nv = min(64, n - base);
-#pragma unroll
-        for (int half = 0; half < 64 / GRAM_TILE_CORNERS; ++half) {
-            if (half * GRAM_TILE_CORNERS >= nv) break;                    // wave-uniform
-            if ((lane / GRAM_TILE_CORNERS) == half) {
-                double* row = tile + (lane % GRAM_TILE_CORNERS) * CS;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                    for (int i = 0; i < RS; i += 2) {
-                        const double v0 = i < D ? sw * J[h * D + (i < D ? i : 0)] : (i == D ? sw * (h ? rv : ru) : 0.0);
-                        const double v1 = (i + 1) < D ? sw * J[h * D + ((i + 1) < D ? (i + 1) : 0)] : ((i + 1) == D ? sw * (h ? rv : ru) : 0.0);
-                        *reinterpret_cast<double2*>(row + h * RS + i) = make_double2(v0, v1);
-                    }
-                }
-            }
-            wsync();
-            const int npairs = (min(GRAM_TILE_CORNERS, nv - half * GRAM_TILE_CORNERS) + 1) >> 1;
-            const double* rd = tile + rd_off;
-            int m = 0;
-            for (; m + 1 < npairs; m += 2) {
-                const double p = rd[(2 * m) * CS];
-                const double q = rd[(2 * m + 2) * CS];
-                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(p, p, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q, q, acc1, 0, 0, 0);
-            }
-            if (m < npairs) {
-                const double p = rd[(2 * m) * CS];
-                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(p, p, acc0, 0, 0, 0);
-            }
-            wsync();
-        }
-    }
-    // Gram -> LDS (aliases the tile), then the compact record.  Columns: camera 0..K-1, pose K..K+5, r = D.
-    double* G = tile;
-    {
-        const d4 acc = acc0 + acc1;
-        const int gi = lane >> 4, gj = lane & 15;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) G[(gi + 4 * v) * 16 + gj] = acc[v];
-    }
-    wsync();
-    double* rec = a.praw[es] + (int64_t)f * a.PRAW;
-    if (lane < 21) {
-        int i = 0, r = lane;
-        while (r > i) { r -= i + 1; ++i; }          // lane -> (i, r) of the packed lower triangle
-        rec[lane] = G[(K + i) * 16 + (K + r)];
-    }
-    for (int e = lane; e < 6 * K1; e += 64) {
-        const int i = e / K1, j = e - i * K1;
-        rec[21 + e] = G[(K + i) * 16 + (j < K ? j : D)];
-    }
-    for (int e = lane; e < K1 * K1; e += 64) {
-        const int i = e / K1, j = e - i * K1;
-        rec[21 + 6 * K1 + e] = G[(i < K ? i : D) * 16 + (j < K ? j : D)];
-    }
-    if (lane == 0) a.cost_f[f] = G[D * 16 + D];
-    if (lane < 9) rec[praw_jl_off(K) + lane] = fc[FC_A + lane];      // the frame's left Jacobian: the elimination maps phi -> rvec with it
-}
-
-#endif  // CCAL_LEGACY_KERNELS
-
-// ---------------------------------------------------------------------------------------------
-// k_gram1v: the same per-frame record as k_gram1, without the LDS transposition the matrix cores need.
+// k_gram1v: the same per-frame record as k_gram1 (the matrix-core kernel of round 1, ccal_legacy_fused.hip), without the LDS
+// transposition the matrix cores need.
 // Measured (profiles/r01, ablations in DESIGN.md): staging sqrt(w)[J|r] rows through LDS in MFMA operand
 // order costs ~45 us of k_gram1's 69 us at 10 000 frames, and f64 MFMA shares the FP64 datapath with the
 // VALU on gfx950 (no overlap).  Here 16 lanes own one frame (4 frames per wavefront; 144 corners = 9 x 16,
@@ -222,19 +65,16 @@ __global__ __launch_bounds__(256, CCAL_GRAM_MINW) void k_gram1(const FusedArgs a
 // ---------------------------------------------------------------------------------------------
 // Where each accumulated triangle entry goes inside the compact per-frame record
 // C (21) | [B|g] (6 x K1) | A (K1 x K1, both halves), worked out at compile time: dst | mirror << 16 (0xffff = none).
-// W = number of leading camera columns whose products with the pose columns are left out (k_gram1w keeps those in LDS
-// and writes them separately).
-template <int K, int W, bool GEN = false>
+template <int K, bool GEN = false>
 struct RecMap {
     static constexpr int D = K + 6, NC = D + 1, K1 = K + 1;
-    static constexpr int N = NC * (NC + 1) / 2 - 6 * W;
+    static constexpr int N = NC * (NC + 1) / 2;
     uint32_t d[N];
     constexpr RecMap() : d{} {
         int r = 0;
         for (int i = 0; i < NC; ++i)
             for (int j = i; j < NC; ++j) {
                 const bool ip = i >= K && i < D, jp = j >= K && j < D;      // pose columns
-                if (!ip && jp && i < W) continue;
                 const int ci = i < K ? i : K, cj = j < K ? j : K;           // camera-block index (r -> K)
                 uint32_t a = 0, b = 0xffff;
                 if (!GEN) {
@@ -252,20 +92,15 @@ struct RecMap {
             }
     }
 };
-template <int K, int W, bool GEN = false> __device__ const RecMap<K, W, GEN> g_recmap = RecMap<K, W, GEN>();
+template <int K, bool GEN = false> __device__ const RecMap<K, GEN> g_recmap = RecMap<K, GEN>();
 
-// camera columns whose products with the pose columns k_gram1w keeps as LDS accumulators
-#ifndef CCAL_GRAMW_NLC
-#define CCAL_GRAMW_NLC 3          // measured at 10 000 frames (EUCM): 6 -> 53.2, 4 -> 51.8, 3 -> 51.0, 2 -> 56.1 us per build
-#endif
-// doubles of LDS per wavefront of k_gram1v (W = false) / k_gram1w (W = true) at lpf lanes per frame: the frames' constants | the
-// reduction buffer (k_gram1w: or its LDS accumulators).  The kernels assert their own layout against it, the launchers size by it.
-template <int MODEL, bool OF, bool W>
+// doubles of LDS per wavefront of k_gram1v at lpf lanes per frame: the frames' constants | the reduction buffer.
+// The kernel asserts its own layout against it, the launchers size by it.
+template <int MODEL, bool OF>
 constexpr int gram1_wave_lds(int lpf) {
     constexpr int NC = block_dim(MODEL, OF, false) + 1, NE = NC * (NC + 1) / 2;
-    constexpr int NL = W ? 6 * (CCAL_GRAMW_NLC < NC - 7 ? CCAL_GRAMW_NLC : NC - 7) : 0;
-    constexpr int LS = ((NE - NL + 1) / 2) | 1;
-    return (64 / lpf) * FC_N0P + (NL * 65 > 64 * LS ? NL * 65 : 64 * LS);
+    constexpr int LS = ((NE + 1) / 2) | 1;
+    return (64 / lpf) * FC_N0P + 64 * LS;
 }
 // structural zeros of the block Jacobian rows (u row: no fy, cy; v row: no fx, cx); f feeds both rows
 template <bool OF> __device__ constexpr bool nz_u(int i) { return OF ? (i != 2) : (i != 1 && i != 3); }
@@ -295,7 +130,7 @@ __device__ __forceinline__ void gram1v_body(const FusedArgs& a, const IterDyn& d
     constexpr int HALF = (NE + 1) / 2;              // entries reduced per LDS round
     constexpr int LS = HALF | 1;                    // odd row stride (doubles): conflict-free column sums
     constexpr int WSL = G * FC_N0P + 64 * LS;           // per wave: G frames' constants | reduction buffer
-    static_assert(WSL == gram1_wave_lds<MODEL, OF, false>(LPF), "the launchers size the LDS by gram1_wave_lds");
+    static_assert(WSL == gram1_wave_lds<MODEL, OF>(LPF),"the launchers size the LDS by gram1_wave_lds");
     constexpr int NQ = (G * HALF + 63) / 64;        // (frame, entry) sums per lane and round
     extern __shared__ double smem[];
 #ifdef CCAL_STAMPS          // diagnostic build (tools/stamps_g1v.py): the phases of every wavefront, 8 stamps per wavefront in the per-frame scratch
@@ -662,7 +497,7 @@ __device__ __forceinline__ void gram1v_body(const FusedArgs& a, const IterDyn& d
             const int g = idx / HALF, t = idx - g * HALF, e = h * HALF + t;
             const int ff = fbase + g;
             if (e >= NE || ff >= a.n_obs) continue;
-            const uint32_t m = g_recmap<K, 0, GEN>.d[e];
+            const uint32_t m = g_recmap<K, GEN>.d[e];
             const double v = res[h][q];
             double* rec = a.praw[es] + (GEN ? a.rec_off[a.list[ff]] : (int64_t)ff * a.PRAW);
             if (keep_rec) {
@@ -730,355 +565,11 @@ __global__ __launch_bounds__(256, 1) void k_gram1v_batch(const FusedArgs* __rest
     gram1v_body<MODEL, OF, LPF, false, true>(a, dy);
 }
 
-// k_gram1w: k_gram1v with two wavefronts per SIMD.  k_gram1v needs 256 VGPRs + 66 AGPRs (91 accumulators and the
-// hoisted frame constants), i.e. one wavefront per SIMD and nothing to hide the f64 dependency stalls behind.
-// Here the 6 K camera x pose accumulators of every lane live in LDS ([entry][lane], stride 65: conflict-free both
-// for the lane-private ds_add_f64 of the corner loop - fire and forget, nothing waits on it - and for the column
-// sums afterwards), and the frame constants are re-read from LDS every corner instead of being hoisted.
 template <int MODEL, bool OF, int LPF, bool GEN>
-__global__ __launch_bounds__(64 * CCAL_GRAMV_WPB, 2) void k_gram1w(const FusedArgs a) {
-    constexpr int G = 64 / LPF;                     // frames per wavefront
-    constexpr int D = block_dim(MODEL, OF, false);
-    constexpr int K = D - 6, K1 = K + 1;
-    constexpr int NC = D + 1;                       // columns of [J | r]
-    constexpr int NE = NC * (NC + 1) / 2;           // upper triangle
-    // camera columns whose products with the pose columns are LDS accumulators: as few as keeps two wavefronts per SIMD
-    constexpr int NLC = CCAL_GRAMW_NLC < K ? CCAL_GRAMW_NLC : K;
-    constexpr int NL = 6 * NLC;
-    constexpr int NR = NE - NL;                     // the rest: registers
-    constexpr int LSA = 65;                         // lane stride of an LDS accumulator row
-    constexpr int HALF = (NR + 1) / 2;              // register entries reduced per LDS round
-    constexpr int LS = HALF | 1;                    // odd row stride (doubles): conflict-free column sums
-    constexpr int RED = NL * LSA > 64 * LS ? NL * LSA : 64 * LS;
-    constexpr int WSL = G * FC_N0P + RED;               // per wave: G frames' constants | accumulators / reduction buffer
-    static_assert(WSL == gram1_wave_lds<MODEL, OF, true>(LPF), "the launchers size the LDS by gram1_wave_lds");
-    constexpr int NQ = (G * HALF + 63) / 64;        // (frame, entry) sums per lane and round
-    constexpr int NQA = (G * NL + 63) / 64;
-    extern __shared__ double smem[];
-    const DevState* st = a.st;
-    // fused elimination (launch_gram1v_t decides): no separate elimination launch; a re-elimination group then runs here too
-    const bool fuse = !GEN && a.fuse_elim != 0;
-    // the records in HBM are what a re-elimination group reads: Gauss-Newton never has one, so a fused GN group skips the stores
-    const bool keep_rec = GEN || !fuse || st->method == CCAL_METHOD_LM;
-    if (st->done || (st->redo && !fuse)) return;            // finished, or a re-elimination group without fusion (no evaluation)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#ifdef CCAL_STAMPS          // diagnostic build (tools/stamps_gram.py): start / end time of every wavefront into the per-frame scratch
-    const long long t_start = wall_clock64();
-#endif
-    // LPF need not divide 64 (12 lanes x 5 frames, 6 x 10): the lanes beyond G * LPF idle along with group G - 1
-    const bool lane_ok = lane < G * LPF;
-    const int grp = lane_ok ? lane / LPF : G - 1, gl = lane % LPF;
-    const int f = (blockIdx.x * CCAL_GRAMV_WPB + wave) * G + grp;
-    const bool active = lane_ok && f < a.n_obs;
-    const int fa_ = GEN ? a.list[active ? f : 0] : (active ? f : 0);      // observation frame (GEN: the camera's list)
-    const int camf = (GEN && a.obs_cam) ? a.obs_cam[fa_] : a.cam;          // GEN, merged launch: the frame's camera
-    double* fcw = smem + wave * WSL;
-    double* fc = fcw + grp * FC_N0P;
-    double* red = fcw + G * FC_N0P;
-    const int cur = st->cur, first = st->first;
-    const int es = first ? cur : (cur ^ 1);
-    if constexpr (!GEN) {
-        constexpr int REC_ = praw_jl_off(K) + 9, GS_ = (REC_ + 6 * K1 + 1) & ~1;
-        static_assert(G * GS_ <= RED, "the frames' records fit the reduction buffer");
-        if (st->redo) {
-            // re-elimination group (LM: rejected step or missed speculation): the accepted set's stored records, new damping
-            double* R = red + grp * GS_;
-            double mcv = 0.0;
-            int slot_r = 0;
-            if (active) {
-                const double* rec = a.praw[cur] + (int64_t)f * a.PRAW;
-                slot_r = a.obs_slot[f];
-                for (int e = gl; e < REC_; e += LPF) R[e] = rec[e];
-                if (gl == 0) mcv = a.mc_f[f];
-            }
-            wsync();
-            gram_fused_tail<K, LPF>(a, schur_lambda(st), red, a.partial + (int64_t)(blockIdx.x * CCAL_GRAMV_WPB + wave) * fused_red_size(K), grp, gl, lane_ok, active, slot_r, cur, mcv);
-            return;
-        }
-    }
-    const double* th_g = a.intr[es] + ((GEN && a.obs_cam) ? camf * CCAL_PMAX : 0);
-    double th[th_len<MODEL>()];
-    load_theta<MODEL, OF>(th_g, a.rt, th);
-    const int64_t start = a.obs_off[fa_];
-    const int n = active ? (int)(a.obs_off[fa_ + 1] - start) : 0;
-    float pX, pY, pZ, pU, pV;
-    {
-        const int64_t g0 = start + (gl < n ? gl : 0);
-        pX = a.x[g0]; pY = a.y[g0]; pZ = a.z[g0]; pU = a.u[g0]; pV = a.v[g0];
-    }
-    {
-        // candidate pose of this group's frame (back-substitution of the previous camera solve) + constants;
-        // the 16 lanes of a group compute the same values, the 4 groups work on 4 frames at once
-        const int slot = a.obs_slot[fa_];
-        double pose[6];
-        // GEN: k_backsub has formed the candidate - or, FusedArgs::gen_backsub, it is formed here from the accepted pose
-        const bool gbs = GEN && a.gen_backsub != 0 && !first;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) pose[i] = a.poses[(GEN && !gbs) ? es : cur][(int64_t)slot * 6 + i];
-        if constexpr (GEN) {
-            if (gbs) {
-                const double mcg = gen_backsub_pose<LPF, G, 0>(a, slot, st->lambda_solve, pose, red, grp, gl, lane_ok);      // (this kernel's buffer holds its LDS accumulators: the record is walked in global memory)
-                if (active && a.g_owner[fa_]) {
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) if (gl == i) a.poses[es][(int64_t)slot * 6 + i] = pose[i];
-                    if (gl == 0) a.g_mc_slot[slot] = mcg;
-                }
-            }
-        }
-        double mc = 0.0;
-        if (!GEN && !first) {
-            const double* pf = a.pf[cur] + (int64_t)slot * a.PF;
-            if (pf[0] != 0.0) {
-                double dp[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const double* yr = pf + 21 + i * K1;
-                    double t = yr[K];
-#pragma unroll
-                    for (int j = 0; j < K; ++j) t += yr[j] * a.dc[j];
-                    dp[i] = -t;
-                }
-#pragma unroll
-                for (int i = 5; i >= 0; --i) {
-                    double t = dp[i];
-#pragma unroll
-                    for (int k = i + 1; k < 6; ++k) t -= pf[k * (k + 1) / 2 + i] * dp[k];
-                    dp[i] = t * pf[i * (i + 1) / 2 + i];
-                }
-                const double lam = st->lambda_solve;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const double gp = pf[21 + 6 * K1 + i], dCi = pf[21 + 6 * K1 + 6 + i];
-                    const double Dii = lam > 0.0 ? lam * clampd1(dCi, a.min_diag, a.max_diag) : 0.0;
-                    mc += dp[i] * (Dii * dp[i] - gp);
-                    pose[i] += dp[i];
-                }
-            }
-            if (active) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) if (gl == i) a.poses[es][(int64_t)slot * 6 + i] = pose[i];
-            }
-        }
-        if (!GEN && active && gl == 0) a.mc_f[f] = mc;
-        if constexpr (GEN) {
-            // composed pose T_c0 o T_0b and the 6 x 12 expansion matrix E (frame_setup_composed); E^T goes straight into
-            // the frame's record, where k_schur finds it
-            const bool other = camf > 0;
-            double ex[6], fcr[12], ept[GEN_EPT];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) ex[i] = other ? a.extr[es][camf * 6 + i] : 0.0;
-            frame_setup_composed(pose, ex, fcr, ept);
-            if (gl == 0 && lane_ok) {
-#pragma unroll
-                for (int i = 0; i < 12; ++i) fc[i] = fcr[i];
-            }
-            if (gl == 0 && active) {
-                double ec[GEN_EC];
-                gen_et_compact(ept, ec);
-                double2* rec = reinterpret_cast<double2*>(a.praw[es] + a.rec_off[fa_] + gen_e_off(K));
-#pragma unroll
-                for (int i = 0; i < GEN_EC / 2; ++i) rec[i] = make_double2(ec[2 * i], ec[2 * i + 1]);
-            }
-        } else {
-            double fcr[FC_N0];
-            frame_setup<false>(pose, nullptr, fcr);
-            if (gl == 0 && lane_ok) {
-#pragma unroll
-                for (int i = 0; i < FC_N0; ++i) fc[i] = fcr[i];
-            }
-        }
-    }
-    wsync();
-
-    double acc[NR];
-#pragma unroll
-    for (int e = 0; e < NR; ++e) acc[e] = 0.0;
-#pragma unroll
-    for (int t = 0; t < NL; ++t) red[t * LSA + lane] = 0.0;
-    // same trip count for the whole wave: the largest frame of the four
-    int nmax = n;
-#pragma unroll
-    for (int off = ((LPF & (LPF - 1)) == 0 ? LPF : 1); off < 64; off <<= 1) nmax = max(nmax, __shfl_xor(nmax, off, 64));
-#ifndef CCAL_GRAMW_HOIST
-#define CCAL_GRAMW_HOIST 1      // measured: 10 000 frames 42.5 -> 41.7 us per build, 20 000: 72.7 -> 70.6 (244 VGPRs, still two wavefronts per SIMD)
-#endif
-#if CCAL_GRAMW_HOIST
-    // phi basis: a corner needs R and t only (12 doubles): in registers, no LDS read (and no wait for one) per corner
-    double fcl[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) fcl[i] = fc[i];
-    const double* fcp = fcl;
-#else
-    const double* fcp = fc;
-#endif
-#ifdef CCAL_STAMPS
-    const long long t_loop = wall_clock64();
-#endif
-    for (int base = 0; base < nmax; base += LPF) {
-#if !CCAL_GRAMW_HOIST
-        asm volatile("" ::: "memory");      // frame constants stay in LDS: no 78 registers of hoisted copies
-#endif
-        const int c = base + gl;
-        const bool valid = c < n;
-        const double X = pX, Y = pY, Z = pZ, uo = pU, vo = pV;
-        if (base + LPF < nmax) {
-            const int cn = base + LPF + gl;
-            const int64_t gn = start + (cn < n ? cn : 0);
-            pX = a.x[gn]; pY = a.y[gn]; pZ = a.z[gn]; pU = a.u[gn]; pV = a.v[gn];
-        }
-        double ru, rv, J[2 * D];
-        corner_block<MODEL, OF, false, true>(th, fcp, X, Y, Z, uo, vo, ru, rv, J, J + D);      // rotation columns in the phi basis
-        const double sw = valid ? huber_sqrt_weight(ru * ru + rv * rv, a.huber_delta) : 0.0;
-        // sqrt(w)-scaled rows (only the structurally non-zero entries are ever touched)
-        double su[NC], sv[NC];
-#pragma unroll
-        for (int i = 0; i < D; ++i) { su[i] = sw * J[i]; sv[i] = sw * J[D + i]; }
-        su[D] = sw * ru; sv[D] = sw * rv;
-        int e = 0, el = 0;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) {
-#pragma unroll
-            for (int j = i; j < NC; ++j) {
-                const bool bu = (i >= K || nz_u<OF>(i)) && (j >= K || nz_u<OF>(j));
-                const bool bv = (i >= K || nz_v<OF>(i)) && (j >= K || nz_v<OF>(j));
-                if (i < NLC && j >= K && j < D) {        // camera x pose: LDS accumulator of this lane
-                    double t = bu ? su[i] * su[j] : 0.0;
-                    if (bv) t = __builtin_fma(sv[i], sv[j], t);
-                    __hip_atomic_fetch_add(red + el * LSA + lane, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    ++el;
-                } else {
-                    if (bu) acc[e] = __builtin_fma(su[i], su[j], acc[e]);
-                    if (bv) acc[e] = __builtin_fma(sv[i], sv[j], acc[e]);
-                    ++e;
-                }
-            }
-        }
-    }
-#ifdef CCAL_STAMPS
-    const long long t_after = wall_clock64();
-#endif
-    const int fbase = (blockIdx.x * CCAL_GRAMV_WPB + wave) * G;
-    // fused elimination: what its tail needs from memory is requested now, behind the reductions
-    int slot_t = 0;
-    double mc_t = 0.0;
-    if constexpr (!GEN) {
-        if (fuse && active) { slot_t = a.obs_slot[f]; if (gl == 0) mc_t = a.mc_f[f]; }
-    }
-    // camera x pose: LPF lane-private LDS sums per frame -> record  [B|g][pose j][camera i]
-    wsync();
-    double resa[NQA];
-    {
-#pragma unroll
-        for (int q = 0; q < NQA; ++q) {
-            const int idx = lane + 64 * q;
-            double sum = 0.0;
-            if (idx < G * NL) {
-                const int g = idx / NL, t = idx - g * NL;
-                const double* src = red + t * LSA + g * LPF;
-#pragma unroll
-                for (int l = 0; l < LPF; ++l) sum += src[l];
-            }
-            resa[q] = sum;
-        }
-#pragma unroll
-        for (int q = 0; q < NQA; ++q) {
-            const int idx = lane + 64 * q;
-            if (idx >= G * NL) continue;
-            const int g = idx / NL, t = idx - g * NL;
-            const int ff = fbase + g;
-            if (ff >= a.n_obs) continue;
-            const int i = t / 6, jp = t - 6 * i;
-            if (keep_rec) a.praw[es][GEN ? a.rec_off[a.list[ff]] + 36 + i * 6 + jp : (int64_t)ff * a.PRAW + 21 + jp * K1 + i] = resa[q];
-        }
-    }
-
-    // 16 partial Grams per frame -> one, through LDS, in two halves of the triangle
-    double res[2][NQ];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        wsync();
-#pragma unroll
-        for (int t = 0; t < HALF; ++t) { const int e = h * HALF + t; if (e < NR) red[lane * LS + t] = acc[e < NR ? e : 0]; }
-        wsync();
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int idx = lane + 64 * q;                      // (group, entry) pairs
-            double sum = 0.0;
-            if (idx < G * HALF) {
-                const int g = idx / HALF, t = idx - g * HALF;
-                const double* src = red + (g * LPF) * LS + t;
-#pragma unroll
-                for (int l = 0; l < LPF; ++l) sum += src[l * LS];
-            }
-            res[h][q] = sum;
-        }
-    }
-    // scatter the upper triangle into the compact record  C (21) | [B|g] (6 x K1) | A (K1 x K1)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int idx = lane + 64 * q;
-            if (idx >= G * HALF) continue;
-            const int g = idx / HALF, t = idx - g * HALF, e = h * HALF + t;
-            const int ff = fbase + g;
-            if (e >= NR || ff >= a.n_obs) continue;
-            const uint32_t m = g_recmap<K, NLC, GEN>.d[e];
-            const double v = res[h][q];
-            double* rec = a.praw[es] + (GEN ? a.rec_off[a.list[ff]] : (int64_t)ff * a.PRAW);
-            if (keep_rec) {
-                rec[m & 0xffff] = v;
-                if ((m >> 16) != 0xffff) rec[m >> 16] = v;
-                if (!GEN && e == NR - 1) a.cost_f[ff] = v;               // the last entry is r x r
-            }
-            if constexpr (!GEN) {
-                if (fuse) {                                          // fused elimination: the same record in LDS (red is free: every sum is in registers)
-                    constexpr int GS_ = (praw_jl_off(K) + 9 + 6 * K1 + 1) & ~1;
-                    red[g * GS_ + (m & 0xffff)] = v;
-                    if ((m >> 16) != 0xffff) red[g * GS_ + (m >> 16)] = v;
-                }
-            }
-        }
-    }
-    // the frame's left Jacobian (phi -> rvec map of the elimination)
-    if (!GEN && active && keep_rec) for (int e = gl; e < 9; e += LPF) a.praw[es][(int64_t)f * a.PRAW + praw_jl_off(K) + e] = fc[FC_A + e];
-    if constexpr (!GEN) {
-        if (fuse) {
-            constexpr int GS_ = (praw_jl_off(K) + 9 + 6 * K1 + 1) & ~1;
-#pragma unroll
-            for (int q = 0; q < NQA; ++q) {
-                const int idx = lane + 64 * q;
-                if (idx >= G * NL) continue;
-                const int g = idx / NL, t = idx - g * NL, ci = t / 6, jp = t - 6 * ci;
-                red[g * GS_ + 21 + jp * K1 + ci] = resa[q];
-            }
-            if (lane_ok) for (int e = gl; e < 9; e += LPF) red[grp * GS_ + praw_jl_off(K) + e] = fc[FC_A + e];
-        }
-    }
-    if constexpr (!GEN) {
-        if (fuse) {
-            // the records are in LDS as well (written along with the global stores above): the elimination right here
-            wsync();
-            gram_fused_tail<K, LPF>(a, schur_lambda(st), red, a.partial + (int64_t)(blockIdx.x * CCAL_GRAMV_WPB + wave) * fused_red_size(K), grp, gl, lane_ok, active, slot_t, es, mc_t);
-        }
-    }
-#ifdef CCAL_STAMPS
-    if (!GEN && lane == 0) { const int wg = blockIdx.x * CCAL_GRAMV_WPB + wave; a.fcbuf[2 * wg] = (double)t_start; a.fcbuf[2 * wg + 1] = (double)wall_clock64(); a.fcbuf[8192 + 2 * wg] = (double)t_loop; a.fcbuf[8192 + 2 * wg + 1] = (double)t_after; }
-#endif
-}
-
-// the second library's developer switches compile k_gram1w and the OPENCV5 instantiations of k_gram1v's single-problem forms in
-#ifdef CCAL_DEV_SWITCHES
-constexpr bool kDevSwitches = true;
-#else
-constexpr bool kDevSwitches = false;
-#endif
-template <int MODEL, bool OF, int LPF, bool W, bool GEN>
 static hipError_t launch_gram1v_l(const FusedArgs& a, hipStream_t s) {
     constexpr int G = 64 / LPF;
-    const size_t lds = sizeof(double) * gram1_wave_lds<MODEL, OF, W>(LPF) * CCAL_GRAMV_WPB;
-    void (*kern)(const FusedArgs);
-    if constexpr (W) kern = k_gram1w<MODEL, OF, LPF, GEN>; else kern = k_gram1v<MODEL, OF, LPF, GEN>;
+    const size_t lds = sizeof(double) * gram1_wave_lds<MODEL, OF>(LPF) * CCAL_GRAMV_WPB;
+    void (*kern)(const FusedArgs) = k_gram1v<MODEL, OF, LPF, GEN>;
     static DynLdsGuard lds_guard;
     if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds, lds_guard); e != hipSuccess) return e;
     const int fpb = G * CCAL_GRAMV_WPB;
@@ -1086,39 +577,23 @@ static hipError_t launch_gram1v_l(const FusedArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3((a.n_obs + fpb - 1) / fpb), dim3(64 * CCAL_GRAMV_WPB), lds, s, a);
     return hipGetLastError();
 }
-// Lanes per frame: the cost model of ccal_gram_plan.hpp with k_gram1v's (one wavefront per SIMD) or k_gram1w's (two) constants.
+// Lanes per frame: the cost model of ccal_gram_plan.hpp with k_gram1v's constants (one wavefront per SIMD).
 // The second library's CCAL_GRAMV_LPF overrides.
-static int gram_lanes_per_frame(int n_obs, int avg_corners, bool two_per_simd, int64_t max_waves = kNoWaveCap, int share = 1) {
+static int gram_lanes_per_frame(int n_obs, int avg_corners, int64_t max_waves = kNoWaveCap, int share = 1) {
     static const int lpf_env = dev_env_int("CCAL_GRAMV_LPF", 0);
-    return lanes_per_frame(n_obs, avg_corners, gram1_lane_cost(two_per_simd), lpf_env, max_waves, share);
+    return lanes_per_frame(n_obs, avg_corners, gram1_lane_cost(false), lpf_env, max_waves, share);
 }
 template <int MODEL, bool OF, bool GEN>
 static hipError_t launch_gram1v_t(FusedArgs& a, hipStream_t s) {
-    // More wavefronts than SIMDs (>= 2000 frames): k_gram1w, two wavefronts per SIMD (10 000 frames: 40 vs 53 us).
-    // Below that every wavefront has a SIMD to itself and k_gram1v's all-register accumulators are a little faster.
-    // CCAL_GRAMV_LDSACC=0|1 forces one or the other.
-    static const int force = [] { const char* e = dev_env("CCAL_GRAMV_LDSACC"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-    constexpr int NCt = block_dim(MODEL, OF, false) + 1;
-    // larger triangles (KB4: 105 / 120 entries, OPENCV5: 120 / 136) do not fit two wavefronts per SIMD without scratch
-    // (one-focal KB4 through k_gram1w: 124 us instead of 64 at 10 000 frames): k_gram1v there
-    // (k_gram1w is not even instantiated for them: CCAL_GRAMV_LDSACC=1 has no effect there)
-    // The PRODUCT launchers never reach k_gram1w (UCM / EUCM from 2 000 frames go to k_gram2, use_gram2) nor any OPENCV5
-    // instantiation of k_gram1v (k_gram2 for every size): they are compiled into the second library only (CCAL_GRAM2=0 there)
-    constexpr bool W_OK = kDevSwitches && NCt * (NCt + 1) / 2 <= 91;
-    const bool w = W_OK && (force >= 0 ? force == 1 : a.n_obs >= 2000);
-    const int lpf = gram_lanes_per_frame(a.n_obs, a.avg_corners, w, fused_wave_cap(a, GEN), a.share);
+    const int lpf = gram_lanes_per_frame(a.n_obs, a.avg_corners, fused_wave_cap(a, GEN), a.share);
     set_fuse_plan(a, lpf, GEN);
-    return dispatch_lanes(lpf, hipErrorInvalidValue, [&](auto l) {
-        constexpr int LPF = decltype(l)::value;
-        if constexpr (W_OK) { if (w) return launch_gram1v_l<MODEL, OF, LPF, true, GEN>(a, s); }
-        return launch_gram1v_l<MODEL, OF, LPF, false, GEN>(a, s);
-    });
+    return dispatch_lanes(lpf, hipErrorInvalidValue, [&](auto l) { return launch_gram1v_l<MODEL, OF, decltype(l)::value, GEN>(a, s); });
 }
 template <bool GEN>
 static hipError_t launch_gram1v_m(int model, bool one_focal, FusedArgs& a, hipStream_t s) {
     return dispatch_model_focal(model, one_focal, hipErrorInvalidValue, [&](auto m, auto of) {
         constexpr int MODEL = decltype(m)::value;
-        if constexpr (MODEL == kOCV5 && !kDevSwitches) return hipErrorNotSupported;          // (OPENCV5: k_gram2 for every size)
+        if constexpr (MODEL == kOCV5) return hipErrorNotSupported;          // (OPENCV5: k_gram2 for every size, use_gram2)
         else return launch_gram1v_t<MODEL, decltype(of)::value, GEN>(a, s);
     });
 }
@@ -1126,7 +601,7 @@ static hipError_t launch_gram1v_m(int model, bool one_focal, FusedArgs& a, hipSt
 constexpr int kIterWpb = 4;
 constexpr size_t kLdsPerCu = 160 * 1024;
 template <int MODEL, bool OF>
-static constexpr size_t iter_lds_bytes(int lpf) { return sizeof(double) * gram1_wave_lds<MODEL, OF, false>(lpf) * kIterWpb; }
+static constexpr size_t iter_lds_bytes(int lpf) { return sizeof(double) * gram1_wave_lds<MODEL, OF>(lpf) * kIterWpb; }
 template <int MODEL, bool OF, int LPF>
 static hipError_t launch_gram_iter_l(FusedArgs& a, hipStream_t s) {
     constexpr int G = 64 / LPF;
@@ -1146,13 +621,13 @@ static constexpr size_t iter_static_lds() { return sizeof(HeadShared) + 4 * 2 * 
 // rows (= workgroups) of a single-launch group, 0 if the form does not apply; launch: the group is launched as well (*err)
 template <int MODEL, bool OF>
 static int iter_rows_t(int n_obs, int avg_corners, int share, bool launch, FusedArgs* a, hipStream_t s, hipError_t* err) {
-    // OPENCV5 in the product: only the batched form exists (k_gram1v_batch) - the row count without the single-problem launcher
-    constexpr bool LAUNCHER = MODEL != kOCV5 || kDevSwitches;
+    // OPENCV5: only the batched form exists (k_gram1v_batch) - the row count without the single-problem launcher
+    constexpr bool LAUNCHER = MODEL != kOCV5;
     // CCAL_ITER_ROWS: most rows (= workgroups, each of which reads every row of the launch before) for which a group is one
     // launch; 0 = never.  One wavefront per SIMD, every workgroup resident at once: <= 256 workgroups.
     static const int max_rows = std::min(dev_env_int("CCAL_ITER_ROWS", 256), 256);
     if (n_obs <= 0 || max_rows <= 0 || (launch && !LAUNCHER)) return 0;
-    const int lpf = gram_lanes_per_frame(n_obs, avg_corners, false, kNoWaveCap, share);
+    const int lpf = gram_lanes_per_frame(n_obs, avg_corners, kNoWaveCap, share);
     const int g = 64 / lpf, rows = (n_obs + g * kIterWpb - 1) / (g * kIterWpb);
     if (rows > max_rows || iter_lds_bytes<MODEL, OF>(lpf) + iter_static_lds<MODEL, OF>() > kLdsPerCu) return 0;
     if constexpr (LAUNCHER) {
@@ -1185,7 +660,7 @@ hipError_t launch_gram_iter_batch(int model, bool one_focal, int lpf, const Fuse
     });
 }
 // the lane mapping a single-launch group of this problem takes (what launch_gram_iter dispatches on)
-int fused_iter_lpf(int n_obs, int avg_corners, int share) { return gram_lanes_per_frame(n_obs, avg_corners, false, kNoWaveCap, share); }
+int fused_iter_lpf(int n_obs, int avg_corners, int share) { return gram_lanes_per_frame(n_obs, avg_corners, kNoWaveCap, share); }
 
 // CCAL_GRAM2_ITER=0 (second library) / -DCCAL_NO_GRAM2_ITER (A/B builds): k_gram1v's single-launch form at every size
 static bool use_gram2_iter(bool batch, int share) {
@@ -1200,9 +675,8 @@ int fused_iter_rows(int model, bool one_focal, int n_obs, int avg_corners, int K
     if (K != block_dim(model, one_focal, false) - 6) return 0;      // (the kernel's compile-time column count is the problem's)
     // OPENCV5 alone: k_gram2 (fewer AGPR copies) + reduce + head stays ahead - 625 frames GN 0.132 ms against 0.139 in the single-launch
     // form (112-double rows: two chunks per lane to sum, 4.9 us) - so only members of a lockstep batch take it (one launch per step
-    // for the whole batch beats n x three).  The second library's CCAL_ITER_OCV5=1 forces the single-launch form.
-    static const bool ocv5 = dev_env_int("CCAL_ITER_OCV5", 0) == 1;
-    if (model == kOCV5 && !ocv5 && !batch) return 0;
+    // for the whole batch beats n x three).
+    if (model == kOCV5 && !batch) return 0;
     // UCM / EUCM from 2 000 frames, a problem that has the GPU to itself: the single-launch form of the two-wavefronts-per-SIMD kernel
     // (k_gram2i, ccal_kernels_gram2.hip) - 10 000 frames: ~30 us per group against 36 with k_gram1v's 1 000 one-per-SIMD wavefronts
     if (use_gram2_iter(batch, share)) { const int r = gram2_iter_rows(model, one_focal, n_obs, avg_corners, K); if (r > 0) return r; }
@@ -1217,13 +691,14 @@ hipError_t launch_gram_iter(int model, bool one_focal, FusedArgs& a, hipStream_t
 
 // single-camera loop; a.fuse_elim in: fusion allowed, out: fusion done (then a.n_part = rows of partial sums, a.elim_fused = 1)
 // Which register Gram kernel.  k_gram2 (the block's rows on neighbouring lanes, ccal_kernels_gram2.hip) where it measured faster
-// (10 000 / 2 500 frames, us per build, k_gram2 vs k_gram1v|w): OPENCV5 47.1 / 25.6 vs 51.2 / 27.3, EUCM 35.8 / 21.1 vs 36.9 / 22.2
+// (10 000 / 2 500 frames, us per build, k_gram2 vs k_gram1v): OPENCV5 47.1 / 25.6 vs 51.2 / 27.3, EUCM 35.8 / 21.1 vs 36.9 / 22.2
 // (from 2 000 frames: two wavefronts per SIMD, no LDS accumulators; 625 frames 15.9 vs 14.2 with k_gram1v); KB4 since round 5
-// (neighbouring-lane form): 46.7 / 24.4 vs 49.7 / 25.8, one focal 45.9 vs 47.2.  CCAL_GRAM2=0|1 forces (second library).
+// (neighbouring-lane form): 46.7 / 24.4 vs 49.7 / 25.8, one focal 45.9 vs 47.2.  CCAL_GRAM2=0|1 forces (second library) for
+// UCM / EUCM / KB4.  OPENCV5 takes k_gram2 whatever the switch says: k_gram1v has no single-problem instantiation for it.
 static bool use_gram2(int model, int n_obs) {
     static const int force = [] { const char* e = dev_env("CCAL_GRAM2"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-    if (force >= 0) return force == 1;
     if (model == kOCV5) return true;
+    if (force >= 0) return force == 1;
     return n_obs >= 2000;
 }
 static int gram2_lpf_force() { static const int v = dev_env_int("CCAL_GRAM2_LPF", 0); return v; }
@@ -1237,101 +712,6 @@ hipError_t launch_gram1v_general(int model, bool one_focal, const FusedArgs& a0,
     if (use_gram2(model, a0.n_obs)) { a.lpf_force = gram2_lpf_force(); return launch_gram2_general(model, one_focal, a, s); }
     return launch_gram1v_m<true>(model, one_focal, a, s);
 }
-#ifdef CCAL_LEGACY_KERNELS
-template <int MODEL, bool OF>
-static hipError_t launch_gram1_t(const FusedArgs& a, hipStream_t s) {
-    constexpr int WS = FC_N0P + GRAM_TILE_CORNERS * 34;
-    const size_t lds = sizeof(double) * WS * WAVES_PER_BLOCK;
-    static DynLdsGuard lds_guard;
-    if (hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&k_gram1<MODEL, OF>), lds, lds_guard); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_gram1<MODEL, OF>), dim3((a.n_obs + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_gram1(int model, bool one_focal, const FusedArgs& a, hipStream_t s) {
-    return dispatch_model_focal(model, one_focal, hipErrorInvalidValue, [&](auto m, auto of) { return launch_gram1_t<decltype(m)::value, decltype(of)::value>(a, s); });
-}
-
-#else
-hipError_t launch_gram1(int, bool, const FusedArgs&, hipStream_t) { return hipErrorNotSupported; }      // not in the product build
-#endif
-
-// ---------------------------------------------------------------------------------------------
-// The separate elimination launch - superseded by the Gram kernels' fused tail (gram_fused_tail) for every model and size; kept
-// in the SECOND library only (-DCCAL_LEGACY_KERNELS), where the matrix-core Gram k_gram1 and CCAL_FUSE_ELIM=0 still use it and
-// tools/count_flops.py reads the elimination's operation count off its ISA.
-// ---------------------------------------------------------------------------------------------
-#ifdef CCAL_LEGACY_KERNELS
-// k_schur1m: the elimination with FOUR frames per wavefront (16 lanes each), one pass per wavefront: the grid covers all frames
-// (n_pw = 4 ceil(n_obs / 16)).
-constexpr int SCHUR1M_WAVES = 8;          // 32 frames per workgroup: a quarter of the partial sums k_head / k_reduce1 have to add up
-template <int K>
-__global__ __launch_bounds__(64 * SCHUR1M_WAVES) void k_schur1m(const FusedArgs a) {
-    constexpr int K1 = K + 1, NA = K1 * K1;
-    constexpr int NQ = (NA + 15) / 16;                    // A / Y^T Y entries per lane
-    constexpr int REC = 21 + 6 * K1 + NA + 9;             // C (21) | [B|g] (6 x K1) | A (K1 x K1) | J_l (9)
-    constexpr int GS = (REC + 6 * K1 + 1) & ~1;           // per frame in LDS: record | Y (6 x K1); later the frame's sums
-    constexpr int NF = 4 * SCHUR1M_WAVES;                 // frames per workgroup
-    static_assert(2 * NA + 2 <= GS, "a frame's sums reuse its record row");
-    __shared__ double smem[NF * GS];
-    const DevState* st = a.st;
-    if (st->done) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 4, gl = lane & 15;
-    const int f = (blockIdx.x * SCHUR1M_WAVES + wave) * 4 + grp;
-    const bool active = f < a.n_obs;
-    double* R = smem + (wave * 4 + grp) * GS;
-    double* Ym = R + REC;
-    const int set = schur_set(st);
-    const double lambda = schur_lambda(st);
-    double accA[NQ], accY[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) { accA[q] = 0.0; accY[q] = 0.0; }
-    double mcv = 0.0;
-    if (active) {
-        const double* rec = a.praw[set] + (int64_t)f * a.PRAW;
-        for (int e = gl; e < REC; e += 16) R[e] = rec[e];
-        if (gl == 0) mcv = a.mc_f[f];
-    }
-    const int slot = active ? a.obs_slot[f] : 0;
-    wsync();
-    const bool ok = eliminate_frame<K, 16>(R, Ym, gl, active, lambda, a.min_diag, a.max_diag,
-                                          a.pf[set] + (int64_t)slot * a.PF, a.PF, accA, accY);
-    // the frames of the workgroup combine in LDS (fixed order), one flush per workgroup; a frame's sums reuse its row
-    wsync();
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int e = gl + 16 * q;
-        if (e < NA) { R[e] = accA[q]; R[NA + e] = accY[q]; }
-    }
-    if (gl == 0) { R[2 * NA] = mcv; R[2 * NA + 1] = (active && !ok) ? 1.0 : 0.0; }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 2 * NA + 2; e += 64 * SCHUR1M_WAVES) {
-        double t = 0.0;
-#pragma unroll
-        for (int g = 0; g < NF; ++g) t += smem[g * GS + e];
-        a.partial[(int64_t)blockIdx.x * (2 * NA + 2) + e] = t;
-    }
-}
-hipError_t launch_schur1m(FusedArgs& a, hipStream_t s) {
-    const dim3 grid((a.n_obs + 4 * SCHUR1M_WAVES - 1) / (4 * SCHUR1M_WAVES)), blk(64 * SCHUR1M_WAVES);
-    a.n_part = (int32_t)grid.x;
-    if (grid.x == 0) return hipSuccess;
-    switch (a.K) {
-        case 4: hipLaunchKernelGGL(k_schur1m<4>, grid, blk, 0, s, a); break;
-        case 5: hipLaunchKernelGGL(k_schur1m<5>, grid, blk, 0, s, a); break;
-        case 6: hipLaunchKernelGGL(k_schur1m<6>, grid, blk, 0, s, a); break;
-        case 7: hipLaunchKernelGGL(k_schur1m<7>, grid, blk, 0, s, a); break;
-        case 8: hipLaunchKernelGGL(k_schur1m<8>, grid, blk, 0, s, a); break;
-        case 9: hipLaunchKernelGGL(k_schur1m<9>, grid, blk, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-#else
-hipError_t launch_schur1m(FusedArgs&, hipStream_t) { return hipErrorNotSupported; }       // not in the product build
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // k_reduce1: red[e] = sum over workgroups of partial[w][e], fixed order (no atomics: bitwise reproducible)
 // ---------------------------------------------------------------------------------------------

@@ -52,7 +52,7 @@ __host__ __device__ constexpr int g2_fullcol(int row, int a) {
     return a == 0 ? (row ? 1 : 0) : (a == 1 ? (row ? 3 : 2) : a + 2);
 }
 // where entry (i <= j) of the full triangle goes in the per-frame record: dst | mirror << 16 (0xffff = none); the maps of
-// RecMap (ccal_kernels_fused.hip) with W = 0
+// RecMap (ccal_kernels_fused.hip)
 template <int K, bool GEN>
 __host__ __device__ constexpr uint32_t g2_rec_dst(int i, int j) {
     constexpr int D = K + 6, K1 = K + 1;
@@ -228,7 +228,7 @@ __device__ __forceinline__ double g2_from_partner(double v) {
 }
 
 // LPF = lanes per frame, EVEN: LPF corners of a frame per pass, every lane evaluates one.  The frame's lanes are contiguous (grp = lane / LPF), so
-// the prologue and the fused tail are those of k_gram1w.
+// the prologue and the fused tail are those of k_gram1v.
 // The body of a workgroup.  BIN = false: workgroup `wg` of a launch in which every frame has LPF lanes; the frames are a.n_obs
 // observation frames in their own order (GEN: a.list).  BIN = true (single camera, ragged frames): the launch is cut into BINS of
 // frames sorted by corner count, each with the lanes per frame ITS frames need (k_gram2b below) - this workgroup is number `wg` of a bin

@@ -1,7 +1,6 @@
 // Entry points of the SECOND library only (-DCCAL_TEST_HOOKS, libccal_hip_legacy.so): what the tests need to reach code that no
 // call of include/ccal.h reaches with data of their choice.  Not declared in the header, not in _ffi.SYMBOLS; the product
-// library links this translation unit as an empty object.
-#ifdef CCAL_TEST_HOOKS
+// library does not contain this translation unit.
 #include "ccal_call.hpp"
 #include "ccal_device.hpp"
 
@@ -200,4 +199,3 @@ extern "C" int ccal_test_guard_damage(ccal_ctx* ctx, int slice, int from_end, in
     return blk.finish(where);
     CCAL_API_CATCH(ctx)
 }
-#endif

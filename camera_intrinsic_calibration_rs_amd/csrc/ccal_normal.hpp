@@ -113,7 +113,7 @@ struct NormalWs {
     int cur = 0;                               // which G buffer holds the current point
     bool red_fused = false;                    // the last ccal_build_normal_dev left its sums in fws->red (single camera)
     bool gstate_is_eval = false;               // d_gstate already says "first evaluation of set 0" (ccal_build_normal)
-    bool register_gram = false;                // general loop: every camera's blocks come from k_gram1v / k_gram1w (GEN record format, caminfo NCP = 0)
+    bool register_gram = false;                // general loop: every camera's blocks come from k_gram1v / k_gram2 (GEN record format, caminfo NCP = 0)
     int64_t g_len = 0;
     DevState* d_gstate = nullptr;              // general loop: optimizer state on the device,
     HostStatus* h_gstatus = nullptr;           //   its published copy (pinned, host-coherent)
@@ -256,7 +256,10 @@ constexpr size_t kZeroCopyBytes = 96 * 1024;
 // launchers (ccal_kernels_normal.hip).  Host-driven form: `cand` / gbuf / lambda select parameter set, G buffer and
 // damping.  Device-resident form (st != NULL, *_dev): set 0 = (p->d_*, G[w->cur]), set 1 = (p->d_*_c, G[w->cur ^ 1]),
 // the kernels pick the current set by st->cur, take lambda from st->lambda and do nothing once st->done is set.
+#ifdef CCAL_LEGACY_KERNELS      // second library only (ccal_legacy_normal.hip): the matrix-core Gram, host-driven and device-resident form
 hipError_t launch_gram(const ccal_problem* p, int cam, bool use_candidate_params, int gbuf, hipStream_t s);
+hipError_t launch_gram_dev_mfma(const ccal_problem* p, int cam, const DevState* st, hipStream_t s);
+#endif
 hipError_t launch_gram_dev(const ccal_problem* p, int cam, const DevState* st, hipStream_t s);
 hipError_t launch_gram_dev_all(const ccal_problem* p, const DevState* st, hipStream_t s);     // every camera: one launch if w->merged_gram, else one per camera
 hipError_t launch_schur(const ccal_problem* p, int gbuf, double lambda, double min_diag, double max_diag, hipStream_t s,

@@ -36,8 +36,13 @@ static int enqueue_gram(ccal_problem* p, bool cand, int gbuf) {
         return CCAL_OK;
     }
     if (w->register_gram) { ctx->err = "enqueue_gram: candidate sets go through the device loop"; return CCAL_ERR_UNSUPPORTED; }
+#ifdef CCAL_LEGACY_KERNELS      // second library: the matrix-core pair (the product's normal_ws_ensure never plans a workspace without the register Gram)
     for (int c = 0; c < p->n_cams; ++c) HIP_TRY(ctx, launch_gram(p, c, cand, gbuf, ctx->stream));
     return CCAL_OK;
+#else
+    ctx->err = std::string("enqueue_gram: the matrix-core Gram: ") + hipGetErrorString(hipErrorNotSupported);
+    return CCAL_ERR_HIP;
+#endif
 }
 
 // The step's one collective: in-place sum of `n` doubles over the ranks, ordered on the context stream.  Native RCCL
@@ -106,10 +111,19 @@ static hipError_t enqueue_fused_gram_schur(const ccal_problem* p, FusedArgs& fa,
     // CCAL_FUSE_ELIM=0 (developer switch, read when the problem's workspace is created): always the separate elimination launch
     const bool valu = fused_use_valu_gram(p);
     fa.fuse_elim = (p->nws->fws->fuse_elim && valu) ? 1 : 0; fa.elim_fused = 0;
-    hipError_t e = valu ? launch_gram1v(p->cams[0].model, p->one_focal, fa, st) : launch_gram1(p->cams[0].model, p->one_focal, fa, st);
+    // the matrix-core Gram (CCAL_GRAM=mfma) and the separate elimination launch (behind it, or CCAL_FUSE_ELIM=0) exist in the
+    // second library only (ccal_legacy_fused.hip)
+    hipError_t e = hipErrorNotSupported;
+    if (valu) e = launch_gram1v(p->cams[0].model, p->one_focal, fa, st);
+#ifdef CCAL_LEGACY_KERNELS
+    else e = launch_gram1(p->cams[0].model, p->one_focal, fa, st);
+#endif
     if (e != hipSuccess) return e;
     if (fa.elim_fused) return hipSuccess;      // the Gram kernel eliminated its frames' pose blocks itself: fa.n_part rows of partial sums
-    return schur_m ? launch_schur1m(fa, st) : hipErrorNotSupported;      // (second library: matrix-core Gram / CCAL_FUSE_ELIM=0)
+#ifdef CCAL_LEGACY_KERNELS
+    if (schur_m) return launch_schur1m(fa, st);
+#endif
+    return hipErrorNotSupported;
 }
 // ... + k_reduce1: the reduced sums in fws->red (the all-reduce buffer of sharded solves; ccal_build_normal_dev)
 static hipError_t enqueue_fused_system(const ccal_problem* p, FusedArgs& fa, bool schur_m, hipStream_t st) {

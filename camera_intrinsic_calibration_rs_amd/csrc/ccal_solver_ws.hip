@@ -143,9 +143,9 @@ int normal_ws_ensure_general(ccal_problem* p) {
     std::vector<int64_t> goff(p->n_obs);
     std::vector<int32_t> caminfo(p->n_cams * 4);
     int64_t gl = 0;
-    // Register Gram kernels + record format for every camera (k_gram1v / k_gram1w, GEN; k_schur expands the records).
-    // CCAL_GENERAL_GRAM=mfma: the matrix-core kernel k_gram with its 16 x 16 / 32-stride tiles (19-column other-camera
-    // blocks), kept as the independent second implementation the tests compare against.
+    // Register Gram kernels + record format for every camera (k_gram1v / k_gram2, GEN; k_schur expands the records).
+    // CCAL_GENERAL_GRAM=mfma: the matrix-core kernel k_gram (ccal_legacy_normal.hip) with its 16 x 16 / 32-stride tiles
+    // (19-column other-camera blocks), kept as the independent second implementation the tests compare against.
 #ifdef CCAL_LEGACY_KERNELS
     { const char* e = dev_env("CCAL_GENERAL_GRAM"); w->register_gram = !(e && e[0] == 'm') || w->schur_wpb == 1; }      // the matrix-core pair: four-wavefront elimination only
 #else

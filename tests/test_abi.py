@@ -53,6 +53,33 @@ def test_no_test_hooks_in_the_product_library():
     assert b"CCAL_TEST_GUARD_SLICES" in legacy                         # the one-shot calls' slice guards (tests/test_gpu_guard.py)
 
 
+def _defined_symbols(path):
+    import subprocess
+    nm = "/opt/rocm/lib/llvm/bin/llvm-nm"
+    if not os.path.exists(nm):
+        nm = "nm"
+    out = subprocess.run([nm, "-C", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    # "<address> <type> <demangled name>": the name may hold spaces
+    return [ln.split(None, 2)[2] for ln in out.splitlines() if len(ln.split(None, 2)) == 3]
+
+
+def test_superseded_kernels_only_in_the_second_library():
+    """The matrix-core Gram kernels (k_gram1, k_gram), the separate elimination launch (k_schur1m) and their launchers live in
+    units only the second library contains (csrc/ccal_legacy_*.hip): the product defines none of them - no stub either - the
+    second library all of them.  k_gram1w (LDS accumulators) is gone from both."""
+    superseded = ["launch_gram1(", "launch_schur1m(", "ccal::launch_gram(", "k_gram1<", "k_schur1m<", "k_gram<"]
+    product = _defined_symbols(_ffi.LIB_PATH)
+    legacy = _defined_symbols(_ffi.LEGACY_LIB_PATH)
+    assert any("k_gram1v<" in s for s in product) and any("launch_gram1v(" in s for s in product)     # the listing does see kernels and launchers
+    for pat in superseded:
+        hits = [s for s in product if pat in s]
+        assert not hits, f"the product library defines {pat!r}: {hits[:3]}"
+        assert any(pat in s for s in legacy), f"the second library does not define {pat!r}"
+    for name, syms in (("product", product), ("second", legacy)):
+        hits = [s for s in syms if "k_gram1w" in s]
+        assert not hits, f"the {name} library still has k_gram1w: {hits[:3]}"
+
+
 def test_host_only_entry_points():
     lib = _ffi.load()
     assert lib.ccal_version().startswith(b"ccal-mi355x")

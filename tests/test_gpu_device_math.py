@@ -1,7 +1,7 @@
 """GPU: the six pieces of f64 device math of csrc/ccal_device.hpp on the named inputs of tests/device_math_cases.py, against the
 mpmath yardstick of tests/device_math_ref.py.
 
-The inputs go in through ccal_test_device_math, an entry point of the second library only (csrc/ccal_test_hooks.hip): one element
+The inputs go in through ccal_test_device_math, an entry point of the second library only (csrc/ccal_legacy_test_hooks.hip): one element
 per lane, the header's functions as they are.  Bounds are the header's own written claims, or derived from the arithmetic:
 
     RCP, SQRT_RSQRT   2 ulp                        the header's "<= 1-2 ulp"

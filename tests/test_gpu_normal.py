@@ -211,8 +211,8 @@ def test_lm_hard_start_never_crashes(gpu_ctx):
 @pytest.mark.parametrize("n_frames", [700, 1500, 2500, 5000])
 def test_solve_all_lane_mappings(gpu_ctx, oracle, n_frames):
     """The register-Gram kernels map 64 / 32 / 16 lanes to a frame depending on the problem size (<= 1024, <= 4800,
-    more) and keep all accumulators in registers below 2000 frames (k_gram1v) or part of them in LDS above
-    (k_gram1w): every combination against the oracle, ragged frames included."""
+    more); below 2000 frames a lane accumulates both rows of a corner (k_gram1v), above a corner's two rows sit on neighbouring
+    lanes (k_gram2): every combination against the oracle, ragged frames included."""
     sp = synth.make_problem(n_frames, "eucm", ragged=True, outlier_frac=0.01)
     gp, op = _pair(gpu_ctx, oracle, sp)
     intr, poses, _, rep = gp.solve(sp.intr0, sp.poses0, opts=default_opts(_ffi.METHOD_GN))
@@ -714,8 +714,8 @@ def test_two_equal_cameras_elimination_kernels(dev_ctx, oracle, model, one_focal
 
 @pytest.mark.parametrize("model,frames", [("eucm", 2600), ("kb4", 2100), ("eucm", 300)])
 def test_fused_elimination_equals_separate_launch(gpu_ctx, dev_ctx, oracle, model, frames, monkeypatch):
-    """The Gram kernels eliminate their frames' pose blocks in their own tail (k_gram1w from 2 000 frames up for UCM / EUCM,
-    k_gram1v otherwise; re-elimination groups of LM run there too).  Against the separate elimination launch
+    """The Gram kernels eliminate their frames' pose blocks in their own tail (k_gram2 from 2 000 frames up and for OPENCV5,
+    k_gram1v below; re-elimination groups of LM run there too).  Against the separate elimination launch
     (CCAL_FUSE_ELIM=0: k_schur1m) and the oracle, from a poor start that makes LM reject steps and miss speculations."""
     sp = synth.make_problem(frames, model, init_perturb=0.6, outlier_frac=0.03, seed=5, ragged=True)
     gp, op = _pair(gpu_ctx, oracle, sp)
@@ -749,7 +749,7 @@ def test_fused_elimination_equals_separate_launch(gpu_ctx, dev_ctx, oracle, mode
             assert (rep.lm_spec_hits, rep.lm_spec_misses) == (rep2.lm_spec_hits, rep2.lm_spec_misses)
             rejected = rep.lm_rejected + rep.lm_spec_misses
     if (model, frames) == ("eucm", 2600):
-        assert rejected >= 1                                 # the re-elimination path of k_gram1w did run
+        assert rejected >= 1                                 # the re-elimination path of the Gram kernel did run
     gs.close()
 
 

@@ -1,7 +1,7 @@
 """GPU: the radix select behind validation()'s two numbers (csrc/ccal_kernels_stats.hip: k_sel_one, k_sel_hist, sel_advance,
 k_sel_sum, k_sel_finish) on raw values, against the exact integer reference of tests/order_stats_ref.py.
 
-The values go in through ccal_test_order_stats, an entry point of the second library only (csrc/ccal_test_hooks.hip): it uploads
+The values go in through ccal_test_order_stats, an entry point of the second library only (csrc/ccal_legacy_test_hooks.hip): it uploads
 them and calls order_stats_block, the multi-GPU path's call - the kernels are the product's (one object file in both libraries).
 
     median    the reference's BIT PATTERN (compared as uint64: also tells +0.0 from -0.0)

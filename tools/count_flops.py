@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Developer tool: exact FP64 operation counts of the mode-N kernels, read off the gfx950 ISA hipcc generates (not an
-estimate): compiles ccal_kernels_fused.hip to assembly, finds the corner loop of the Gram kernel (the innermost loop
+estimate): compiles the Gram units to assembly, finds the corner loop of the Gram kernel (the innermost loop
 that holds the v_fma_f64 stream) and counts, per lane and iteration = per corner,
     v_fma_f64 / v_fmac_f64 (2 flop), v_mul_f64 / v_add_f64 (1 flop), ds_add_f64 (1 flop, executed by the LDS),
 and the other FP64 VALU instructions that occupy the same issue slots (rcp / rsq seeds, ldexp, conversions).  The
-per-frame elimination kernel (k_schur1m) has no loop: its whole body is counted per lane (16 lanes per frame).
+per-frame elimination kernel (k_schur1m, ccal_legacy_fused.hip: second library only) has no loop: its whole body is counted per lane (16 lanes per frame).
 Writes profiles/<tag>/flops.json, which bench.py reads for extra.mode_N_roofline.
 
     python tools/count_flops.py r02
@@ -91,24 +91,23 @@ def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
     bodies, regs = {}, {}
     with tempfile.TemporaryDirectory() as td:
-        for tu in ("ccal_kernels_fused", "ccal_kernels_gram2", "ccal_kernels_schurq"):
+        for tu in ("ccal_kernels_fused", "ccal_legacy_fused", "ccal_kernels_gram2", "ccal_kernels_schurq"):
             s = os.path.join(td, tu + ".s")
-            # (-DCCAL_LEGACY_KERNELS: the separate elimination kernel k_schur1m - whose body is what the Gram kernels' fused tail runs -
-            #  and the superseded Gram kernels exist in the second library only)
+            # (the second library's macros: ccal_legacy_fused - the separate elimination kernel k_schur1m, whose body is what the Gram
+            #  kernels' fused tail runs, and the matrix-core Gram k_gram1 - compiles with them only)
             subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "-S",
                                    "-DCCAL_LEGACY_KERNELS", "-DCCAL_DEV_SWITCHES", "--cuda-device-only", "-o", s, os.path.join(SRC, tu + ".hip")], stderr=subprocess.DEVNULL)
             asm = open(s).read()
             bodies.update(kernel_bodies(asm)); regs.update(registers(asm))
-    out = {"source": "gfx950 ISA of ccal_kernels_fused.hip and ccal_kernels_gram2.hip (hipcc -O3 -ffp-contract=fast), counted by tools/count_flops.py",
+    out = {"source": "gfx950 ISA of ccal_kernels_fused.hip, ccal_legacy_fused.hip and ccal_kernels_gram2.hip (hipcc -O3 -ffp-contract=fast), counted by tools/count_flops.py",
            "fp64_vector_peak_tflops": 78.6, "kernels": {}}
-    # model ids: 0 UCM 1 EUCM 2 KB4 3 OPENCV5; k_gram1w<MODEL, OF, LPF>, k_gram1v<...>, k_gram1<MODEL, OF>, k_schur1m<K>
+    # model ids: 0 UCM 1 EUCM 2 KB4 3 OPENCV5; k_gram1v<MODEL, OF, LPF, GEN, ITER>, k_gram1<MODEL, OF>, k_schur1m<K>
     names = {0: "UCM", 1: "EUCM", 2: "KB4", 3: "OPENCV5"}
     want = {}
     for m, nm in names.items():
         for of in (0, 1):
             focal = "one-focal" if of else "two-focal"
             # the per-corner count does not depend on the lanes-per-frame instantiation: read it off the 12-lane one
-            want[f"k_gram1w<{nm},{focal}>"] = f"k_gram1wILi{m}ELb{of}ELi12ELb0EE"
             want[f"k_gram1v<{nm},{focal}>"] = f"k_gram1vILi{m}ELb{of}ELi12ELb0ELb0EE"       # <MODEL, OF, LPF, GEN = false, ITER = false>
             want[f"k_gram1<{nm},{focal}>"] = f"k_gram1ILi{m}ELb{of}EE"
             want[f"k_gram2<{nm},{focal}>"] = f"k_gram2ILi{m}ELb{of}ELi12ELb0EE"         # <MODEL, OF, LPF, GEN = false>
