@@ -61,6 +61,11 @@ class Report(C.Structure):
     ]
 
 
+class CovReport(C.Structure):             # ccal_cov_report
+    _fields_ = [("status", C.c_int32), ("bad_slot", C.c_int32), ("dof", C.c_int64), ("n_free", C.c_int32), ("n_posed", C.c_int32),
+                ("cost", C.c_double), ("sigma2", C.c_double), ("leverage_sum", C.c_double), ("reserved_", C.c_int32 * 4)]
+
+
 class ModelConventions(C.Structure):
     _fields_ = [("kb4_small_radius", C.c_double), ("dist_lo", (C.c_double * 5) * 4), ("dist_hi", (C.c_double * 5) * 4),
                 ("unproject_small_radius", C.c_double), ("ocv5_order", C.c_int32 * 5), ("reserved_", C.c_int32)]
@@ -293,6 +298,8 @@ SYMBOLS = [
     ("ccal_grey_dev", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(GreyOpts)]),
     ("ccal_reprojection_errors", C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     ("ccal_validation", C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    # calibration uncertainty: covariances and leverage
+    ("ccal_covariance", C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, C.POINTER(CovReport)]),
 ]
 
 LEGACY_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libccal_hip_legacy.so")

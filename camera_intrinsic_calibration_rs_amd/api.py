@@ -609,6 +609,115 @@ def validation(cam_idx: int, final_result: GenericModel, rtvec_list: Dict[int, R
         return prob.validation(0, _intr_matrix([final_result]), poses, None)
 
 
+@dataclasses.dataclass
+class Uncertainty:
+    """How far to trust a finished calibration (engine.Problem.covariance, the rule at ccal_covariance in include/ccal.h).
+    calibration_uncertainty: param_names / param_std / param_corr are the camera's; rig_uncertainty: lists with one entry per
+    camera, and extr_std [n_cams, 6] (row 0 zeros) beside them.  Standard deviations are in the parameters' own units (px, rad, m);
+    a fixed parameter has 0 (and a NaN-free 0 correlation row).  pose_std / pose_cov: per frame, rvec | tvec as the solver steps
+    in them.  leverage: {frame: {feature id: h}} - rig_uncertainty: one such dict per camera - h in [0, 2], their sum over all
+    corners = report.n_free.  cov_cam: the reduced system's whole covariance [K, K] in the order of ccal_build_normal."""
+    sigma: float
+    param_names: list
+    param_std: object
+    param_corr: object
+    pose_std: Dict[int, np.ndarray]
+    pose_cov: Dict[int, np.ndarray]
+    leverage: object
+    report: object
+    cov_cam: np.ndarray
+    extr_std: Optional[np.ndarray] = None
+
+
+def _corr(cov: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(standard deviations, correlation matrix) of a covariance; rows and columns of zero variance are 0."""
+    std = np.sqrt(np.maximum(np.diag(cov), 0.0))
+    inv = np.divide(1.0, std, out=np.zeros_like(std), where=std > 0)
+    return std, cov * inv[:, None] * inv[None, :]
+
+
+def _camera_block(model: GenericModel, cov_cam: np.ndarray, col: int, xy_same_focal: bool):
+    """(names, std, corr) of one camera's params() vector out of the reduced system's covariance, whose block starts at column
+    `col`; under one focal fy repeats fx's column."""
+    names = list(_MODEL_KEYS[model.kind])
+    idx = [col + (0 if i == 0 else i - 1) for i in range(len(names))] if xy_same_focal else [col + i for i in range(len(names))]
+    std, corr = _corr(cov_cam[np.ix_(idx, idx)])
+    return names, std, corr
+
+
+def _uncertainty(prob, cams, slots, use, frames, xy_same_focal, intr, poses, extr) -> Uncertainty:
+    res = prob.covariance(intr, poses, extr)
+    rep = res.report
+    col, blocks, extr_std = 0, [], np.zeros((len(cams), 6))
+    for c, m in enumerate(cams):
+        blocks.append(_camera_block(m, res.cov_cam, col, xy_same_focal))
+        col += len(m._params) - (1 if xy_same_focal else 0)
+        if c > 0:
+            extr_std[c] = np.sqrt(np.maximum(np.diag(res.cov_cam)[col:col + 6], 0.0))
+            col += 6
+    posed = [s for s in range(len(slots)) if res.slot_status[s] == 0]
+    pose_cov = {slots[s]: res.cov_poses[s].copy() for s in posed}
+    pose_std = {fi: np.sqrt(np.maximum(np.diag(c), 0.0)) for fi, c in pose_cov.items()}
+    lev = [dict() for _ in cams]
+    at = 0
+    for fi in slots:                                     # the corner order of _flatten: slot, camera, sorted feature ids
+        for c, idxs in enumerate(use):
+            if fi not in idxs:
+                continue
+            ids = sorted(frames[c][fi].features.keys())
+            lev[c][fi] = {k: float(res.leverage[at + j]) for j, k in enumerate(ids)}
+            at += len(ids)
+    one = len(cams) == 1
+    return Uncertainty(sigma=float(np.sqrt(rep.sigma2)), param_names=blocks[0][0] if one else [b[0] for b in blocks],
+                       param_std=blocks[0][1] if one else [b[1] for b in blocks],
+                       param_corr=blocks[0][2] if one else [b[2] for b in blocks], pose_std=pose_std, pose_cov=pose_cov,
+                       leverage=lev[0] if one else lev, report=rep, cov_cam=res.cov_cam, extr_std=None if one else extr_std)
+
+
+def calibration_uncertainty(frame_feature_list: Sequence[Optional[FrameFeature]], model: GenericModel,
+                            rtvec_map: Dict[int, RvecTvec], xy_same_focal: bool = False, disabled_distortions: int = 0,
+                            fixed_focal: bool = False, ctx: Optional[Context] = None) -> Uncertainty:
+    """The uncertainty of a finished single-camera calibration (model, rtvec_map: what calib_camera returned, with the same
+    xy_same_focal / disabled_distortions / fixed_focal): standard deviations and correlations of the camera parameters, the
+    covariance of every frame's pose and the leverage of every detection, evaluated on the device at that point."""
+    valid = [i for i in sorted(rtvec_map.keys()) if i < len(frame_feature_list) and frame_feature_list[i] is not None]
+    if not valid:
+        raise ValueError("calibration_uncertainty: no frame with both detections and a pose")
+    slots, obs_cam, obs_slot, offs, X, U = _flatten([frame_feature_list], [valid])
+    d, keep = make_desc(1, [model.model_id], [model.width()], [model.height()], xy_same_focal, len(slots), obs_cam, obs_slot, offs,
+                        X[:, 0], X[:, 1], X[:, 2], U[:, 0], U[:, 1], 1.0)
+    with _Opened(ctx, None, d, keep) as prob:
+        intr = _intr_matrix([model])
+        prob.disable_distortions(disabled_distortions, intr)
+        if fixed_focal:
+            prob.fix_param(0, 0)
+        poses = np.stack([rtvec_map[i].as6() for i in slots])
+        return _uncertainty(prob, [model], slots, [valid], [frame_feature_list], xy_same_focal, intr, poses, None)
+
+
+def rig_uncertainty(cameras: Sequence[GenericModel], t_cam_i_0: Sequence[RvecTvec], board_rtvecs: Dict[int, RvecTvec],
+                    cams_detected_feature_frames: Sequence[Sequence[Optional[FrameFeature]]], xy_same_focal: bool = False,
+                    disabled_distortions: int = 0, fixed_focal: bool = False, ctx: Optional[Context] = None) -> Uncertainty:
+    """calibration_uncertainty for the joint problem of a rig (cameras, t_cam_i_0, board_rtvecs: what
+    calib_all_camera_with_extrinsics returned - board_rtvecs the poses T_0_b): per-camera parameter blocks, the extrinsics'
+    standard deviations, every board pose's covariance and per-camera leverages."""
+    n_cams = len(cameras)
+    cam_rtvecs = [{fi: rt for fi, rt in board_rtvecs.items() if fi < len(cams_detected_feature_frames[c])
+                   and cams_detected_feature_frames[c][fi] is not None} for c in range(n_cams)]
+    # (_joint_problem_inputs derives T_0_b from per-camera poses; here the board poses themselves are given and replace what it derives)
+    built = _joint_problem_inputs(cameras, t_cam_i_0, cam_rtvecs, cams_detected_feature_frames, xy_same_focal)
+    if built is None:
+        raise ValueError("rig_uncertainty: no frame with both detections and a pose")
+    d, keep, slots, intr, poses, extr = built
+    poses = np.stack([board_rtvecs[fi].as6() for fi in slots])
+    with _Opened(ctx, None, d, keep) as prob:
+        prob.disable_distortions(disabled_distortions, intr)
+        if fixed_focal:
+            prob.fix_param(0, 0)
+        use = [sorted(cam_rtvecs[c].keys()) for c in range(n_cams)]
+        return _uncertainty(prob, list(cameras), slots, use, cams_detected_feature_frames, xy_same_focal, intr, poses, extr)
+
+
 _REFINE_MIN_POINTS = 4
 
 

@@ -319,7 +319,7 @@ void ccal_problem_destroy(ccal_problem* p) {
         if (ctx->own_stream && ctx->stream) (void)hipStreamSynchronize(ctx->stream); else (void)hipDeviceSynchronize();
         (void)hipGetLastError();
     }
-    void* ptrs[] = { p->d_block, p->d_r, p->d_J, p->d_err, p->d_scratch };          // (corner arrays, frame tables, parameter arrays: slices of d_block)
+    void* ptrs[] = { p->d_block, p->d_r, p->d_J, p->d_err, p->d_scratch, p->d_cov };          // (corner arrays, frame tables, parameter arrays: slices of d_block)
     for (void* q : ptrs) if (q) ctx_release(ctx, q, false);
     normal_ws_destroy(p);
     const bool counted = p->counted;

@@ -267,6 +267,7 @@ struct ccal_problem {
     ccal::NormalWs* nws = nullptr;
     // lazily sized scratch for host<->device staging of ccal_eval
     double *d_r = nullptr, *d_J = nullptr, *d_err = nullptr;
+    char* d_cov = nullptr;                     // ccal_covariance's block (CovLayout), made at the first call
     ccal_allreduce_fn allreduce = nullptr;     // callback form of the step's collective (tests over gloo)
     void* allreduce_user = nullptr;
     void* rccl_comm = nullptr;                 // ncclComm_t: the library issues ncclAllReduce itself (ccal_set_rccl_comm)
@@ -359,6 +360,21 @@ struct PoseScratch {
 struct StatsScratch {
     CallPlan plan; Slice<int64_t> offsets; Slice<double> values; Slice<char> work;
     StatsScratch(size_t n_offsets, int64_t n) { offsets = plan.add<int64_t>(n_offsets); values = plan.add<double, kDoubles>((size_t)n); work = plan.add<char>(kSelWorkBytes); }
+};
+// ccal_problem::d_cov, ccal_covariance's block (ccal_kernels_cov.hip), made at the first call and kept: the per-frame records
+// { V_o (21) | W_o (15 x 6, rows past the camera's columns 0) | sum r^2 }, S^-1 (zero rows and columns at fixed parameters),
+// the per-corner leverages, the two sums (+ 128 partial sums behind them), the slots' 6 x 6 blocks; then the slot -> observation frames table and the slots' verdicts
+constexpr int kCovCamCols = 15;                                  // camera columns of one block at most: 9 intrinsics + 6 extrinsics
+constexpr int kCovRec = 21 + 6 * kCovCamCols + 1;                // doubles per record
+struct CovLayout {
+    CallPlan plan; Slice<double> rec, sinv, lev, sums, pose_cov; Slice<int32_t> slot_off, slot_obs, status;
+    CovLayout(size_t n_corners, size_t n_obs, size_t n_slots, size_t K) {
+        const size_t no = std::max<size_t>(n_obs, 1), ns = std::max<size_t>(n_slots, 1);
+        rec = plan.add<double, kDoubles>(no * kCovRec); sinv = plan.add<double, kDoubles>(std::max<size_t>(K * K, 1));
+        lev = plan.add<double, kDoubles>(std::max<size_t>(n_corners, 1)); sums = plan.add<double, kDoubles>(8 + 128);
+        pose_cov = plan.add<double, kDoubles>(ns * 36);
+        slot_off = plan.add<int32_t>(n_slots + 1); slot_obs = plan.add<int32_t>(no); status = plan.add<int32_t>(ns);
+    }
 };
 // first size of ccal_problem::d_scratch: what ccal_init_poses and validation() of every camera need (gathered values + the selection's work area)
 inline size_t problem_scratch_hint(const ccal_problem* p) {

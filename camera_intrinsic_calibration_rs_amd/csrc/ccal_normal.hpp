@@ -245,6 +245,9 @@ int normal_ws_ensure(ccal_problem* p);          // sizes, column table, camera s
 int normal_ws_ensure_general(ccal_problem* p);  // + the general (multi-camera) loop's buffers
 __attribute__((visibility("hidden"))) int fused_ws_ensure(ccal_problem* p);           // + the single-camera loop's (after normal_ws_ensure)
 int normal_upload_cols(ccal_problem* p);        // bounds / fixed flags -> device
+// ccal_solver.hip: S [K][K], b [K], cost (any may be NULL) of the last ccal_build_normal_dev(p, lambda), in the caller's parameter
+// order; waits for the stream.  CCAL_ERR_NOT_PD when a pose block failed in the elimination (ccal_build_normal, ccal_covariance)
+int normal_readback(ccal_problem* p, double lambda, double* S, double* b, double* cost);
 __attribute__((visibility("hidden"))) void build_cols(const ccal_problem* p, ColInfo* cols);        // [CCAL_KMAX]: the reduced system's columns, bounds and fixed flags in
 __attribute__((visibility("hidden"))) void caller_columns(const ccal_problem* p, int* ext);         // [K]: reduced-system column -> the same parameter's column in the caller's order
 // Session-sized solves (poses up to this many bytes: 2 048 frames) move their parameters without a copy operation: k_unpack1

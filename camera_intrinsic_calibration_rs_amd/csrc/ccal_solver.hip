@@ -679,12 +679,19 @@ int ccal_build_normal(ccal_problem* p, const double* intr, const double* poses, 
                       double lambda, double* S, double* b, double* cost) {
     if (!p || !intr || (!poses && p->n_slots) || (!extr && p->n_cams > 1)) return CCAL_ERR_INVALID_ARG;
     CCAL_API_TRY
-    ccal_ctx* ctx = p->ctx;
     int rc = ccal_upload_params(p, intr, poses, extr);
     if (rc != CCAL_OK) return rc;
     if ((rc = normal_ws_ensure(p)) != CCAL_OK) return rc;
-    NormalWs* w = p->nws;
     if ((rc = ccal_build_normal_dev(p, lambda)) != CCAL_OK) return rc;
+    return normal_readback(p, lambda, S, b, cost);
+    CCAL_API_CATCH(p->ctx)
+}
+
+}  // extern "C"
+// what the last ccal_build_normal_dev(p, lambda) left on the device, in the caller's parameter order (waits for the stream)
+int ccal::normal_readback(ccal_problem* p, double lambda, double* S, double* b, double* cost) {
+    ccal_ctx* ctx = p->ctx;
+    NormalWs* w = p->nws;
     const int K = w->K, K1 = K + 1;
     double failed = 0.0;
     int ec[CCAL_KMAX];
@@ -719,8 +726,8 @@ int ccal_build_normal(ccal_problem* p, const double* intr, const double* poses, 
     }
     if (failed > 0.0) { ctx->err = "a frame's pose block is not positive definite"; return CCAL_ERR_NOT_PD; }
     return CCAL_OK;
-    CCAL_API_CATCH(p->ctx)
 }
+extern "C" {
 
 int ccal_solve(ccal_problem* p, const ccal_solver_opts* o, double* intr_io, double* poses_io, double* extr_io, ccal_report* rep) {
     if (!p || !o || !intr_io || (!poses_io && p->n_slots) || (!extr_io && p->n_cams > 1)) return CCAL_ERR_INVALID_ARG;

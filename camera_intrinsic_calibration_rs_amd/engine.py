@@ -1143,6 +1143,15 @@ def solve_sharded(problems, intr, poses_list, extr=None, opts: _ffi.SolverOpts |
     return intr, poses, extr, rep
 
 
+class Covariance:
+    """What Problem.covariance returns: cov_cam [K, K], cov_poses [n_slots, 6, 6] (NaN blocks for empty slots) or None, leverage
+    [n_corners] or None, slot_status [n_slots] int32 (1: no corner, no pose) and the call's report (_ffi.CovReport)."""
+    __slots__ = ("cov_cam", "cov_poses", "leverage", "slot_status", "report")
+
+    def __init__(self, cov_cam, cov_poses, leverage, slot_status, report):
+        self.cov_cam, self.cov_poses, self.leverage, self.slot_status, self.report = cov_cam, cov_poses, leverage, slot_status, report
+
+
 class Problem:
     """Calib-frame inputs resident in HBM (ccal_problem)."""
 
@@ -1339,6 +1348,34 @@ class Problem:
         self._check(self.lib.ccal_validation(self.handle, cam, _dp(intr), _dp(poses), _dp(extr), C.byref(a), C.byref(m)),
                     "ccal_validation")
         return a.value, m.value
+
+    # -- calibration uncertainty (ccal_covariance, ccal_kernels_cov.hip) -----------------------------------------------------------
+    def covariance(self, intr=None, poses=None, extr=None, poses_cov=True, leverage=True, raise_on_error=True) -> "Covariance":
+        """The covariance of the camera block and of every board pose and the leverage of every corner at a solved point, by the
+        rule stated at ccal_covariance in include/ccal.h.  intr None: the point on the device (upload_params / a device-resident
+        solve); else intr, poses (and extr for a rig) as for eval.  poses_cov / leverage False: that output is not fetched (None
+        in the result).  CCAL_ERR_NOT_PD raises unless raise_on_error is False: the report then names the slot."""
+        if intr is None:
+            if poses is not None or extr is not None:
+                raise ValueError("covariance: poses / extr without intr (intr None means the point on the device)")
+            pi = pp = pe = None
+        else:
+            if poses is None and self.n_slots:
+                raise ValueError("covariance: poses is missing")
+            if extr is None and self.n_cams > 1:
+                raise ValueError("covariance: extr is missing (a rig)")
+            intr, poses, extr = self._params(intr, np.zeros((0, 6)) if poses is None else poses, extr)
+            pi, pp, pe = _dp(intr), _dp(poses), _dp(extr)
+        cov_cam = np.full((self.K, self.K), np.nan)
+        cov_p = np.full((max(self.n_slots, 1), 6, 6), np.nan) if poses_cov else None
+        lev = np.full(max(self.n_corners, 1), np.nan) if leverage else None
+        status = np.full(max(self.n_slots, 1), -2, dtype=np.int32)
+        rep = _ffi.CovReport()
+        rc = self.lib.ccal_covariance(self.handle, pi, pp, pe, _dp(cov_cam), _dp(cov_p), _dp(lev), _ip(status), C.byref(rep))
+        if rc != _ffi.OK and (raise_on_error or rc != _ffi.ERR_NOT_PD):
+            raise CcalError(rc, "ccal_covariance", self.ctx.last_error())
+        return Covariance(cov_cam, None if cov_p is None else cov_p[:self.n_slots], None if lev is None else lev[:self.n_corners],
+                          status[:self.n_slots], rep)
 
     def close(self):
         if getattr(self, "handle", None):

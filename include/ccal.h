@@ -1271,6 +1271,46 @@ int ccal_reprojection_errors(ccal_problem* p, const double* intr, const double* 
 int ccal_validation(ccal_problem* p, int cam, const double* intr, const double* poses, const double* extr,
                     double* avg_99_percent, double* median);
 
+/* ---- calibration uncertainty at a solved point: covariances and leverage ---------------------
+ * How well every parameter and every board pose is determined, and which detections carry the estimate - the first-order
+ * (Gauss-Newton) covariance of the least-squares problem ccal_solve minimises.  The rule:
+ *   The unknowns, in order: x = [camera block (K columns, in the order of ccal_build_normal) | pose of slot 0 (rvec, tvec) |
+ *   pose of slot 1 | ...].  J and r are the loss-corrected Jacobian and residuals of all cameras at the given point - exactly
+ *   what ccal_eval(..., apply_loss = 1, ...) returns - and H = J^T J.
+ *   - Columns of parameters fixed with ccal_fix_param / ccal_disable_distortions are removed before anything is inverted; their
+ *     rows and columns of every output are 0.
+ *   - Bounds are IGNORED: a parameter resting on a bound is treated as free (its variance is that of the unbounded problem).
+ *   - A slot without a single corner has no pose: it is not an unknown.
+ *   With n_free = K_free + 6 n_posed, N the number of corners and dof = 2 N - n_free (dof <= 0: CCAL_ERR_INVALID_ARG):
+ *   cost         = sum r^2 over the loss-corrected residuals (the quantity ccal_report::final_cost holds)
+ *   sigma2       = cost / dof
+ *   cov_cam      [K][K] = sigma2 (H^-1)[camera, camera] = sigma2 S^-1, S the reduced system of mode N at lambda = 0
+ *   cov_poses    [n_slots][6][6] = sigma2 (V_s^-1 + Y_s^T S^-1 Y_s), Y_s = W_s V_s^-1; V_s the slot's 6 x 6 block of H, W_s its
+ *                K x 6 coupling block summed over every camera that saw the slot.  The covariance is in the parameters the solver
+ *                steps in (additive axis-angle and translation).  An empty slot: 36 NaN and slot_status 1 (else 0)
+ *   leverage     [n_corners] = trace(J_k H^-1 J_k^T), J_k the corner's two rows, with (H^-1)[camera, pose s] = -S^-1 Y_s: NOT
+ *                scaled by sigma2, in [0, 2]; the sum over all corners equals n_free (report->leverage_sum: check it)
+ * A Cholesky pivot of any V_s or of S at or below 2^-36 x its own diagonal entry: CCAL_ERR_NOT_PD for the whole call (the rule of
+ * ccal_init_poses); report->bad_slot names the first offending slot, -1 for S.  Nothing is written to the arrays then.
+ * intr == NULL: the point is what ccal_upload_params or a device-resident solve left on the device (poses / extr are ignored);
+ * the results are the same bits as with host pointers to the same values.  cov_poses, leverage, slot_status may be NULL.
+ * Results are bit-identical from run to run (fixed summation orders, no atomics) and do not depend on what ran before.
+ * A sharded problem (communicator, callback or in-process peer set): CCAL_ERR_UNSUPPORTED.  p, cov_cam or report NULL, poses NULL
+ * with slots or extr NULL with several cameras (when intr is given): CCAL_ERR_INVALID_ARG, the argument named in ccal_last_error. */
+typedef struct {
+    int32_t status;                /* ccal_status of the call */
+    int32_t bad_slot;              /* CCAL_ERR_NOT_PD: the first slot whose V_s failed, -1: S; else -1 */
+    int64_t dof;                   /* 2 N - n_free */
+    int32_t n_free;                /* K_free + 6 n_posed */
+    int32_t n_posed;               /* slots with at least one corner */
+    double cost, sigma2, leverage_sum;
+    int32_t reserved_[4];          /* 0 */
+} ccal_cov_report;
+int ccal_covariance(ccal_problem* p, const double* intr, const double* poses, const double* extr,   /* intr == NULL: the point on the device */
+                    double* cov_cam /* [K][K] */, double* cov_poses /* [n_slots][36] or NULL */,
+                    double* leverage /* [n_corners], the description's corner order, or NULL */,
+                    int32_t* slot_status /* [n_slots] or NULL */, ccal_cov_report* report);
+
 #ifdef __cplusplus
 }
 #endif
