@@ -3,6 +3,7 @@
 // library does not contain this translation unit.
 #include "ccal_call.hpp"
 #include "ccal_device.hpp"
+#include "ccal_pose_init.hpp"
 
 // The radix select of validation() on raw values (tests/test_gpu_order_stats.py): vals[n] (host) -> the two statistics, through
 // order_stats_block - the multi-GPU path's call, the product's kernels (build/ccal_kernels_stats.o is in both libraries).
@@ -75,6 +76,64 @@ extern "C" int ccal_test_device_math(ccal_ctx* ctx, int op, int64_t n, const dou
     ccal::ctx_release(ctx, block, false);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return ccal::hip_fail(ctx, "ccal_test_device_math", e);
+    return CCAL_OK;
+    CCAL_API_CATCH(ctx)
+}
+
+// The pose initialisation's model inverse on pixels of the tests' choice (tests/test_gpu_model_inverse.py): unproject_normalized of
+// ccal_pose_init.hpp as it is, one row per lane, grid-stride, with the context's ModelRt.  model: a camera model of include/ccal.h
+// with its params() vector, or 100 (kUnprojDivision) with th = [half, half, w/2, h/2, lambda].  uv [n][2] -> xn_yn_out [n][2]
+// (NaN where there is no ray), valid_out [n].
+namespace {
+struct UnprojNormArgs { double th[CCAL_PMAX]; double small_radius; int64_t n; const double* uv; double* out; uint8_t* valid; };
+
+template <int MODEL>
+__global__ void __launch_bounds__(256) k_test_unproject_normalized(const UnprojNormArgs a) {
+    const double nan = __builtin_nan("");
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+        double xn = nan, yn = nan;
+        const bool ok = ccal::unproject_normalized<MODEL>(a.th, a.small_radius, a.uv[2 * i], a.uv[2 * i + 1], xn, yn);
+        a.out[2 * i] = ok ? xn : nan; a.out[2 * i + 1] = ok ? yn : nan;
+        a.valid[i] = ok ? 1 : 0;
+    }
+}
+template <int M> struct LaunchUnprojNorm {
+    static void go(int g, hipStream_t st, const UnprojNormArgs& a) { k_test_unproject_normalized<M><<<dim3(g), dim3(256), 0, st>>>(a); }
+};
+}  // namespace
+
+extern "C" int ccal_test_unproject_normalized(ccal_ctx* ctx, int model, const double* params, int64_t n, const double* uv,
+                                              double* xn_yn_out, uint8_t* valid_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    const char* where = "ccal_test_unproject_normalized";
+    if (!params || n <= 0 || !uv || !xn_yn_out || !valid_out)
+        return ccal::fail(ctx, CCAL_ERR_INVALID_ARG, "ccal_test_unproject_normalized: params, n > 0 pixels and both outputs");
+    const bool division = model == ccal::kUnprojDivision;
+    if (!division) { if (const int rc = ccal::check_model(ctx, model, where)) return rc; }
+    CCAL_API_TRY
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    UnprojNormArgs a = {};
+    if (division) { for (int i = 0; i < 5; ++i) a.th[i] = params[i]; a.small_radius = ccal::model_rt(ctx).unproject_eps; }
+    else { ccal::ModelRt rt; ccal::canonical_theta(ctx, model, params, a.th, &rt); a.small_radius = rt.unproject_eps; }
+    const size_t xy_bytes = (size_t)n * 2 * sizeof(double);
+    char* block = nullptr;
+    hipError_t e = ccal::ctx_dev_alloc(ctx, (void**)&block, 2 * xy_bytes + (size_t)n);
+    if (e != hipSuccess) return ccal::hip_fail(ctx, "ccal_test_unproject_normalized: allocation", e);
+    a.n = n; a.uv = (const double*)block; a.out = (double*)(block + xy_bytes); a.valid = (uint8_t*)(block + 2 * xy_bytes);
+    e = hipMemcpyAsync(block, uv, xy_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        const int64_t blocks = (n + 255) / 256;
+        const int g = (int)(blocks < 1024 ? blocks : 1024);
+        if (division) LaunchUnprojNorm<ccal::kUnprojDivision>::go(g, ctx->stream, a);
+        else ccal::launch_model<LaunchUnprojNorm>(model, g, ctx->stream, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(xn_yn_out, a.out, xy_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(valid_out, a.valid, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);        // nothing in flight uses the block when it goes back to the context
+    ccal::ctx_release(ctx, block, false);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return ccal::hip_fail(ctx, where, e);
     return CCAL_OK;
     CCAL_API_CATCH(ctx)
 }

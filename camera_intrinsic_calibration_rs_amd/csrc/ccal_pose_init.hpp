@@ -28,8 +28,9 @@ __device__ __forceinline__ bool unproject_normalized(const double* th, double sm
         if (alpha > 0.5 && r2 > 1.0 / (beta * (2.0 * alpha - 1.0))) return false;
         const double t1 = 1.0 - (2.0 * alpha - 1.0) * beta * r2;
         if (t1 < 0.0) return false;
-        const double k = (1.0 - alpha * alpha * beta * r2) / (alpha * sqrt(t1) + (1.0 - alpha));
-        if (!(k > 1e-3)) return false;
+        const double den = alpha * sqrt(t1) + (1.0 - alpha);
+        const double k = (1.0 - alpha * alpha * beta * r2) / den;
+        if (!(den > 0.0) || !(k > 1e-3) || !(k < __builtin_inf())) return false;      // alpha = 1 on the domain's edge: 0 / 0
         xn = mx / k; yn = my / k;
         return true;
     } else if constexpr (MODEL == kKB4) {
@@ -43,6 +44,8 @@ __device__ __forceinline__ bool unproject_normalized(const double* th, double sm
             t -= f / fp;
         }
         if (!(t > 0.0) || !(t < 1.5)) return false;             // theta < ~86 deg: in front of the camera
+        const double tt = t * t;                                // accept only if re-projection reproduces the input (as OPENCV5 below)
+        if (!(fabs(t * (1.0 + tt * (th[4] + tt * (th[5] + tt * (th[6] + tt * th[7])))) - r) < 1e-9)) return false;
         const double s = tan(t) / r;
         xn = mx * s; yn = my * s;
         return true;

@@ -587,6 +587,13 @@ int ccal_convert_model(ccal_ctx* ctx, int src_model, const double* src_params, i
  *                        of the UCM / EUCM cone, a non-zero KB4 point, z > 1e-9 for OPENCV5); invalid rows are NaN, NaN.
  * ccal_unproject_points  GenericModel::unproject: uv [n][2] -> rays_out [n][3] (a unit ray; (mx, my, 1) below KB4's small
  *                        radius), valid_out [n]; invalid rows are NaN.  n == 0 is allowed in both.
+ *                        THE CONTRACT of every unprojection of this library (this call, the new camera matrix, the renderer,
+ *                        ccal_convert_model's rays, pose initialisation): valid means the ray re-projects onto the pixel under
+ *                        the acceptance rule, None otherwise.  The rule: the iterative inverses (KB4's Newton, OPENCV5's fixed
+ *                        point) accept their last iterate only if its residual is below 1e-9 in normalised image units; the
+ *                        closed form (UCM, EUCM) only inside its domain and where its denominator and the ray's norm are
+ *                        positive finite numbers (alpha = 1 on the domain's edge is None).  A pixel that has a ray which the
+ *                        published iteration does not find from its start is None as well.
  * ccal_estimate_new_camera_matrix
  *                        the pinhole K_out [9] (row-major [[f,0,cx],[0,f,cy],[0,0,1]]) whose new_w x new_h image (0, 0: width x
  *                        height) holds the rays of the four edge midpoints (cx,0), (W-1,cy), (cx,H-1), (0,cy) of the model:

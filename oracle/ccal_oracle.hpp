@@ -279,6 +279,9 @@ template <class T> inline void project_one(int model, const T* p, const V3<T>& p
 // KB4: Kannala-Brandt 2006 with Newton on theta; OPENCV5: fixed-point undistortion).  Used only by the
 // ModelConvertFactor restatement (src/optimization/factors.rs:23-54).  Parity unpinned for the crate's
 // exact validity thresholds and iteration counts.
+// Convention (the contract of ccal_unproject_points, include/ccal.h): `true` means the ray re-projects onto the pixel.  The
+// iterative inverses (KB4, OPENCV5) accept their last iterate only if its residual in normalised units is below 1e-9; the
+// closed form (UCM, EUCM) only if its denominator and norm are positive finite numbers.  Everything else is None.
 // ---------------------------------------------------------------------------
 inline bool unproject_one(int model, const double* p, double u, double v, double ray[3]) {
     const double mx = (u - p[2]) / p[0], my = (v - p[3]) / p[1];
@@ -288,8 +291,10 @@ inline bool unproject_one(int model, const double* p, double u, double v, double
         if (alpha > 0.5 && r2 > 1.0 / (beta * (2.0 * alpha - 1.0))) return false;
         const double t1 = 1.0 - (2.0 * alpha - 1.0) * beta * r2;
         if (t1 < 0.0) return false;
-        const double mz = (1.0 - beta * alpha * alpha * r2) / (alpha * std::sqrt(t1) + (1.0 - alpha));
+        const double den = alpha * std::sqrt(t1) + (1.0 - alpha);
+        const double mz = (1.0 - beta * alpha * alpha * r2) / den;
         const double n = std::sqrt(r2 + mz * mz);
+        if (!(den > 0.0) || !(n > 0.0) || !std::isfinite(n)) return false;
         ray[0] = mx / n; ray[1] = my / n; ray[2] = mz / n;
         return true;
     }
@@ -306,6 +311,8 @@ inline bool unproject_one(int model, const double* p, double u, double v, double
             if (std::fabs(dt) < 1e-14) break;
         }
         if (!(t > 0.0) || !(t < 3.141592653589793)) return false;
+        const double tt = t * t;
+        if (!(std::fabs(t * (1.0 + tt * (p[4] + tt * (p[5] + tt * (p[6] + tt * p[7])))) - r) < 1e-9)) return false;
         const double s = std::sin(t) / r;
         ray[0] = mx * s; ray[1] = my * s; ray[2] = std::cos(t);
         return true;

@@ -87,6 +87,9 @@ def unproject(model, params, uv, unproject_eps=1e-8):
                     break
             if not (t > 0) or not (t < 1.5):
                 continue
+            tt = t * t
+            if not abs(t * (one + tt * (th[4] + tt * (th[5] + tt * (th[6] + tt * th[7])))) - r[i]) < 1e-9:   # the kernel's acceptance rule
+                continue
             s = np.tan(t) / r[i]
             xn[i], yn[i], valid[i] = mx[i] * s, my[i] * s, True
     elif model == OPENCV5:
@@ -142,8 +145,9 @@ def unproject_kernel_f64(model, params, uv, unproject_eps=1e-8):
                 valid &= ~(r2 > 1.0 / (beta * (2.0 * alpha - 1.0)))
             t1 = 1.0 - (2.0 * alpha - 1.0) * beta * r2
             valid &= ~(t1 < 0.0)
-            k = (1.0 - alpha * alpha * beta * r2) / (alpha * np.sqrt(t1) + (1.0 - alpha))
-            valid &= k > 1e-3
+            den = alpha * np.sqrt(t1) + (1.0 - alpha)
+            k = (1.0 - alpha * alpha * beta * r2) / den
+            valid &= (den > 0.0) & (k > 1e-3) & (k < np.inf)
             x, y = mx / k, my / k
         elif model == KB4:
             r = np.sqrt(r2)
@@ -154,7 +158,9 @@ def unproject_kernel_f64(model, params, uv, unproject_eps=1e-8):
                 fp = 1.0 + t2 * (3.0 * th[4] + t2 * (5.0 * th[5] + t2 * (7.0 * th[6] + t2 * 9.0 * th[7])))
                 t = t - f / fp
             small = r < unproject_eps
-            valid = small | ((t > 0.0) & (t < 1.5))
+            tt = t * t
+            res = t * (1.0 + tt * (th[4] + tt * (th[5] + tt * (th[6] + tt * th[7])))) - r
+            valid = small | ((t > 0.0) & (t < 1.5) & (np.abs(res) < 1e-9))          # the kernel's acceptance rule
             s = np.tan(t) / r
             x, y = np.where(small, mx, mx * s), np.where(small, my, my * s)
         elif model == OPENCV5:
