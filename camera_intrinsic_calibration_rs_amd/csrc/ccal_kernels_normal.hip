@@ -831,4 +831,44 @@ hipError_t launch_backsub(const ccal_problem* p, double lambda, double min_diag,
     return hipGetLastError();
 }
 
+#ifdef CCAL_TEST_HOOKS
+// The two kernels above on buffers of the tests' choice (ccal_normal.hpp: TestSolveIO, TestBacksubIO): launch_solve's and
+// launch_backsub's geometry, the caller has checked the sizes.  The dynamic-LDS limit is set to the largest size the kernel claims
+// (K = CCAL_KMAX - 1) on every call and without a guard of its own: the launchers' guards above then never claim more than is enabled.
+hipError_t test_launch_solve(const TestSolveIO& t, hipStream_t s) {
+    SolveArgs a = {};
+    a.st = t.st; a.hs = t.hs; a.seq = 1; a.publish_all = 0;
+    a.red = t.red; a.cols = t.cols; a.K = t.K; a.RB = red_size(t.K); a.lambda = 0.0; a.min_diag = t.min_diag; a.max_diag = t.max_diag;
+    a.intr = t.intr[0]; a.extr = t.extr[0]; a.intr_c = t.intr[1]; a.extr_c = t.extr[1];
+    a.n_intr = t.n_intr; a.n_extr = t.n_extr;
+    a.dc = t.dc; a.scal = t.scal; a.flags = t.flags;
+    if (t.K >= 64) {
+        const int K1 = t.K + 1;
+        const size_t lds = sizeof(double) * (size_t)(K1 | 1) * K1, most = sizeof(double) * (size_t)(CCAL_KMAX | 1) * CCAL_KMAX;
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most); e != hipSuccess) {
+            (void)hipGetLastError();
+            return e;
+        }
+        hipLaunchKernelGGL(k_solve<true>, dim3(1), dim3(128), lds, s, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_solve<false>, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t test_launch_backsub(const TestBacksubIO& t, hipStream_t s) {
+    BacksubArgs a = {};
+    a.st = t.st;
+    a.pf = t.pf; a.dc = t.dc; a.poses_s[0] = t.poses[0]; a.poses_s[1] = t.poses[1]; a.mc_slot = t.mc_slot;
+    a.n_slots = t.n_slots; a.K = t.K; a.PF = pf_size(t.K); a.lambda = 0.0;
+    a.min_diag = t.min_diag; a.max_diag = t.max_diag;
+    const size_t lds = sizeof(double) * 16 * (size_t)(a.PF + 6), most = sizeof(double) * 16 * (size_t)(pf_size(CCAL_KMAX - 1) + 6);
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_backsub), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most); e != hipSuccess) {
+        (void)hipGetLastError();
+        return e;
+    }
+    hipLaunchKernelGGL(k_backsub, dim3((t.n_slots + 15) / 16), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+#endif
+
 }  // namespace ccal

@@ -3,6 +3,8 @@
 // library does not contain this translation unit.
 #include "ccal_call.hpp"
 #include "ccal_device.hpp"
+#include "ccal_fused.hpp"
+#include "ccal_normal.hpp"
 #include "ccal_pose_init.hpp"
 
 // The radix select of validation() on raw values (tests/test_gpu_order_stats.py): vals[n] (host) -> the two statistics, through
@@ -255,6 +257,150 @@ extern "C" int ccal_test_guard_damage(ccal_ctx* ctx, int slice, int from_end, in
     const int64_t pos = (int64_t)(slice == 0 ? s_a.off : s_c.off) + (from_end ? (slice == 0 ? 5 * (int64_t)sizeof(double) : 65 * (int64_t)sizeof(int32_t)) : 0) + delta;
     if (pos >= 0 && pos < (int64_t)blk.total && blk.ok())
         blk.note(hipMemsetAsync(reinterpret_cast<char*>(blk.at(s_a)) - s_a.off + pos, 0x3C, 1, ctx->stream));
+    return blk.finish(where);
+    CCAL_API_CATCH(ctx)
+}
+
+// The two small dense solves at the end of every step, on systems of the tests' choice (tests/test_gpu_camera_solve.py): k_solve
+// (launch_solve's geometry: test_launch_solve, ccal_kernels_normal.hip) or k_head (launch_head), and k_backsub (test_launch_backsub) -
+// the kernels as they are, device-resident form, on a state as launch_state_eval leaves it (first evaluation, method from lambda) with
+// set `cur` as the current one.  Every in / out array is [guard | payload | guard] doubles, goes to the device as the caller filled
+// it and comes back whole: what a kernel does not write keeps the caller's value, the kernels get the payload's address.
+//   form 0 k_solve: red [red_size(K)], 1 <= K < CCAL_KMAX;  form 1 k_head: red [fused_red_size(K)], 4 <= K <= 9, n_intr = CCAL_PMAX, n_extr = 0
+//   cols [K] of col_bytes = sizeof(ColInfo) each;  intr0/1 [n_intr + tail], extr0/1 [n_extr + tail], dc [CCAL_KMAX]: payloads
+//   state_out [8]: mc_cam, lambda_solve, done, cam_failed, cur, first, flags[1], scal[2] (k_head: the last two stay as they came)
+namespace {
+struct HookBlock {          // one block of the context's allocator cut into 256-byte aligned pieces; a sticky status like CallBlock's
+    ccal_ctx* ctx; char* base = nullptr; size_t total = 0; hipError_t e = hipSuccess;
+    explicit HookBlock(ccal_ctx* c) : ctx(c) {}
+    ~HookBlock() { if (base) { (void)hipStreamSynchronize(ctx->stream); ccal::ctx_release(ctx, base, false); } }
+    size_t add(size_t bytes) { const size_t off = total; total += (bytes + 255) & ~(size_t)255; return off; }
+    bool alloc() { e = hipSetDevice(ctx->device); if (e == hipSuccess) e = ccal::ctx_dev_alloc(ctx, (void**)&base, total); return e == hipSuccess; }
+    template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+    void note(hipError_t r) { if (e == hipSuccess) e = r; }
+    void up(size_t off, const void* host, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpyAsync(base + off, host, bytes, hipMemcpyHostToDevice, ctx->stream); }
+    void down(void* host, size_t off, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpyAsync(host, base + off, bytes, hipMemcpyDeviceToHost, ctx->stream); }
+    void zero(size_t off, size_t bytes) { if (e == hipSuccess) e = hipMemsetAsync(base + off, 0, bytes, ctx->stream); }
+    int finish(const char* where) {
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        return e == hipSuccess ? CCAL_OK : ccal::hip_fail(ctx, where, e);
+    }
+};
+ccal::DevState hook_state(double lambda, int cur) {
+    ccal::DevState st = {};
+    st.lambda = lambda; st.lambda_spec = lambda; st.lambda_solve = -1.0;        // (k_state_eval: 0; -1 shows the kernel's store in Gauss-Newton too)
+    st.radius = lambda > 0.0 ? 1.0 / lambda : 1e4; st.dec = 2.0;
+    st.mc_cam = __builtin_nan("");
+    st.min_error = 1e-10; st.min_abs = 1e-5; st.min_rel = 1e-5;
+    st.cur = cur; st.first = 1; st.max_iter = 100;
+    st.method = lambda > 0.0 ? CCAL_METHOD_LM : CCAL_METHOD_GN;
+    return st;
+}
+constexpr int kHookMaxGuard = 4096, kHookMaxParams = 1024, kHookMaxSlots = 4096;
+}  // namespace
+
+extern "C" int ccal_test_camera_solve(ccal_ctx* ctx, int form, int K, const double* red, const void* cols, int col_bytes, int n_intr, int n_extr,
+                                      int guard, int tail, double* intr0, double* intr1, double* extr0, double* extr1,
+                                      double lambda, double min_diag, double max_diag, int cur, double* dc, double* state_out) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    const char* where = "ccal_test_camera_solve";
+    const ccal::BadArg bad{ ctx, where };
+    if (form != 0 && form != 1) return bad("form 0 (k_solve) or 1 (k_head)");
+    if (form == 0 ? (K < 1 || K >= CCAL_KMAX) : (K < 4 || K > ccal::kFusedMaxK)) return bad("K outside the form's sizes");
+    if (col_bytes != (int)sizeof(ccal::ColInfo)) return bad("col_bytes is not the size of a column record");
+    if (guard < 0 || guard > kHookMaxGuard || tail < 0 || tail > kHookMaxGuard) return bad("guard and tail: 0 .. 4096 doubles");
+    if (form == 0 ? (n_intr < 1 || n_intr > kHookMaxParams) : n_intr != CCAL_PMAX) return bad("n_intr outside the form's sizes");
+    if (form == 0 ? (n_extr < 0 || n_extr > kHookMaxParams) : n_extr != 0) return bad("n_extr outside the form's sizes");
+    if (cur != 0 && cur != 1) return bad("cur 0 or 1");
+    if (!(lambda >= 0.0) || !(lambda < 1.7e308)) return bad("lambda: finite, >= 0");
+    if (!(min_diag <= max_diag)) return bad("min_diag <= max_diag");
+    if (!red || !cols || !intr0 || !intr1 || !extr0 || !extr1 || !dc || !state_out) return bad("every array");
+    const ccal::ColInfo* ci = static_cast<const ccal::ColInfo*>(cols);
+    for (int i = 0; i < K; ++i) {
+        const int n = ci[i].is_extr ? n_extr : n_intr;
+        if (ci[i].is_extr != 0 && ci[i].is_extr != 1) return bad("a column's is_extr is 0 or 1");
+        if (ci[i].dst < 0 || ci[i].dst >= n) return bad("a column's dst outside its parameter array");
+        if (ci[i].dst2 < -1 || ci[i].dst2 >= n) return bad("a column's dst2 outside its parameter array");
+    }
+    const size_t g = (size_t)guard, D = sizeof(double);
+    const size_t n_red = (size_t)(form == 0 ? ccal::red_size(K) : ccal::fused_red_size(K));
+    const size_t len_i = 2 * g + (size_t)n_intr + (size_t)tail, len_e = 2 * g + (size_t)n_extr + (size_t)tail, len_dc = 2 * g + CCAL_KMAX;
+    HookBlock blk(ctx);
+    const size_t o_red = blk.add(n_red * D), o_cols = blk.add((size_t)K * sizeof(ccal::ColInfo));
+    const size_t o_i0 = blk.add(len_i * D), o_i1 = blk.add(len_i * D), o_e0 = blk.add(len_e * D), o_e1 = blk.add(len_e * D);
+    const size_t o_dc = blk.add(len_dc * D), o_scal = blk.add(8 * D), o_flags = blk.add(4 * sizeof(int32_t));
+    const size_t o_st = blk.add(sizeof(ccal::DevState)), o_hs = blk.add(sizeof(ccal::HostStatus));
+    if (!blk.alloc()) return blk.finish(where);
+    const ccal::DevState st0 = hook_state(lambda, cur);
+    blk.up(o_red, red, n_red * D); blk.up(o_cols, cols, (size_t)K * sizeof(ccal::ColInfo));
+    blk.up(o_i0, intr0, len_i * D); blk.up(o_i1, intr1, len_i * D); blk.up(o_e0, extr0, len_e * D); blk.up(o_e1, extr1, len_e * D);
+    blk.up(o_dc, dc, len_dc * D); blk.up(o_st, &st0, sizeof st0);
+    blk.zero(o_scal, 8 * D); blk.zero(o_flags, 4 * sizeof(int32_t)); blk.zero(o_hs, sizeof(ccal::HostStatus));
+    if (blk.e == hipSuccess) {
+        if (form == 0) {
+            ccal::TestSolveIO t = {};
+            t.red = blk.at<double>(o_red); t.cols = blk.at<ccal::ColInfo>(o_cols); t.K = K; t.min_diag = min_diag; t.max_diag = max_diag;
+            t.intr[0] = blk.at<double>(o_i0) + g; t.intr[1] = blk.at<double>(o_i1) + g;
+            t.extr[0] = blk.at<double>(o_e0) + g; t.extr[1] = blk.at<double>(o_e1) + g;
+            t.n_intr = n_intr; t.n_extr = n_extr;
+            t.dc = blk.at<double>(o_dc) + g; t.scal = blk.at<double>(o_scal); t.flags = blk.at<int32_t>(o_flags);
+            t.st = blk.at<ccal::DevState>(o_st); t.hs = blk.at<ccal::HostStatus>(o_hs);
+            blk.note(ccal::test_launch_solve(t, ctx->stream));
+        } else {
+            ccal::HeadArgs a = {};
+            a.st = blk.at<ccal::DevState>(o_st); a.hs = blk.at<ccal::HostStatus>(o_hs); a.red = blk.at<double>(o_red);
+            a.cols = blk.at<ccal::ColInfo>(o_cols);
+            a.intr[0] = blk.at<double>(o_i0) + g; a.intr[1] = blk.at<double>(o_i1) + g; a.dc = blk.at<double>(o_dc) + g;
+            a.K = K; a.seq = 1; a.min_diag = min_diag; a.max_diag = max_diag;
+            blk.note(ccal::launch_head(a, ctx->stream));
+        }
+    }
+    ccal::DevState st1 = {};
+    double scal[8] = {}; int32_t flags[4] = {};
+    blk.down(intr0, o_i0, len_i * D); blk.down(intr1, o_i1, len_i * D); blk.down(extr0, o_e0, len_e * D); blk.down(extr1, o_e1, len_e * D);
+    blk.down(dc, o_dc, len_dc * D); blk.down(&st1, o_st, sizeof st1); blk.down(scal, o_scal, sizeof scal); blk.down(flags, o_flags, sizeof flags);
+    if (const int rc = blk.finish(where)) return rc;
+    state_out[0] = st1.mc_cam; state_out[1] = st1.lambda_solve; state_out[2] = st1.done; state_out[3] = st1.cam_failed;
+    state_out[4] = st1.cur; state_out[5] = st1.first;
+    if (form == 0) { state_out[6] = flags[1]; state_out[7] = scal[2]; }
+    return CCAL_OK;
+    CCAL_API_CATCH(ctx)
+}
+
+// k_backsub on records of the tests' choice: pf [n_slots][pf_size(K)], dc_in [K]; poses0 / poses1 [guard | n_slots * 6 | guard] (set
+// `cur` is read, the other one written), mc_slot [guard | n_slots | guard]: in / out, whole, as above.
+extern "C" int ccal_test_backsub(ccal_ctx* ctx, int n_slots, int K, const double* pf, const double* dc_in, int guard,
+                                 double* poses0, double* poses1, double lambda, double min_diag, double max_diag, int cur, double* mc_slot) {
+    if (!ctx) return CCAL_ERR_INVALID_ARG;
+    CCAL_API_TRY
+    const char* where = "ccal_test_backsub";
+    const ccal::BadArg bad{ ctx, where };
+    if (n_slots < 1 || n_slots > kHookMaxSlots) return bad("n_slots: 1 .. 4096");
+    if (K < 1 || K >= CCAL_KMAX) return bad("K: 1 .. CCAL_KMAX - 1");
+    if (guard < 0 || guard > kHookMaxGuard) return bad("guard: 0 .. 4096 doubles");
+    if (cur != 0 && cur != 1) return bad("cur 0 or 1");
+    if (!(lambda >= 0.0) || !(lambda < 1.7e308)) return bad("lambda: finite, >= 0");
+    if (!(min_diag <= max_diag)) return bad("min_diag <= max_diag");
+    if (!pf || !dc_in || !poses0 || !poses1 || !mc_slot) return bad("every array");
+    const size_t g = (size_t)guard, D = sizeof(double), ns = (size_t)n_slots, PF = (size_t)ccal::pf_size(K);
+    const size_t len_p = 2 * g + 6 * ns, len_m = 2 * g + ns;
+    HookBlock blk(ctx);
+    const size_t o_pf = blk.add(ns * PF * D), o_dc = blk.add((size_t)K * D), o_p0 = blk.add(len_p * D), o_p1 = blk.add(len_p * D);
+    const size_t o_mc = blk.add(len_m * D), o_st = blk.add(sizeof(ccal::DevState));
+    if (!blk.alloc()) return blk.finish(where);
+    ccal::DevState st0 = hook_state(lambda, cur);
+    st0.first = 0;                                    // behind a k_solve that has decided and solved
+    blk.up(o_pf, pf, ns * PF * D); blk.up(o_dc, dc_in, (size_t)K * D); blk.up(o_p0, poses0, len_p * D); blk.up(o_p1, poses1, len_p * D);
+    blk.up(o_mc, mc_slot, len_m * D); blk.up(o_st, &st0, sizeof st0);
+    if (blk.e == hipSuccess) {
+        ccal::TestBacksubIO t = {};
+        t.pf = blk.at<double>(o_pf); t.dc = blk.at<double>(o_dc); t.mc_slot = blk.at<double>(o_mc) + g;
+        t.poses[0] = blk.at<double>(o_p0) + g; t.poses[1] = blk.at<double>(o_p1) + g;
+        t.n_slots = n_slots; t.K = K; t.min_diag = min_diag; t.max_diag = max_diag; t.st = blk.at<ccal::DevState>(o_st);
+        blk.note(ccal::test_launch_backsub(t, ctx->stream));
+    }
+    blk.down(poses0, o_p0, len_p * D); blk.down(poses1, o_p1, len_p * D); blk.down(mc_slot, o_mc, len_m * D);
     return blk.finish(where);
     CCAL_API_CATCH(ctx)
 }

@@ -275,5 +275,19 @@ hipError_t launch_reduce(const ccal_problem* p, hipStream_t s, const DevState* s
 hipError_t launch_solve(const ccal_problem* p, double lambda, double min_diag, double max_diag, hipStream_t s, DevState* st = nullptr,
                         HostStatus* hs = nullptr, int seq = 0, bool publish_all = false);
 hipError_t launch_backsub(const ccal_problem* p, double lambda, double min_diag, double max_diag, hipStream_t s, const DevState* st = nullptr);
+#ifdef CCAL_TEST_HOOKS          // second library only: k_solve / k_backsub as they are, device-resident form, on buffers of the tests' choice
+// (ccal_test_camera_solve / ccal_test_backsub, ccal_legacy_test_hooks.hip).  Set 0 / 1 = intr[0], extr[0] / intr[1], extr[1]; damping and set from *st
+struct TestSolveIO {
+    const double* red; const ColInfo* cols; int32_t K; double min_diag, max_diag;
+    double* intr[2]; double* extr[2]; int32_t n_intr, n_extr;
+    double* dc; double* scal; int32_t* flags; DevState* st; HostStatus* hs;
+};
+struct TestBacksubIO {
+    const double* pf; const double* dc; double* mc_slot; double* poses[2]; int32_t n_slots, K;
+    double min_diag, max_diag; const DevState* st;
+};
+hipError_t test_launch_solve(const TestSolveIO& t, hipStream_t s);
+hipError_t test_launch_backsub(const TestBacksubIO& t, hipStream_t s);
+#endif
 
 }  // namespace ccal

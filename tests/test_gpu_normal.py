@@ -332,6 +332,84 @@ def test_eight_cameras_matches_oracle(gpu_ctx, oracle, model, one_focal, K):
         np.testing.assert_allclose(extr, extr_o, rtol=0, atol=1e-7)
 
 
+def _solve_pair_with_fixed_columns(gp, op, sp, i0, method):
+    """test_solve_matches_oracle's comparison on a rig whose reduced system has fixed columns: the same iteration count, its
+    tolerances - 1e-6 relative on the intrinsics, 1e-7 on poses and extrinsics"""
+    intr, poses, extr, rep = gp.solve(i0, sp.poses0, sp.extr0, opts=default_opts(method))
+    intr_o, poses_o, extr_o, rep_o = op.solve(i0, sp.poses0, sp.extr0, opts=default_opts(method))
+    assert rep.status == rep_o.status == 0
+    assert rep.iterations == rep_o.iterations
+    assert abs(rep.initial_cost - rep_o.initial_cost) <= 1e-12 * rep_o.initial_cost
+    assert abs(rep.final_cost - rep_o.final_cost) <= 1e-9 * rep_o.final_cost
+    assert (np.abs(intr - intr_o) / np.maximum(np.abs(intr_o), 1e-3)).max() <= 1e-6
+    np.testing.assert_allclose(poses, poses_o, rtol=0, atol=1e-7)
+    np.testing.assert_allclose(extr, extr_o, rtol=0, atol=1e-7)
+    return intr, intr_o
+
+
+@pytest.mark.parametrize("method", [_ffi.METHOD_GN, _ffi.METHOD_LM])
+def test_rig_with_fixed_focal_disabled_distortion_and_an_active_bound(gpu_ctx, oracle, method):
+    """calib_all_camera_with_extrinsics(..., disabled_distortions, fixed_focal) (src/util.rs:567-651) is a RIG: its fixed columns, their
+    zeroed right-hand side and undamped diagonal, the clamp and the fy mirror run in k_solve, not in the single-camera head.  Two EUCM
+    cameras: camera 1's focal length fixed, the last distortion of both disabled (beta = 0: alpha then has no effect on the projection,
+    its column is null - the reference's binary would stop NOT_PD - so alpha is fixed as well: three more fixed columns), and a lower
+    bound on camera 1's cx that is active at the optimum (the free optimum is ~241)."""
+    sp = synth.make_problem(30, "eucm", n_cams=2, outlier_frac=0.01)
+    gp, op = _pair(gpu_ctx, oracle, sp)
+    assert gp.K == 2 * 6 + 6
+    i0, i0o = sp.intr0.copy(), sp.intr0.copy()
+    gp.disable_distortions(1, i0); op.disable_distortions(1, i0o)
+    np.testing.assert_array_equal(i0, i0o)
+    for q in (gp, op):
+        q.apply_reference_bounds()
+        q.fix_param(1, 0); q.fix_param(0, 4); q.fix_param(1, 4)
+        q.set_bounds(1, 2, 245.0, 512.0)
+    assert i0[1, 2] > 245.0
+    intr, intr_o = _solve_pair_with_fixed_columns(gp, op, sp, i0, method)
+    for got in (intr, intr_o):
+        assert got[1, 0] == i0[1, 0] and (got[:, 4] == i0[:, 4]).all() and (got[:, 5] == 0.0).all()      # the fixed values, bit for bit
+        assert got[1, 2] == 245.0                                                                          # the clamped one on its bound
+    assert intr[0, 0] != i0[0, 0] and intr[1, 1] != i0[1, 1]
+
+
+@pytest.mark.parametrize("method", [_ffi.METHOD_GN, _ffi.METHOD_LM])
+def test_mixed_rig_with_one_fixed_column_per_camera(gpu_ctx, oracle, method):
+    """test_rig_of_different_cameras' three cameras (K = 31: rows in registers, one below the LDS loop) with cx of the EUCM camera, k2
+    of the KB4 camera and alpha of the UCM camera fixed"""
+    sp = synth.make_rig(48, ("eucm", "kb4", "ucm"), RIG_EXTR[3], xy_same_focal=False, seed=0xBEEF + 3)
+    gp, op = _pair(gpu_ctx, oracle, sp)
+    assert gp.K == 31
+    fixed = ((0, 2), (1, 5), (2, 4))
+    for q in (gp, op):
+        q.apply_reference_bounds()
+        for cam, idx in fixed:
+            q.fix_param(cam, idx)
+    intr, intr_o = _solve_pair_with_fixed_columns(gp, op, sp, sp.intr0, method)
+    for cam, idx in fixed:
+        assert intr[cam, idx] == sp.intr0[cam, idx] == intr_o[cam, idx]
+    assert intr[0, 3] != sp.intr0[0, 3]
+
+
+@pytest.mark.parametrize("method", [_ffi.METHOD_GN, _ffi.METHOD_LM])
+def test_eight_cameras_with_the_last_columns_of_the_last_camera_fixed(gpu_ctx, oracle, method):
+    """test_eight_cameras_matches_oracle's OPENCV5 rig (K = 114, k_solve<true>) with camera 7's last two distortions disabled: fixed
+    columns 106 and 107, rows of the second wavefront of the camera solve"""
+    rng = np.random.default_rng(8)
+    extr = [[0.0] * 6] + [list(np.concatenate([rng.uniform(-0.04, 0.04, 3), rng.uniform(-0.03, 0.03, 3)])) for _ in range(7)]
+    sp = synth.make_rig(16, ("opencv5",) * 8, extr, xy_same_focal=False, seed=0xE16)
+    gp, op = _pair(gpu_ctx, oracle, sp)
+    assert gp.K == 114
+    i0 = sp.intr0.copy()
+    i0[7, 7:9] = 0.0
+    for q in (gp, op):
+        q.apply_reference_bounds()
+        q.fix_param(7, 7); q.fix_param(7, 8)
+    intr, intr_o = _solve_pair_with_fixed_columns(gp, op, sp, i0, method)
+    for got in (intr, intr_o):
+        assert (got[7, 7:9] == 0.0).all()
+    assert intr[7, 6] != i0[7, 6] and intr[6, 8] != i0[6, 8]
+
+
 @pytest.mark.parametrize("models,one_focal,K", [(("opencv5",) * 4 + ("kb4",), True, 63), (("opencv5", "kb4", "ucm", "kb4", "kb4"), False, 62),
                                                  (("opencv5", "ucm", "eucm", "opencv5", "kb4"), False, 61)])
 def test_five_camera_rigs_at_the_lds_boundary(gpu_ctx, oracle, models, one_focal, K):
